@@ -16,6 +16,14 @@ touched the GPU - relays rank 0's line and exits non-zero if any rank fails; lau
   workload  BASELINE.json configs[1]: 4096x4096 uint16, 1 % sparsity, L1 + LZ4 (d = 16 primary; --depth 12 secondary);
             --config 1..5 = the other BASELINE configurations, --clustered = detector-like events.
   value     frames/s, whole job (all ranks' frames / max-over-ranks time); gb_per_s_in = value * 2*nx*ny.
+  plain run (no --full) only what `value` needs: set-up, W warm-up steps, ONE timed region of exactly K steps (ms_per_step = its
+            time / K), --dump-outputs DIR, the line.  verified, roofline and cpu_baseline are null there.
+  --full    everything below as well: the timed region repeated until --min-seconds (median repeat reported), HIP events around
+            reduce kernels (roofline, stage_ms_per_step), the host-enqueue burst, the records' check against the oracle, the
+            gathered table's check, cpu_baseline, ingest_inclusive and the reader's line.
+  dump      --dump-outputs DIR: rank 0's records of the LAST timed step as float .npy files (dump_outputs(): offsets, metadata rows
+            and the bytes of a fixed, seeded sample of whole records; 48 MiB at most).  The inputs are seeded: same arguments,
+            same files.
   verified  every rank decodes TWO records of every distinct batch of its stack - one inside the batch and its last - with the stock
             library / the oracle's decoders and compares them with the oracle's reduce of those frames (level 2: scipy.ndimage.label);
             gather_verified: every rank's block of the metadata table the last step gathered, on every rank.
@@ -67,23 +75,26 @@ def parse(argv=None):
     ap.add_argument("--device-zlib", action="store_true", help="--scheme 0: both streams of a record made by the device's DEFLATE encoder (RC_SCHEME_ZLIB_DEVICE: zlib streams that "
                     "stdlib zlib expands to the oracle's bytes) instead of the reduce-only pieces for the host's zlib.compress")
     ap.add_argument("--level", type=int, default=1, help="reduction level: 1 (headline), 2 = summary statistics, 3 = bitmap only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--source-bytes", type=int, default=2, choices=[1, 2, 4], help="bytes per source pixel: 2 = uint16 frames (every BASELINE configuration), 1 = uint8 frames (source_bit_depth <= 8: the reference's map_dtype, misc.py:41-49; implies --depth 8 unless given lower), 4 = uint32 frames (> 16 bits; implies --depth 20 unless given above 16); both without the CPU baseline / ingest legs")
     ap.add_argument("--read", action="store_true", help="measure the READER instead: stored frames -> device decode of both streams -> sparse expand (rc_expand_frames)")
     ap.add_argument("--blob-on-device", action="store_true", help="--read: the stored frames' bytes already sit in device memory (the decoders without the link)")
-    ap.add_argument("--kernel-events-every", type=int, default=4, help="HIP events around every k-th reduce-kernel launch of the timed region (roofline.kernel_ms is their mean; "
+    ap.add_argument("--kernel-events-every", type=int, default=4, help="--full: HIP events around every k-th reduce-kernel launch of the timed region (roofline.kernel_ms is their mean; "
                     "1: every launch).  A timing event is a packet of its own between two reduce kernels: with events around every launch the step is 1.3 %% longer "
                     "(same box, profiles/r05_exp12_level2_listed_words_events.log)")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the extra ingest-inclusive measurement (host frames -> part file)")
+    ap.add_argument("--no-ingest", action="store_true", help="--full: skip the extra ingest-inclusive measurement (host frames -> part file)")
     ap.add_argument("--ingest-frames", type=int, default=512, help="frames per pass of the ingest-inclusive measurement (capped at 16 GiB of host memory)")
     ap.add_argument("--no-pipeline", action="store_true", help="plain stream order: a batch's reduce kernel waits for the previous batch's records")
     ap.add_argument("--clevel", type=int, default=1, help="compression_level: 0 = the fast device encoders, >= 1 = the modelled zstd encoder")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="the K-step timed region is repeated until this much time has been measured (>= 3 repeats); the median repeat is reported")
+    ap.add_argument("--min-seconds", type=float, default=2.0, help="--full: the K-step timed region is repeated until this much time has been measured (>= 3 repeats); the median repeat is reported")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI (the product); gloo only to rehearse on a box with fewer GPUs than ranks")
     ap.add_argument("--shared-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --dist-backend gloo; RCCL refuses two ranks on one device)")
     ap.add_argument("--gather-every", type=int, default=0, help="steps per metadata all-gather: 0 = ONE gather per timed region (default - BASELINE: 'RCCL only for the final merged-index gather'), 1 = every step (the form of rounds 1-3), K = every K steps")
     ap.add_argument("--no-collective", action="store_true", help="rehearsal: the ranks only meet at the fences (barrier, max-over-ranks time); no metadata gather - isolates the HOST side of N step loops from the rehearsal backend's host copies")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin each rank to its share of the usable CPUs")
+    ap.add_argument("--full", action="store_true", help="measure and check everything, not only `value` (see the docstring): repeated timed regions, "
+                    "kernel events / roofline, host-enqueue burst, records against the oracle, cpu_baseline, ingest_inclusive, reader")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64")
     pre, _ = ap.parse_known_args(argv)
     if pre.config:
         ap.set_defaults(**CONFIGS[pre.config])
@@ -96,6 +107,8 @@ def parse(argv=None):
         a.no_cpu_baseline = a.no_ingest = True
     if a.shared_gpu and a.dist_backend == "nccl":
         ap.error("--shared-gpu needs --dist-backend gloo")
+    if a.read and a.dump_outputs:
+        ap.error("--dump-outputs dumps the writer path's records; --read has no dump")
     return a
 
 
@@ -514,6 +527,32 @@ def pattern_floor(N, B, k_ms):
             "kernel_over_floor": (round(k_ms / rw, 3) if rw > 0 else None)}
 
 
+DUMP_RECORDS = 8                  # records in the --dump-outputs sample ...
+DUMP_RECORD_BYTES = 12 << 20      # ... and their bytes at most (as float32: 48 MiB)
+
+
+def dump_outputs(out_dir, out, rec, md):
+    """--dump-outputs: what the caller of the timed path holds after the last timed step - its records (uint8 device buffer `out`),
+    their offsets (`rec`, B + 1) and the metadata rows (`md`, B x 3 u32) - as float .npy files in out_dir:
+      record_offsets.npy   float64 [B + 1]
+      record_metadata.npy  float64 [B, 3]
+      record_sample_index.npy  float64 [k]   which records the sample holds: a fixed, seeded choice of DUMP_RECORDS of the B
+      record_sample_bytes.npy  float32 [n]   their bytes, concatenated in index order; each record's first
+                                             DUMP_RECORD_BYTES // k bytes (a record is rarely longer)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rec_h = rec.cpu().numpy()
+    B = rec_h.size - 1
+    pick = np.sort(np.random.default_rng(20261016).choice(B, min(B, DUMP_RECORDS), replace=False))
+    cap = DUMP_RECORD_BYTES // pick.size
+    parts = [out[int(rec_h[z]):min(int(rec_h[z + 1]), int(rec_h[z]) + cap)] for z in pick]
+    sample = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.uint8)
+    np.save(os.path.join(out_dir, "record_offsets.npy"), rec_h.astype(np.float64))
+    np.save(os.path.join(out_dir, "record_metadata.npy"), md.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(out_dir, "record_sample_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "record_sample_bytes.npy"), sample.astype(np.float32))
+
+
 def run_rank(a):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -618,14 +657,15 @@ def run_rank(a):
     ctx.set_pipelined(not a.no_pipeline)  # batch i+1's reduce kernel may overlap batch i's scans / layout / assembly
     step, fence = loop.step, loop.fence
 
-    # The timed region is EXACTLY a.steps steps between two fences (barrier + synchronize on both sides).  It is repeated
-    # (>= 3 times, until --min-seconds of timed work): at 0.5 ms per step a single pass of the driver's --steps 20 lasts 10 ms,
-    # too short for the clocks to settle or for the driver's utilisation sampler to see the GPU.  The MEDIAN repeat is reported.
+    # The timed region is EXACTLY a.steps steps between two fences (barrier + synchronize on both sides).  A plain run times it
+    # once.  --full repeats it (>= 3 times, until --min-seconds of timed work): at 0.5 ms per step a single pass of --steps 20 lasts
+    # 10 ms, too short for the clocks to settle or for a utilisation sampler to see the GPU; the MEDIAN repeat is reported.
     with torch.cuda.stream(stream):
         for i in range(a.warmup):
             step(i)
         ctx.sync()
-        ctx.set_profiling(True, every=a.kernel_events_every)
+        if a.full:
+            ctx.set_profiling(True, every=a.kernel_events_every)
         times, k_ms_list, it, issue = [], [], a.warmup, []
         more = True
         while more:
@@ -634,47 +674,56 @@ def run_rank(a):
             for i in range(a.steps):
                 step(it + i)
             t_issued = time.perf_counter()
+            if a.dump_outputs:   # the metadata rows the last step wrote (before fence() starts the loop's next group)
+                md_last = (loop._group & 1, loop._pos - 1) if loop._pos else ((loop._group - 1) & 1, loop.G - 1)
             fence()
             dt = time.perf_counter() - t0
             issue.append((t_issued - t0) / a.steps)
             it += a.steps
             ctx.sync()  # also raises if the device flagged a batch
-            sums, nbatches = ctx.profile()
-            ctx.set_profiling(True, every=a.kernel_events_every)   # clears the sums for the next repeat
-            assert nbatches == -(-a.steps // a.kernel_events_every)   # every k-th launch of the region carries events, the first included
+            if a.full:
+                sums, nbatches = ctx.profile()
+                ctx.set_profiling(True, every=a.kernel_events_every)   # clears the sums for the next repeat
+                assert nbatches == -(-a.steps // a.kernel_events_every)   # every k-th launch of the region carries events, the first included
+                k_ms_list.append((sums[0] / nbatches, sums[4] / nbatches, [v / nbatches for v in sums]))
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             if use_dist:
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
             times.append(float(t.item()))   # the same list on every rank, so every rank leaves the loop together
-            k_ms_list.append((sums[0] / nbatches, sums[4] / nbatches, [v / nbatches for v in sums]))
-            more = len(times) < 3 or (sum(times) < a.min_seconds and len(times) < 1000)
-        # host side of a step by itself: a short burst into an EMPTY queue (nothing to wait for, no back-pressure), no sync inside
-        ctx.set_profiling(False)
-        burst, enq = min(16, max(a.steps, 1)), []
-        for _ in range(5):
+            more = a.full and (len(times) < 3 or (sum(times) < a.min_seconds and len(times) < 1000))
+        if a.dump_outputs and rank == 0:
+            k, row = md_last
+            dump_outputs(a.dump_outputs, loop.out, loop.rec, loop.md2[k][row * B:(row + 1) * B])
+        if a.full:
+            # host side of a step by itself: a short burst into an EMPTY queue (nothing to wait for, no back-pressure), no sync inside
+            ctx.set_profiling(False)
+            burst, enq = min(16, max(a.steps, 1)), []
+            for _ in range(5):
+                fence()
+                t0 = time.perf_counter()
+                for i in range(burst):
+                    step(it + i)
+                enq.append((time.perf_counter() - t0) / burst)
+                it += burst
             fence()
-            t0 = time.perf_counter()
-            for i in range(burst):
-                step(it + i)
-            enq.append((time.perf_counter() - t0) / burst)
-            it += burst
-        fence()
-    host_enqueue_us = sorted(enq)[len(enq) // 2] * 1e6
     order = sorted(range(len(times)), key=lambda i: times[i])
     mid = order[len(order) // 2]
     dt_max = times[mid]
-    sums = [v * a.steps for v in k_ms_list[mid][2]]
-    nbatches = a.steps
-    issue_us = issue[mid] * 1e6
     last_step = it - 1
     frames_total = world * B * a.steps
     fps = frames_total / dt_max
     rec_h = loop.rec.cpu().numpy()
     assert rec_h[0] == 0 and rec_h[-1] > 0
-    gather_verified = loop.verify_gather()   # collective: every rank's block of the gathered table, on every rank
     gathers_in_region = loop.gathers_issued
+    if a.full:
+        host_enqueue_us = sorted(enq)[len(enq) // 2] * 1e6
+        sums = [v * a.steps for v in k_ms_list[mid][2]]
+        nbatches = a.steps
+        issue_us = issue[mid] * 1e6
+        gather_verified = loop.verify_gather()   # collective: every rank's block of the gathered table, on every rank
+    else:
+        gather_verified = None
 
-    thr_h = dark.cpu().numpy().view(src_dtype).astype(np.uint16 if a.source_bytes < 4 else np.uint32)
     corrupt = os.environ.get("RC_BENCH_CORRUPT_RECORD")          # test switch: one byte of a record flipped before the check
 
     def verify_batch(j, z):
@@ -693,67 +742,50 @@ def run_rank(a):
             print("rank %d: verification of batch %d record %d raised: %r" % (rank, j, z, e), file=sys.stderr)   # through the same steps)
             return False
 
-    # One record of EVERY distinct batch of the stack: the last timed step's records as they stand, then each other batch run once more
-    # through the same loop (same kernels, same buffers; every rank takes the same steps, so the collectives stay matched).
-    checked, verified = [], True
-    try:
-        j_last = last_step % nb
-        zs = [(B // 2 + 7 * k) % max(B - 1, 1) for k in range(nb)]   # one record inside the batch ...
+    # --full: one record of EVERY distinct batch of the stack: the last timed step's records as they stand, then each other batch run once
+    # more through the same loop (same kernels, same buffers; every rank takes the same steps, so the collectives stay matched).
+    checked, verified = [], (True if a.full else None)
+    if a.full:
+        thr_h = dark.cpu().numpy().view(src_dtype).astype(np.uint16 if a.source_bytes < 4 else np.uint32)
+        try:
+            j_last = last_step % nb
+            zs = [(B // 2 + 7 * k) % max(B - 1, 1) for k in range(nb)]   # one record inside the batch ...
 
-        def check_two(j, z):   # ... and the batch's LAST record (behind every other record's bytes: a wrong size anywhere in the batch moves it)
-            ok_all = True
-            for zz in sorted({z, B - 1}):
-                ok1 = verify_batch(j, zz)
-                checked.append({"batch": j, "record": zz, "ok": ok1})
-                ok_all = ok_all and ok1
-            return ok_all
-        verified = check_two(j_last, zs[0]) and verified
-        with torch.cuda.stream(stream):
-            for k in range(1, nb):
-                j = (j_last + k) % nb
-                i_extra = it + ((j - it) % nb)                   # a step index that maps to batch j
-                fence()
-                step(i_extra)
-                fence()
-                ctx.sync()
-                verified = check_two(j, zs[k]) and verified
-    except Exception as e:
-        verified = False
-        print("rank %d: verification raised: %r" % (rank, e), file=sys.stderr)
-        if use_dist:
-            raise            # (a rank that leaves the steps the others take would leave them waiting at a fence)
-    if use_dist:   # every rank checks one of ITS records; the line reports the conjunction
-        v = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
-        dist.all_reduce(v, op=dist.ReduceOp.MIN)
-        verified = bool(int(v.item()) == 1)
+            def check_two(j, z):   # ... and the batch's LAST record (behind every other record's bytes: a wrong size anywhere in the batch moves it)
+                ok_all = True
+                for zz in sorted({z, B - 1}):
+                    ok1 = verify_batch(j, zz)
+                    checked.append({"batch": j, "record": zz, "ok": ok1})
+                    ok_all = ok_all and ok1
+                return ok_all
+            verified = check_two(j_last, zs[0]) and verified
+            with torch.cuda.stream(stream):
+                for k in range(1, nb):
+                    j = (j_last + k) % nb
+                    i_extra = it + ((j - it) % nb)                   # a step index that maps to batch j
+                    fence()
+                    step(i_extra)
+                    fence()
+                    ctx.sync()
+                    verified = check_two(j, zs[k]) and verified
+        except Exception as e:
+            verified = False
+            print("rank %d: verification raised: %r" % (rank, e), file=sys.stderr)
+            if use_dist:
+                raise            # (a rank that leaves the steps the others take would leave them waiting at a fence)
+        if use_dist:   # every rank checks one of ITS records; the line reports the conjunction
+            v = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
+            dist.all_reduce(v, op=dist.ReduceOp.MIN)
+            verified = bool(int(v.item()) == 1)
 
     if rank == 0:
-        k_ms = sums[0] / max(nbatches, 1)
         frame_bytes = N * a.source_bytes        # algorithmic bytes: one read of the frame in its source dtype
-        achieved = B * frame_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        traffic, traffic_note = None, None
-        tpath = os.path.join(REPO, "profiles", "traffic.json")
-        key = "%dx%d_b%d_ppm%d_d%d_s%d%s%s%s%s" % (a.ny, a.nx, B, a.sparsity_ppm, a.depth, a.scheme, "_clustered" if a.clustered else "", {1: "_u8", 2: "", 4: "_u32"}[a.source_bytes],
-                                              "" if a.level == 1 else "_l%d" % a.level, "_devzlib" if a.device_zlib and a.scheme == 0 else "")   # (the reduce kernel of levels 2 / 3 writes other things)
-        if os.path.exists(tpath):
-            traffic = json.load(open(tpath)).get(key, {}).get("reduce_kernel_hbm_bytes_per_launch")
-        if traffic is None:
-            traffic_note = "no PMC pass committed for configuration %s (profiles/traffic.json)" % key
-        else:
-            traffic_note = "PMC (2*FETCH_SIZE + WRITE_SIZE) of a separate rocprofv3 --pmc run of this configuration, profiles/traffic.json"
         result = {
             "metric": "frames/sec + GB/s in, 4096x4096 uint16 @1% sparsity, 1/2/4/8 GPU",
             "value": round(fps, 1), "unit": "frames/s", "gb_per_s_in": round(fps * frame_bytes / 1e9, 1),
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt_max / a.steps * 1e3, 4),
-            "repeats": len(times), "timed_seconds_total": round(sum(times), 3),
-            "ms_per_step_all_repeats": {"min": round(min(times) / a.steps * 1e3, 4), "median": round(dt_max / a.steps * 1e3, 4),
-                                        "max": round(max(times) / a.steps * 1e3, 4)},
+            "repeats": len(times), "timed_seconds_total": round(sum(times), 3), "full": bool(a.full),
             "verified": verified, "records_checked": checked, "gather_verified": gather_verified,
-            # host side of one step (Python loop + ctypes + launches + the collective's enqueue): a burst of steps issued into an empty
-            # queue without any sync; `issue_us_per_step_in_timed_region` is the same loop inside the timed region (includes waiting
-            # for room in the device queue when the host runs ahead)
-            "host_enqueue_us_per_step": round(host_enqueue_us, 1), "issue_us_per_step_in_timed_region": round(issue_us, 1),
-            "host_enqueue_frac_of_step": round(host_enqueue_us / (dt_max / a.steps * 1e6), 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": {1: "u8", 2: "u16", 4: "u32"}[a.source_bytes], "data": "synthetic",
             "config": {
                 "workload": "%s%dx%d %s, %s, L%d + %s, source_bit_depth %d, batch %d frames/GPU/step, %d-frame stack/GPU in HBM" % (
@@ -776,52 +808,75 @@ def run_rank(a):
                 "shared_gpu_rehearsal": bool(a.shared_gpu),
             },
             "rccl_ranks": (dist.get_world_size() if use_dist and backend == "nccl" else (1 if not use_dist else 0)),
-            "roofline": {"bound": "hbm", "kernel": "k_reduce_tiles32" if a.source_bytes == 4 else "k_reduce_tiles", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note,
-                         "traffic_ratio": (round(traffic / (B * frame_bytes), 4) if traffic else None),
-                         "kernel_ms": round(k_ms, 4), "kernel_events_every": a.kernel_events_every, "algorithmic_bytes_per_launch": B * frame_bytes,
-                         "pattern_floor_ms": pattern_floor(N, B, k_ms) if a.source_bytes == 2 else None,
-                         "whole_path_frac": round(fps / world * frame_bytes / 1e9 / HBM_PEAK_GBS, 4)},
-            # only the events the roofline needs are recorded in the timed region (each costs stream time); the full
-            # per-stage split is available with RC_PROFILE_ALL_STAGES=1
-            "stage_ms_per_step": ({"reduce": round(sums[0] / nbatches, 4), "bitmap_codec_kernel": round(sums[1] / nbatches, 4),
-                                   "scan": round(sums[2] / nbatches, 4), "layout_assemble": round(sums[3] / nbatches, 4),
-                                   "total": round(sums[4] / nbatches, 4)} if os.environ.get("RC_PROFILE_ALL_STAGES") else
-                                  {"reduce": round(sums[0] / nbatches, 4), "everything_else": round((sums[4] - sums[0]) / nbatches, 4),
-                                   "total": round(sums[4] / nbatches, 4)}),
+            "roofline": None, "cpu_baseline": None,     # (--full)
         }
-        if world == 1 and not a.no_cpu_baseline:
-            ns = min(32, S)
-            frames_h = stack[:ns].cpu().numpy().view(np.uint16)
-            thr_h = dark.cpu().numpy().view(np.uint16)
-            result["cpu_baseline"] = cpu_baseline(frames_h, thr_h, a.depth, a.scheme, zlib_level=(a.clevel if a.scheme == 0 and a.device_zlib else None))
-        else:
-            result["cpu_baseline"] = None
-        if world == 1 and not a.no_ingest and a.level in (1, 3):
-            try:
-                result["ingest_inclusive"], host_frames = ingest_inclusive(stack, dark, a, nframes=a.ingest_frames)
-                v, _ = ingest_inclusive(stack, dark, a, nframes=a.ingest_frames, validation_frame_gap=10, data=host_frames)   # validation frames ride the same stream (recode_writer.py:402-415)
-                del host_frames
-                result["ingest_inclusive"]["with_validation_frame_gap_10"] = {
-                    "frames_per_s": v["frames_per_s"], "gb_per_s_in": v["gb_per_s_in"], "frames_per_s_min_max": v["frames_per_s_min_max"],
-                    "ratio_to_plain": round(v["frames_per_s"] / max(result["ingest_inclusive"]["frames_per_s"], 1e-9), 3)}
-            except Exception as e:   # an extra: never lets the contract line fail
-                result["ingest_inclusive"] = {"error": repr(e)}
-        if world == 1 and not a.no_ingest and a.level in (1, 3) and a.scheme in (1, 2):
-            # extra, not `value`: the READER's batched path on the same configuration (stored frames in host memory -> device decode of both
-            # streams -> triplets in device memory; bench.py --read prints this as a line of its own)
-            try:
-                import copy
-                ra = copy.copy(a)
-                ra.steps, ra.warmup, ra.min_seconds = 20, 3, 0.5
-                ctx.close()
-                del stack
-                torch.cuda.empty_cache()
-                rl = bench_read(ra, emit=False)
-                result["reader"] = {"frames_per_s_streaming": rl["value"], "frames_per_s_one_call_at_a_time": rl["one_call_at_a_time"]["frames_per_s"],
-                                    "verified": rl["verified"], "what": rl["metric"]}
-            except Exception as e:
-                result["reader"] = {"error": repr(e)}
+        if a.full:
+            k_ms = sums[0] / max(nbatches, 1)
+            achieved = B * frame_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            traffic, traffic_note = None, None
+            tpath = os.path.join(REPO, "profiles", "traffic.json")
+            key = "%dx%d_b%d_ppm%d_d%d_s%d%s%s%s%s" % (a.ny, a.nx, B, a.sparsity_ppm, a.depth, a.scheme, "_clustered" if a.clustered else "", {1: "_u8", 2: "", 4: "_u32"}[a.source_bytes],
+                                                  "" if a.level == 1 else "_l%d" % a.level, "_devzlib" if a.device_zlib and a.scheme == 0 else "")   # (the reduce kernel of levels 2 / 3 writes other things)
+            if os.path.exists(tpath):
+                traffic = json.load(open(tpath)).get(key, {}).get("reduce_kernel_hbm_bytes_per_launch")
+            if traffic is None:
+                traffic_note = "no PMC pass committed for configuration %s (profiles/traffic.json)" % key
+            else:
+                traffic_note = "PMC (2*FETCH_SIZE + WRITE_SIZE) of a separate rocprofv3 --pmc run of this configuration, profiles/traffic.json"
+            result.update({
+                "ms_per_step_all_repeats": {"min": round(min(times) / a.steps * 1e3, 4), "median": round(dt_max / a.steps * 1e3, 4),
+                                            "max": round(max(times) / a.steps * 1e3, 4)},
+                # host side of one step (Python loop + ctypes + launches + the collective's enqueue): a burst of steps issued into an empty
+                # queue without any sync; `issue_us_per_step_in_timed_region` is the same loop inside the timed region (includes waiting
+                # for room in the device queue when the host runs ahead)
+                "host_enqueue_us_per_step": round(host_enqueue_us, 1), "issue_us_per_step_in_timed_region": round(issue_us, 1),
+                "host_enqueue_frac_of_step": round(host_enqueue_us / (dt_max / a.steps * 1e6), 4),
+                "roofline": {"bound": "hbm", "kernel": "k_reduce_tiles32" if a.source_bytes == 4 else "k_reduce_tiles", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note,
+                             "traffic_ratio": (round(traffic / (B * frame_bytes), 4) if traffic else None),
+                             "kernel_ms": round(k_ms, 4), "kernel_events_every": a.kernel_events_every, "algorithmic_bytes_per_launch": B * frame_bytes,
+                             "pattern_floor_ms": pattern_floor(N, B, k_ms) if a.source_bytes == 2 else None,
+                             "whole_path_frac": round(fps / world * frame_bytes / 1e9 / HBM_PEAK_GBS, 4)},
+                # only the events the roofline needs are recorded in the timed region (each costs stream time); the full
+                # per-stage split is available with RC_PROFILE_ALL_STAGES=1
+                "stage_ms_per_step": ({"reduce": round(sums[0] / nbatches, 4), "bitmap_codec_kernel": round(sums[1] / nbatches, 4),
+                                       "scan": round(sums[2] / nbatches, 4), "layout_assemble": round(sums[3] / nbatches, 4),
+                                       "total": round(sums[4] / nbatches, 4)} if os.environ.get("RC_PROFILE_ALL_STAGES") else
+                                      {"reduce": round(sums[0] / nbatches, 4), "everything_else": round((sums[4] - sums[0]) / nbatches, 4),
+                                       "total": round(sums[4] / nbatches, 4)}),
+            })
+            if world == 1 and not a.no_cpu_baseline:
+                ns = min(32, S)
+                frames_h = stack[:ns].cpu().numpy().view(np.uint16)
+                thr_h = dark.cpu().numpy().view(np.uint16)
+                result["cpu_baseline"] = cpu_baseline(frames_h, thr_h, a.depth, a.scheme, zlib_level=(a.clevel if a.scheme == 0 and a.device_zlib else None))
+            else:
+                result["cpu_baseline"] = None
+            if world == 1 and not a.no_ingest and a.level in (1, 3):
+                try:
+                    result["ingest_inclusive"], host_frames = ingest_inclusive(stack, dark, a, nframes=a.ingest_frames)
+                    v, _ = ingest_inclusive(stack, dark, a, nframes=a.ingest_frames, validation_frame_gap=10, data=host_frames)   # validation frames ride the same stream (recode_writer.py:402-415)
+                    del host_frames
+                    result["ingest_inclusive"]["with_validation_frame_gap_10"] = {
+                        "frames_per_s": v["frames_per_s"], "gb_per_s_in": v["gb_per_s_in"], "frames_per_s_min_max": v["frames_per_s_min_max"],
+                        "ratio_to_plain": round(v["frames_per_s"] / max(result["ingest_inclusive"]["frames_per_s"], 1e-9), 3)}
+                except Exception as e:   # an extra: never lets the contract line fail
+                    result["ingest_inclusive"] = {"error": repr(e)}
+            if world == 1 and not a.no_ingest and a.level in (1, 3) and a.scheme in (1, 2):
+                # extra, not `value`: the READER's batched path on the same configuration (stored frames in host memory -> device decode of both
+                # streams -> triplets in device memory; bench.py --read prints this as a line of its own)
+                try:
+                    import copy
+                    ra = copy.copy(a)
+                    ra.steps, ra.warmup, ra.min_seconds = 20, 3, 0.5
+                    ctx.close()
+                    del stack
+                    torch.cuda.empty_cache()
+                    rl = bench_read(ra, emit=False)
+                    result["reader"] = {"frames_per_s_streaming": rl["value"], "frames_per_s_one_call_at_a_time": rl["one_call_at_a_time"]["frames_per_s"],
+                                        "verified": rl["verified"], "what": rl["metric"]}
+                except Exception as e:
+                    result["reader"] = {"error": repr(e)}
         print(json.dumps(result), flush=True)
     ok = (gather_verified is not False)
     if use_dist:
@@ -830,7 +885,7 @@ def run_rank(a):
     ctx.close()
     if not ok:
         raise SystemExit("rank %d: the gathered metadata table does not hold every rank's rows" % rank)
-    if not verified:     # a fast wrong answer is not a result: the line above says verified: false, the exit code says it too
+    if verified is False:     # a fast wrong answer is not a result: the line above says verified: false, the exit code says it too
         raise SystemExit("rank %d: a record failed the check against the oracle (verified: false)" % rank)
 
 

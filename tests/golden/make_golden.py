@@ -26,6 +26,7 @@ Fixture groups:
   G4  512-byte header bytes                    (recode_header.py:58-94, 257-275)
   G5  get_frame_sparse triplets                (pyrecode.cpp:95-119, reader.h:10-68)
   G6  321-byte v0.1 header                     (recode_header.py:27-56, 98-127, 257-275)
+  G12 reader.h's C loops themselves: _bit_pack_pixel_intensities / _unpack_frame_sparse (oracle/_ref/libreader_ref.so)
 """
 import contextlib
 import io
@@ -226,6 +227,36 @@ def g5():
         out[f"g5_{tag}_triplets"] = trip
     np.savez_compressed(os.path.join(OUT, "g5_expand.npz"), **out)
     print("g5:", len(out), "arrays")
+
+
+def g12():
+    """The reference's reader.h C functions, called directly (oracle/_ref/libreader_ref.so, build_ref.sh) on seeded cases: the packed
+    bytes _bit_pack_pixel_intensities writes into a dirty buffer and the triplets _unpack_frame_sparse expands them to."""
+    import ctypes as C
+    ref = C.CDLL(os.path.join(REFBUILD, "libreader_ref.so"))
+    ref._unpack_frame_sparse.restype = C.c_int64
+    ref._unpack_frame_sparse.argtypes = [C.c_uint16, C.c_uint16, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint8]
+    ref._bit_pack_pixel_intensities.restype = C.c_float
+    ref._bit_pack_pixel_intensities.argtypes = [C.c_uint64, C.c_uint32, C.c_uint8, C.c_void_p, C.c_void_p]
+    out = {}
+    rng = np.random.default_rng(9)
+    for k, (ny, nx, d, s) in enumerate([(33, 47, 12, 0.2), (64, 64, 16, 0.01), (10, 130, 9, 0.5), (8, 8, 13, 1.0), (8, 8, 12, 0.0)]):
+        binary = rng.random((ny, nx)) < s
+        vals = rng.integers(0, 65536, int(binary.sum())).astype(np.uint16)
+        nbytes = (vals.size * d + 7) // 8
+        packed = np.full(max(nbytes, 1), 0xAA, np.uint8)                       # dirty buffer: zeroing is part of the spec
+        ref._bit_pack_pixel_intensities(nbytes, vals.size, d, vals.ctypes.data, packed.ctypes.data)
+        bitmap = np.packbits(binary.ravel(), bitorder="little")
+        pk = np.concatenate([packed[:nbytes], np.zeros(8, np.uint8)])
+        buf = np.zeros((max(vals.size, 1), 3), np.uint64)
+        n = ref._unpack_frame_sparse(nx, ny, d, bitmap.ctypes.data, pk.ctypes.data, buf.ctypes.data, 1)
+        out[f"g12_{k}_shape"] = np.array([ny, nx, d])
+        out[f"g12_{k}_bitmap"] = bitmap
+        out[f"g12_{k}_vals"] = vals
+        out[f"g12_{k}_packed"] = packed[:nbytes]
+        out[f"g12_{k}_triplets"] = buf[:n].copy()
+    np.savez_compressed(os.path.join(OUT, "g12_ref_c_loops.npz"), **out)
+    print("g12:", len(out), "arrays")
 
 
 def g6():
@@ -523,7 +554,9 @@ def g11():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "g11":
+    if len(sys.argv) > 1 and sys.argv[1] == "g12":
+        g12()
+    elif len(sys.argv) > 1 and sys.argv[1] == "g11":
         g11()
     elif len(sys.argv) > 1 and sys.argv[1] == "g10":
         g10()
@@ -545,3 +578,4 @@ if __name__ == "__main__":
         g9()
         g10()
         g11()
+        g12()

@@ -220,11 +220,20 @@ def test_g9_other_host_schemes_records_byte_exact(tag, level):
 
 
 def test_against_reference_c_loops_when_built():
-    """oracle/_ref/libreader_ref.so = the reference's own reader.h compiled in place (build_ref.sh)."""
+    """G12: what the reference's own reader.h C loops returned (tests/golden/make_golden.py g12) = the oracle's pack and expand on the
+    same seeded cases.  Where oracle/_ref/libreader_ref.so is built (reader.h compiled in place, build_ref.sh), the live library too."""
     import ctypes as C
+    g12 = load_npz("g12_ref_c_loops.npz")
+    for k in range(5):
+        ny, nx, d = (int(x) for x in g12[f"g12_{k}_shape"])
+        vals, packed = g12[f"g12_{k}_vals"], g12[f"g12_{k}_packed"]
+        assert np.array_equal(orc.bit_pack(vals, d), packed)
+        pk = np.concatenate([packed, np.zeros(8, np.uint8)])
+        got = orc.unpack_frame_sparse(nx, ny, d, g12[f"g12_{k}_bitmap"], pk, 1)
+        assert got.shape[0] == vals.size and np.array_equal(got, g12[f"g12_{k}_triplets"])
     path = os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "libreader_ref.so")
     if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+        return
     ref = C.CDLL(path)
     ref._unpack_frame_sparse.restype = C.c_int64
     ref._unpack_frame_sparse.argtypes = [C.c_uint16, C.c_uint16, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint8]

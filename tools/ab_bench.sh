@@ -6,7 +6,7 @@ for round in 1 2 3; do
   for v in "$@"; do
     if [ $v = main ]; then unset RC_LIB_PATH; else export RC_LIB_PATH=$(pwd)/$v; fi
     echo -n "$(basename $v): "
-    python3 bench.py $ARGS --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
+    python3 bench.py $ARGS --full --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1])
 r = j['roofline']

@@ -3,7 +3,7 @@
 # Two interleaved rounds per configuration; prints frames/s and the reduce kernel's ms per build.
 A=$1; B=$2
 run() { if [ $1 = main ]; then unset RC_LIB_PATH; else export RC_LIB_PATH=$(pwd)/$1; fi; shift
-  python3 bench.py "$@" --steps 20 --warmup 5 --min-seconds 0.7 --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
+  python3 bench.py "$@" --steps 20 --warmup 5 --full --min-seconds 0.7 --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1]); print('%9.0f fps  kernel %.4f ms  step %.4f ms' % (j['value'], j['roofline']['kernel_ms'], j['ms_per_step']), end='')"; }
 while read -r cfg; do

@@ -23,7 +23,7 @@ def run(variant, bench_args):
             env[k] = v
         elif tok:
             env["RC_LIB_PATH"] = os.path.join(REPO, tok)
-    cmd = [sys.executable, "bench.py"] + bench_args + ["--steps", "20", "--warmup", "5", "--min-seconds", "0.7", "--no-cpu-baseline", "--no-ingest"]
+    cmd = [sys.executable, "bench.py"] + bench_args + ["--steps", "20", "--warmup", "5", "--full", "--min-seconds", "0.7", "--no-cpu-baseline", "--no-ingest"]
     p = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     if not lines:

@@ -3,7 +3,7 @@
 # make -C <old tree>/pyrecode_amd/csrc; make -C <old tree>/oracle) against this tree - interleaved rounds per configuration, medians at the end.
 # usage: tools/ab_trees.sh <old tree> <rounds> <<< "one bench.py argument line per configuration"
 OLD=$1; R=${2:-3}
-run() { tree=$1; shift; (cd $tree && python3 bench.py "$@" --steps 20 --warmup 5 --min-seconds 0.7 --no-cpu-baseline --no-ingest 2>/dev/null) | python3 -c "
+run() { tree=$1; shift; (cd $tree && python3 bench.py "$@" --steps 20 --warmup 5 --full --min-seconds 0.7 --no-cpu-baseline --no-ingest 2>/dev/null) | python3 -c "
 import sys, json
 try:
     j = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('%.0f %.4f %.4f %.3f %.0f %s' % (j['value'], j['roofline']['kernel_ms'], j['ms_per_step'], j['roofline']['whole_path_frac'], j['config']['record_bytes_per_frame'], 'ok' if j['verified'] else 'NOT-VERIFIED'))

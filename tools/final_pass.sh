@@ -5,7 +5,7 @@
 T=$1
 OUT=gpurun_out/final_$T
 mkdir -p $OUT
-line() { name=$1; shift; python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; tail -c 700 $OUT/$name.json | head -c 300; echo; }
+line() { name=$1; shift; python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; tail -c 700 $OUT/$name.json | head -c 300; echo; }
 Q="--no-cpu-baseline --no-ingest --min-seconds 1"
 line headline
 line cfg1 --config 1 $Q

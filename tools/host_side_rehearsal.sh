@@ -6,7 +6,7 @@
 OUT=$1; shift
 RANKS=${@:-"2 4 5"}
 mkdir -p $OUT
-COMMON="--stack 64 --steps 100 --warmup 10 --min-seconds 1.0"
+COMMON="--stack 64 --steps 100 --warmup 10 --full --min-seconds 1.0"
 python3 bench.py $COMMON --no-cpu-baseline --no-ingest > $OUT/ranks1.json 2> $OUT/ranks1.err
 for n in $RANKS; do
   python3 bench.py --gpus $n --shared-gpu --dist-backend gloo --no-collective $COMMON > $OUT/ranks${n}_no_collective.json 2> $OUT/ranks${n}_no_collective.err

@@ -5,7 +5,7 @@ set -e
 TAG=$1; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out/kt_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $REPO/bench.py "$@" > $OUT/line.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --full "$@" > $OUT/line.json 2> $OUT/kt.err
 cd $REPO
 python3 tools/summarize_rocprof.py $OUT > $OUT/summary.md
 find $OUT -name "*_kernel_trace.csv" -delete

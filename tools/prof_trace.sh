@@ -3,7 +3,7 @@
 set -e
 REPO=$(pwd); OUT=$REPO/gpurun_out/trace; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --steps 12 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --steps 12 --warmup 3 --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log
 cd $REPO
 f=$(find $OUT -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'

@@ -7,7 +7,7 @@ for round in 1 2; do
   for b in "$@"; do
     export RC_DEV_SKIP_BITS=$b
     echo -n "skip=$b: "
-    python3 bench.py $ARGS --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
+    python3 bench.py $ARGS --full --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1])
 r = j['roofline']

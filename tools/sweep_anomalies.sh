@@ -1,7 +1,8 @@
 #!/bin/bash
 # A sweep over the parameter space for slow paths (one short bench line each): tools/sweep_anomalies.sh
-# (a line's stderr is kept - appended to gpurun_out/sweep_anomalies.err - so that an ERROR row says why)
-run() { echo "== $*" >> gpurun_out/sweep_anomalies.err; timeout -k 10 120 python3 bench.py "$@" --steps 20 --warmup 5 --min-seconds 0.4 --no-cpu-baseline --no-ingest 2>> gpurun_out/sweep_anomalies.err | python3 -c "
+# (a line's stderr is kept - appended to bench_out/sweep_anomalies.err - so that an ERROR row says why)
+mkdir -p bench_out
+run() { echo "== $*" >> bench_out/sweep_anomalies.err; timeout -k 10 120 python3 bench.py "$@" --steps 20 --warmup 5 --full --min-seconds 0.4 --no-cpu-baseline --no-ingest 2>> bench_out/sweep_anomalies.err | python3 -c "
 import sys, json
 try:
     j = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('%-58s %9.0f fps  kernel %.4f  step %.4f  whole %.3f  rec %9.0f %s' % (sys.argv[1], j['value'], j['roofline']['kernel_ms'], j['ms_per_step'], j['roofline']['whole_path_frac'], j['config']['record_bytes_per_frame'], 'ok' if j['verified'] else 'NOT VERIFIED'))

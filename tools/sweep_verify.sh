@@ -1,4 +1,4 @@
-run() { timeout -k 10 120 python3 bench.py "$@" --steps 10 --warmup 3 --min-seconds 0.2 --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
+run() { timeout -k 10 120 python3 bench.py "$@" --steps 10 --warmup 3 --full --min-seconds 0.2 --no-cpu-baseline --no-ingest 2>/dev/null | python3 -c "
 import sys, json
 try:
     j = json.loads(sys.stdin.readlines()[-1]); print('%-66s %9.0f fps  whole %.3f  rec %9.0f %s' % (sys.argv[1], j['value'], j['roofline']['whole_path_frac'], j['config']['record_bytes_per_frame'], 'ok' if j['verified'] else 'NOT VERIFIED'))
