@@ -360,7 +360,7 @@ void launch_gather(const Scratch &sc, const RecordParams &rp, uint32_t B, uint8_
     static const char *wgs_env = RC_KNOB("RC_GATHER_WGS");
     // 64 tiles per item; fewer where that leaves the chip without work (configs[0]: nine 512 x 512 frames are nine items of 64 tiles -
     // nine wavefronts walking 64 tiles each took twice k_assemble's time; with eight tiles per item they are 72)
-    uint32_t tpi = 64;
+    uint32_t tpi = 64;   // (tests/bitphase_cases.py::gather_tpi restates this rule: keep the two in step)
     while (tpi > 8 && (uint64_t)B * ((sc.ntiles + tpi - 1) / tpi) < 1024) tpi >>= 1;
     const uint32_t gpf = (sc.ntiles + tpi - 1) / tpi, nitems = gpf * B;
     uint32_t wgs = wgs_env ? (uint32_t)atoi(wgs_env) : 0u;

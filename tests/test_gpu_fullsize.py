@@ -134,10 +134,11 @@ def test_4096_all_set_frame_is_refused_like_the_reference(env):
         ctx.close()
 
 
-def _full_oracle_compare(env, ny, nx, B, depth, ppm, scheme):
+def _full_oracle_compare(env, ny, nx, B, depth, ppm, scheme, stack=None):
+    """stack: (dark_d, frames_d) made by the caller from _device_stack(seed 7, ppm) - the same event mask, other values"""
     torch, hip, synth, orc = env
     N = ny * nx
-    dark_d, frames_d = _device_stack(torch, hip, 7, B, N, ppm)
+    dark_d, frames_d = stack if stack is not None else _device_stack(torch, hip, 7, B, N, ppm)
     ctx = hip.ReduceContext(nx, ny, depth, 1, 1, 0 if scheme == "zd" else scheme, 1, 0, max_batch=B, device_zlib=scheme == "zd")
     ctx.set_dark(dark_d.data_ptr(), 0)
     cap = int(hip.lib().rc_out_capacity(ctx.handle, B))   # B raw frames: what a batch of legal records cannot exceed
@@ -152,7 +153,8 @@ def _full_oracle_compare(env, ny, nx, B, depth, ppm, scheme):
     frames = frames_d.cpu().numpy().view(np.uint16)
     # generator: device == host mirror (one frame is enough at this size; small sizes are covered elsewhere)
     assert np.array_equal(thr, synth.dark_frame(7, N))
-    assert np.array_equal(frames[2], synth.frames(7, 2, 1, N, ppm, thr)[0])
+    if stack is None:
+        assert np.array_equal(frames[2], synth.frames(7, 2, 1, N, ppm, thr)[0])
     for z in range(B):
         r = out_h[int(rec_h[z]):int(rec_h[z + 1])].tobytes()
         fid, cb, cp, npk = struct.unpack_from("<IIII", r, 0)
@@ -164,6 +166,24 @@ def _full_oracle_compare(env, ny, nx, B, depth, ppm, scheme):
         assert int(np.unpackbits(bitmap).sum()) == nnz
         assert abs(nnz / N - ppm / 1e6) < max(2e-4, 6 * (ppm / 1e6 * (1 - ppm / 1e6) / N) ** 0.5)
     ctx.close()
+
+
+@pytest.mark.parametrize("ny,nx,B,depth,ppm,scheme", [(4096, 4096, 4, 16, 10000, 2), (3710, 3838, 4, 14, 20000, 1)])
+def test_full_range_residuals_full_size(env, ny, nx, B, depth, ppm, scheme):
+    """The event mask of the device generator (k_synth_frames), residuals uniform over [1, 2^depth - 1] instead of its 11 bits: every
+    bit of every field in use at the headline size (LZ4, d = 16) and at the detector format's (zstd, d = 14)."""
+    torch, hip, synth, orc = env
+    N = ny * nx
+    dark_d, frames_d = _device_stack(torch, hip, 7, B, N, ppm)
+    g = torch.Generator(device="cuda").manual_seed(depth)
+    dark32 = dark_d.to(torch.int32) & 0xFFFF
+    mask = (frames_d.to(torch.int32) & 0xFFFF) > dark32
+    vals = torch.randint(1, 1 << depth, (B, N), device="cuda", dtype=torch.int32, generator=g)
+    full = torch.clamp(dark32 + vals, max=65535)
+    frames_d = torch.where(mask, full, frames_d.to(torch.int32) & 0xFFFF).to(torch.int16).contiguous()   # (wraps to the same 16 bits)
+    res = (full - dark32)[mask]
+    assert int(res.max()) > (1 << (depth - 1)) and int((res >> (depth - 1)).sum()) > res.numel() // 4   # the top bit in a quarter or more of the values
+    _full_oracle_compare(env, ny, nx, B, depth, ppm, scheme, stack=(dark_d, frames_d))
 
 
 def test_direct_electron_size_reduce_only_and_round_trip(env):

@@ -1253,7 +1253,7 @@ def test_random_shapes_depths_schemes_fuzz(hip, orc):
             dens = float(rng.choice([0.0, 0.002, 0.05, 0.4, 0.97]))
             nz = int(rng.integers(1, 4))
             dark = rng.integers(50, 200, (ny, nx)).astype(np.uint16)
-            amp = rng.integers(1, 1 << min(d, 15), (nz, ny, nx)).astype(np.uint16)
+            amp = rng.integers(1, 1 << d, (nz, ny, nx)).astype(np.uint16)
             frames = np.where(rng.random((nz, ny, nx)) < dens, dark + amp, (dark * rng.random((nz, ny, nx))).astype(np.uint16)).astype(np.uint16)
             mode = 0 if scheme == 0 else 1
             ctx = hip.ReduceContext(nx, ny, d, level, mode, scheme, 1, 0, max_batch=nz)
@@ -1450,7 +1450,7 @@ def test_tiles_at_the_stage_and_slot_capacities(hip, orc, scheme, clevel, d):
     rng = np.random.default_rng(1000 * scheme + d)
     dark = rng.integers(5, 40, (ny, nx)).astype(np.uint16)
     frames = np.minimum(dark, rng.integers(0, 40, (len(counts), ny, nx))).astype(np.uint16)
-    top = min((1 << d) - 1, 4000)
+    top = (1 << d) - 1
     for z, c in enumerate(counts):
         at = rng.choice(ny * nx, c, replace=False)
         f = frames[z].ravel()

@@ -408,6 +408,8 @@ def test_frames_of_4_gib_and_more_are_refused_before_any_gpu_work():
     with pytest.raises(NotImplementedError):
         _lib.ReduceContext(50000, 50000, 16, 1, 1, 2, 1, 0, max_batch=1)
     assert not L.rc_ctx_create(70000, 70000, 16, 1, 1, 2, 1, 0, 4, C.byref(st)) and st.value == _lib.RC_ERR_BAD_ARG   # nx * ny itself >= 2^32
+    if _lib.device_count() > 0:   # (the refusals above hold everywhere; the last line needs a host without a device)
+        pytest.skip("a device is present: a 46340 x 46340 ctx would allocate ~45 GB there instead of failing with RC_ERR_DEVICE")
     assert not L.rc_ctx_create(46340, 46340, 16, 1, 1, 2, 1, 0, 4, C.byref(st)) and st.value == _lib.RC_ERR_DEVICE    # representable: only the GPU is missing here
 
 
