@@ -19,8 +19,7 @@ struct rc_ctx {
     rc::Scratch sc, sets[2];
     int cur = 0;                          // set the NEXT batch uses
     int last = 0;                         // set of the most recent batch
-    hipStream_t pstream = nullptr;        // carries everything behind the reduce kernel: one of the two below
-    hipStream_t pstream_all = nullptr, pstream_masked = nullptr;
+    hipStream_t pstream = nullptr;        // carries everything behind the reduce kernel
     hipStream_t pstream_b = nullptr;      // two chains (pipelined, level 2): the second stage of the batches on scratch set 1
     hipStream_t last_ps = nullptr;        // the stream the most recent batch's second stage went to
     bool two_chains = false;
@@ -127,16 +126,12 @@ static int alloc_set(rc_ctx *c, rc::Scratch &sc)
     HIP_TRY(hipMalloc((void **)&sc.tile_next, B * T * 4));
     HIP_TRY(hipMalloc((void **)&sc.frame_nnz, B * 4));
     HIP_TRY(hipMalloc((void **)&sc.frame_cbytes, B * 4));
-    HIP_TRY(hipMalloc((void **)&sc.scan_part, B * ((T + 255) / 256) * 32));   // (a row of partials per scan segment; room for segments down to 256 tiles: RC_SCAN_T experiments)
+    HIP_TRY(hipMalloc((void **)&sc.scan_part, B * ((T + 255) / 256) * 32));   // (a row of partials per scan segment: room for segments of 256 tiles, more rows than k_scan_seg's 4096-tile ones need)
     HIP_TRY(hipMalloc((void **)&sc.status, sizeof(BatchStatus)));
     if (c->level != 3) HIP_TRY(hipMalloc((void **)&sc.pix_slots, B * T * TILE_PX * 2 + 64));
     if (c->emit != 0) {
-        if (c->level == 1 && !RC_KNOB("RC_NO_COMBINED_SLOTS")) {   // combined slots (rc_launch.h, Scratch::comb); the knob: A/B runs
-            sc.comb = c->emit == RC_SCHEME_ZSTD ? 2u : 1u;
-            if (const char *e = RC_KNOB("RC_COMB_MODE")) {   // (A/B runs; zstd's blocks still grow behind the reduce kernel: form 1 would put residuals in their way)
-                const uint32_t m = (uint32_t)atoi(e);
-                if (m <= 2 && !(c->emit == RC_SCHEME_ZSTD && m == 1)) sc.comb = m;
-            }
+        if (c->level == 1) {   // combined slots (rc_launch.h, Scratch::comb; profiles/r04_ab_combined_slots.log)
+            sc.comb = c->emit == RC_SCHEME_ZSTD ? 2u : 1u;   // (zstd's blocks still grow behind the reduce kernel: form 1 would put residuals in their way)
             sc.blk_stride = 1536;                                  // 12 lines: the block image (<= 5) + 7 or more lines of residuals
         }
         HIP_TRY(hipMalloc((void **)&sc.blk_slots, B * T * (uint64_t)sc.blk_stride + 256));
@@ -169,44 +164,13 @@ static int ctx_alloc(rc_ctx *c)
     using namespace rc;
     const uint64_t B = c->max_batch;
     RC_ON_DEVICE(c->device);
-    {
-        // Experiment knob: RC_PSTREAM_CUS=n with RC_RSTREAM_EXCL=1 - the ctx's own stream (the reduce kernel, when the caller sets no stream) is
-        // confined to the CUs the second stage is NOT confined to: the two stages share no CU at all.
-        const char *e = RC_KNOB("RC_PSTREAM_CUS");
-        const int ncu = e ? atoi(e) : 0;
-        if (ncu > 0 && ncu < 256 && RC_KNOB("RC_RSTREAM_EXCL")) {
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = ncu; i < 256; ++i) mask[i / 32] |= 1u << (i % 32);
-            if (hipExtStreamCreateWithCUMask(&c->own_stream, 8, mask) != hipSuccess) { (void)hipGetLastError(); c->own_stream = nullptr; }
-        }
-    }
-    if (!c->own_stream) HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    // (a high-priority second-stage stream was measured: no gain with LZ4 or zstd, 2 % slower at 11520x8184 - tools/ab_bench.sh)
-    if (const char *pe = RC_KNOB("RC_PSTREAM_PRIO")) {   // experiment knob: the second stage on a high-priority stream (2: a low-priority one)
-        int lo = 0, hi = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_TRY(hipStreamCreateWithPriority(&c->pstream_all, hipStreamNonBlocking, atoi(pe) == 2 ? lo : hi));
-    } else
-        HIP_TRY(hipStreamCreateWithFlags(&c->pstream_all, hipStreamNonBlocking));
-    {
-        // Experiment knob, off by default.  In pipelined mode the second stage runs next to the following batch's reduce
-        // kernel; its waves (80 VGPRs, latency bound) settle on every SIMD and push out one of the three reduce waves
-        // there (168 VGPRs each).  RC_PSTREAM_CUS=n confines the second stage to the first n CU-mask bits.  Measured on
-        // bench.py, same box: LZ4 123.7 k frames/s unmasked, 126.2 k with n = 104 (96: 125.6-127.6 k, 128: 128.5 k on a
-        // faster box, 64: no gain, spread-out masks: worse) - but zstd, whose second stage also carries the FSE kernel,
-        // drops from 112 k to 103 k: the confined stage becomes the longer one.  +2 % on one codec does not pay for that.
-        const char *e = RC_KNOB("RC_PSTREAM_CUS");
-        const int ncu = e ? atoi(e) : 0;
-        c->pstream_masked = nullptr;
-        if (ncu > 0 && ncu < 256) {
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 0; i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
-            if (hipExtStreamCreateWithCUMask(&c->pstream_masked, 8, mask) != hipSuccess) {
-                (void)hipGetLastError();
-                c->pstream_masked = nullptr;  // not available: pipelined mode uses the unmasked stream
-            }
-        }
-    }
+    HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    // The second-stage stream: a plain one.  Measured and not adopted (same-box A/B):
+    //  - a high-priority stream: no gain with LZ4 or zstd, 2 % slower at 11520x8184 (profiles/r05_exp32_second_stage_stream_priority_no_effect.log);
+    //  - the second stage confined to the first n CUs (a CU-masked stream), so that its waves (80 VGPRs, latency bound) stop pushing out
+    //    one of the three reduce waves on every SIMD: LZ4 123.7 k -> 126.2 k frames/s with n = 104, but zstd, whose second stage also
+    //    carries the FSE kernel, 112 k -> 103 k; the reduce kernel on the remaining CUs besides: slower still (profiles/r04_ab_cu_partition.log).
+    HIP_TRY(hipStreamCreateWithFlags(&c->pstream, hipStreamNonBlocking));
     {
         // (the second chain's stream: created at another priority so that it gets a hardware queue of its own - a plain third stream shared
         // the reduce stream's queue on the default four and cost every configuration 10 %, profiles/r05_exp23_two_chains_shared_queue.log)
@@ -214,7 +178,6 @@ static int ctx_alloc(rc_ctx *c)
         HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
         HIP_TRY(hipStreamCreateWithPriority(&c->pstream_b, hipStreamNonBlocking, hi));
     }
-    c->pstream = c->pstream_all;
     c->last_ps = c->pstream;
     c->stream = c->own_stream;
     HIP_TRY(hipMalloc((void **)&c->sc.thr, c->sc.N * 2));
@@ -346,8 +309,7 @@ RC_EXPORT int rc_ctx_destroy(rc_ctx *c)
     DeviceGuard dev_guard_;
     (void)dev_guard_.enter(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->pstream_all) (void)hipStreamSynchronize(c->pstream_all);
-    if (c->pstream_masked) (void)hipStreamSynchronize(c->pstream_masked);
+    if (c->pstream) (void)hipStreamSynchronize(c->pstream);
     if (c->pstream_b) (void)hipStreamSynchronize(c->pstream_b);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (rc::Scratch &sc : c->sets) {
@@ -376,8 +338,7 @@ RC_EXPORT int rc_ctx_destroy(rc_ctx *c)
     hipEvent_t sync_ev[] = {c->ev_red[0], c->ev_red[1], c->ev_post[0], c->ev_post[1], c->ev_in[0], c->ev_in[1]};
     for (hipEvent_t e : sync_ev)
         if (e) (void)hipEventDestroy(e);
-    if (c->pstream_all) (void)hipStreamDestroy(c->pstream_all);
-    if (c->pstream_masked) (void)hipStreamDestroy(c->pstream_masked);
+    if (c->pstream) (void)hipStreamDestroy(c->pstream);
     if (c->pstream_b) (void)hipStreamDestroy(c->pstream_b);
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (auto &e : c->ev)
@@ -573,7 +534,7 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     c->sc = c->sets[k];
     const rc::Scratch &sc = c->sets[k];
     // (two chains: consecutive batches' second stages on two streams - they overlap each other as well as the reduce kernels)
-    const bool two = c->pipelined && c->two_chains && c->pstream == c->pstream_all;
+    const bool two = c->pipelined && c->two_chains;
     hipStream_t ps = two && k == 1 ? c->pstream_b : c->pstream;
     c->last_ps = ps;
     // the batch two calls ago must have left this set.  (Round 5 tried to skip the wait when hipEventQuery says the event has completed -
@@ -607,21 +568,15 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     HIP_TRY(hipEventRecord(red, s));
     HIP_TRY(hipStreamWaitEvent(ps, red, 0));
     if (c->level == 2) launch_l2(sc, n, c->nx, c->l2_sum, c->depth, ps);   // the tiles' raw values -> their components' statistics (rc_l2.hip)
-#ifdef RC_DEV_SKIP   // development builds only (tools/build_def.sh): leave second-stage kernels out (WRONG records) to see what each costs the
-                     // reduce kernel running next to it - bits: 1 FSE, 2 scans, 4 residual Huffman chain, 8 layout, 16 assemble, 32 gather
-    static const unsigned skip = getenv("RC_DEV_SKIP_BITS") ? (unsigned)atoi(getenv("RC_DEV_SKIP_BITS")) : 0u;
-#else
-    constexpr unsigned skip = 0;
-#endif
     const bool lits_only = c->modelled && (c->h_model->valid & ZM_LITS_ONLY);   // dense maps: no block has sequences, nothing for the FSE chain to do
-    if (c->emit == RC_SCHEME_ZSTD && !(skip & 1) && !lits_only) launch_zstd_fse(sc, n, fitted_seq ? (const void *)&c->d_model->seq : c->d_ztab, fitted_seq, ps);
+    if (c->emit == RC_SCHEME_ZSTD && !lits_only) launch_zstd_fse(sc, n, fitted_seq ? (const void *)&c->d_model->seq : c->d_ztab, fitted_seq, ps);
     if (all_ev) HIP_TRY(hipEventRecord(ev[2], ps));
-    if (!(skip & 2)) launch_scans(sc, n, c->level != 3, c->emit != 0, ps);
+    launch_scans(sc, n, c->level != 3, c->emit != 0, ps);
     if (all_ev) HIP_TRY(hipEventRecord(ev[3], ps));
     // modelled zstd, level 1: the residual stream is laid out flat, Huffman-coded in chunks, and placed behind the bitmap stream
     // (rc_pix_huff.hip); its encoded size is part of the record layout
     const bool pix_huff = c->modelled && c->level == 1 && (c->h_model->valid & 2u) && sc.pixraw;
-    if (pix_huff && !(skip & 4)) {
+    if (pix_huff) {
         rp.pix_mode = 1;
         launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
         launch_pix_huff(sc, n, c->depth, ps);
@@ -640,10 +595,10 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     }
     c->prev_out = out_dev; c->prev_out_cap = out_cap; c->prev_n = n;
     c->prev_rec = reinterpret_cast<const uint8_t *>(rec_off_dev); c->prev_md = reinterpret_cast<const uint8_t *>(md_dev);
-    if (!(skip & 8)) launch_layout(sc, rp, n, out_cap, rec_off_dev, md_dev, ps);
-    if (!(skip & 16)) launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
+    launch_layout(sc, rp, n, out_cap, rec_off_dev, md_dev, ps);
+    launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
     ++c->batch_seq;
-    if (pix_huff && !(skip & 32)) launch_pix_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
+    if (pix_huff) launch_pix_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
     if (ev) HIP_TRY(hipEventRecord(ev[4], ps));
     if (two && c->post_pending[k ^ 1]) HIP_TRY(hipStreamWaitEvent(ps, c->ev_post[k ^ 1], 0));   // batches still COMPLETE in order
     HIP_TRY(hipEventRecord(c->ev_post[k], ps));
@@ -675,7 +630,7 @@ RC_EXPORT int rc_reduce_compress_batch_async(rc_ctx *c, const void *frames_dev, 
 // cannot hold it keeps ONE chain - a few per cent slower (rc_api.hip, "two chains"), not an error.  The streams are drained when this runs.
 static void l2_second_chain(rc_ctx *c)
 {
-    if (c->level != 2 || c->two_chains || RC_KNOB("RC_ONE_CHAIN")) return;
+    if (c->level != 2 || c->two_chains) return;
     const uint64_t B = c->max_batch, ids = (uint64_t)c->sc.ntiles * rc::TILE_PX;
     if (!c->d_l2_node[1]) {
         bool ok = hipMalloc((void **)&c->d_l2_node[1], B * ids * 8) == hipSuccess && hipMemset(c->d_l2_node[1], 0, B * ids * 8) == hipSuccess &&
@@ -698,11 +653,10 @@ RC_EXPORT int rc_ctx_set_pipelined(rc_ctx *c, int on)
 {
     if (!c) return fail(RC_ERR_BAD_ARG, "ctx is NULL");
     RC_ON_DEVICE(c->device);
-    HIP_TRY(hipStreamSynchronize(c->pstream));  // the second stage changes streams: drain the old one first
+    HIP_TRY(hipStreamSynchronize(c->pstream));  // drain both: two chains on / off move set 1's second stage between the streams (l2_second_chain relies on it)
     HIP_TRY(hipStreamSynchronize(c->pstream_b));
     if (on) l2_second_chain(c);
     c->pipelined = on != 0;
-    c->pstream = (c->pipelined && c->pstream_masked) ? c->pstream_masked : c->pstream_all;
     return RC_OK;
 }
 RC_EXPORT int rc_ctx_wait_results(rc_ctx *c, void *hip_stream)
@@ -870,23 +824,19 @@ RC_EXPORT int rc_pipe_submit(rc_ctx *c, uint32_t slot, const void *frames_host, 
         if (r != RC_OK) return r;
     }
     if (!c->pipelined) {   // the streaming form always lets consecutive batches overlap
-        HIP_TRY(hipStreamSynchronize(c->pstream));
+        HIP_TRY(hipStreamSynchronize(c->pstream));   // drain both: two chains on / off move set 1's second stage between the streams (l2_second_chain relies on it)
         HIP_TRY(hipStreamSynchronize(c->pstream_b));
         l2_second_chain(c);
         c->pipelined = true;
-        c->pstream = c->pstream_masked ? c->pstream_masked : c->pstream_all;
     }
     // Page-locked (or registered) frames are read by the reduce kernel IN PLACE, over the link: every frame byte is needed
     // exactly once, by wide nontemporal loads, so a copy into device memory first would only add a pass (and the copy
-    // engines moved 26-31 GB/s here where the kernel's own reads move what the link gives).  RC_PIPE_COPY=1 forces the copy.
+    // engines moved 26-31 GB/s where the kernel's own reads move what the link gives).
     const void *fdev = nullptr;
-    static const bool force_copy = RC_KNOB("RC_PIPE_COPY") != nullptr;
-    if (!force_copy) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, frames_host) == hipSuccess) {
-            if (a.type == hipMemoryTypeHost && a.devicePointer) fdev = a.devicePointer;
-        } else (void)hipGetLastError();
-    }
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, frames_host) == hipSuccess) {
+        if (a.type == hipMemoryTypeHost && a.devicePointer) fdev = a.devicePointer;
+    } else (void)hipGetLastError();
     p.zero_copy = fdev != nullptr;
     if (!fdev) {
         HIP_TRY(hipMemcpyAsync(p.d_in, frames_host, (uint64_t)n * c->sc.N * c->src_bytes, hipMemcpyHostToDevice, c->copy_stream));

@@ -16,7 +16,7 @@
 //   emit:   sequence-major, one sequence (literals + match) per lane: bit sizes -> one wave scan -> every lane shifts its codes into
 //           a 64-bit accumulator and ORs whole dwords into the zeroed LDS image (LDS atomics; neighbouring lanes share a dword).
 // Serial restatement judged by stdlib zlib: tests/deflate_block_model.py, tests/test_deflate_format_cpu.py; the device's bytes equal
-// the model's tile for tile (tests/test_gpu_parity.py).
+// the model's tile for tile (tests/test_gpu_deflate.py).
 // The stream's Adler-32 (of the UNcompressed map) comes from per-tile partials left here: see deflate_adler_word.
 #pragma once
 #include "rc_lz4_block.h"

@@ -3,17 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Experiment knobs read from the environment exist only in development builds (-DRC_DEV_KNOBS: tools/build_def.sh); in the product every
-// RC_KNOB(...) is a null pointer at compile time.  (Switches that tests use and that cannot produce a wrong record - RC_REDUCE_GUARDED_LOADS,
-// RC_ZSTD_LITS_ALWAYS / RC_ZSTD_SEQ_ALWAYS - and plain tuning / measurement settings - RC_DEVICE, RC_DECODE_THREADS,
-// RC_READ_THREADS, RC_PROFILE_ALL_STAGES, RC_READ_TIMING, RC_READ_SERIAL - stay ordinary getenv calls.)
-#ifdef RC_DEV_KNOBS
-#include <cstdlib>
-#define RC_KNOB(name) getenv(name)
-#else
-#define RC_KNOB(name) (static_cast<const char *>(nullptr))
-#endif
-
 namespace rc {
 
 // ---- geometry -----------------------------------------------------------------------------------
@@ -28,10 +17,7 @@ constexpr int R = 8;                       // 16-byte loads per lane per frame-t
 constexpr int GROUP_PX = 64 * 8;           // 512
 constexpr int TILE_PX = R * GROUP_PX;      // 4096 pixels = 8 KiB of uint16
 constexpr int TILE_BM = TILE_PX / 8;       // 512 bitmap bytes per tile
-#ifndef RC_SLOT_PX
-#define RC_SLOT_PX TILE_PX
-#endif
-constexpr int SLOT_PX = RC_SLOT_PX;         // uint16 values between two tiles' residual slots (experiments: a denser stride; the product: one slot = one tile's worst case)
+constexpr int SLOT_PX = TILE_PX;           // uint16 values between two tiles' residual slots: one slot = one tile's worst case (profiles/r04_ab_slot_stride.log)
 constexpr int BLK_SLOT = TILE_BM + 128;    // per-tile scratch slot for an encoded block (4-byte size word + payload), 5 x 128-byte lines
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -114,17 +114,10 @@ __device__ __forceinline__ ResidGeom resid_geom(uint32_t coff, uint32_t cnt, uin
 // reduce wave (128) does, and what the reduce kernel's 15 waves leave free on a CU is one such slot.  Same-box A/B
 // (profiles/r05_exp3_gather_variants.log): 4 rounds / 64 registers ahead of 4 / 74, 8 / 110 and 12 / 125 on the headline and the
 // detector-like stack (+1 %); the d-bit form needs a few registers more per round, so it takes 3.
-#ifndef RC_GATHER_U
-#define RC_GATHER_U 4
-#endif
-#ifndef RC_GATHER_UB
-#define RC_GATHER_UB 3
-#endif
-#ifndef RC_GATHER_WPE
-#define RC_GATHER_WPE 8   // waves per SIMD the register allocation aims at (8: at most 64 VGPRs)
-#endif
+constexpr int GATHER_U = 4, GATHER_UB = 3;   // rounds in flight: byte-aligned / d-bit residuals
+constexpr int GATHER_WPE = 8;                // waves per SIMD the register allocation aims at (8: at most 64 VGPRs)
 template <bool BITS, int U, bool ADLER>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RC_GATHER_WPE))) void k_gather(GatherArgs sc, RecordParams rp, uint8_t *__restrict__ out, const uint64_t *__restrict__ rec_off,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))) void k_gather(GatherArgs sc, RecordParams rp, uint8_t *__restrict__ out, const uint64_t *__restrict__ rec_off,
                                                uint32_t lz4f_hdr_bitmap, uint32_t lz4f_hdr_pix, uint32_t batch_seq, uint32_t gpf, uint32_t nitems, uint32_t tpi)
 {
     if (sc.status->code != 0) {   // (the batch's last kernel remembers the first failure across asynchronously enqueued batches)
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RC_GATHER_WP
             // the item's sums -> the frame's accumulators (zeroed by k_layout); k_zlib_finish, behind this kernel, turns them into the trailers.
             // Relaxed device-scope adds and NO fence: a "last item writes the trailers" form needs a release fence per item, and on this chip
             // a device-scope release writes the XCD's whole L2 back - 4096 of them per batch took 230 us and stretched the reduce kernel
-            // running next to them from 0.53 to 0.72 ms (profiles/r06_exp1_trailers.md).
+            // running next to them from 0.53 to 0.72 ms (same-box measurement while the encoder was written; no log of it was kept).
             const uint32_t aux = have ? sc.blk_aux[frow + t] : 0u;
             const uint32_t tA0 = wave_last(wave_incl_scan(aux & 0xFFFFu)), tW0 = wave_last(wave_incl_scan(aux >> 16));
             const uint32_t tA1 = wave_last(wave_incl_scan(ad.A % ADLER_P)), tW1 = wave_last(wave_incl_scan(ad.W));
@@ -356,26 +349,23 @@ __global__ __launch_bounds__(64) void k_zlib_finish(GatherArgs sc, RecordParams 
 void launch_gather(const Scratch &sc, const RecordParams &rp, uint32_t B, uint8_t *out, const uint64_t *rec_off, uint32_t hdr_bitmap, uint32_t hdr_pix,
                    uint32_t batch_seq, hipStream_t s)
 {
-    // a one-wave workgroup per item of 64 tiles (RC_GATHER_WGS, development builds: fewer workgroups, each walking several items)
-    static const char *wgs_env = RC_KNOB("RC_GATHER_WGS");
+    // a one-wave workgroup per item (profiles/r05_exp2_gather_grid_sizes.log: fewer workgroups, each walking several items, were no faster);
     // 64 tiles per item; fewer where that leaves the chip without work (configs[0]: nine 512 x 512 frames are nine items of 64 tiles -
     // nine wavefronts walking 64 tiles each took twice k_assemble's time; with eight tiles per item they are 72)
     uint32_t tpi = 64;   // (tests/bitphase_cases.py::gather_tpi restates this rule: keep the two in step)
     while (tpi > 8 && (uint64_t)B * ((sc.ntiles + tpi - 1) / tpi) < 1024) tpi >>= 1;
-    const uint32_t gpf = (sc.ntiles + tpi - 1) / tpi, nitems = gpf * B;
-    uint32_t wgs = wgs_env ? (uint32_t)atoi(wgs_env) : 0u;
-    if (wgs == 0 || wgs > nitems) wgs = nitems;
+    const uint32_t gpf = (sc.ntiles + tpi - 1) / tpi, nitems = gpf * B, wgs = nitems;
     const GatherArgs ga{sc.blk_slots, sc.bitmap, sc.pix_slots, sc.blk_size, sc.blk_off, sc.tile_cnt, sc.tile_off, sc.tile_next, sc.frame_nnz, sc.frame_cbytes,
                         sc.frame_pbytes, sc.blk_aux, sc.zl_acc, sc.pixraw, sc.status, sc.first_err, sc.nb, sc.nb_stride, sc.pixraw_stride, sc.ntiles, sc.blk_stride, sc.pix_slot_bytes, sc.comb};
     const bool bits = rp.level == 1 && rp.depth % 8 != 0;
     if (rp.emit == EMIT_DEFLATE) {   // (the zlib streams' Adler-32 is summed up on the way: the ADLER instantiations)
-        if (bits) hipLaunchKernelGGL((k_gather<true, RC_GATHER_UB - 1, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
-        else hipLaunchKernelGGL((k_gather<false, RC_GATHER_U, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
+        if (bits) hipLaunchKernelGGL((k_gather<true, GATHER_UB - 1, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
+        else hipLaunchKernelGGL((k_gather<false, GATHER_U, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
         if (rp.pix_mode != 1) hipLaunchKernelGGL(k_zlib_finish, dim3((B + 63) / 64), dim3(64), 0, s, ga, rp, out, rec_off, B);
     } else if (bits)
-        hipLaunchKernelGGL((k_gather<true, RC_GATHER_UB, false>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
+        hipLaunchKernelGGL((k_gather<true, GATHER_UB, false>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
     else
-        hipLaunchKernelGGL((k_gather<false, RC_GATHER_U, false>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
+        hipLaunchKernelGGL((k_gather<false, GATHER_U, false>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
 }
 
 }  // namespace rc

@@ -1,6 +1,9 @@
 // rc_host.h - host-side plumbing shared by the translation units behind the C ABI (rc_api.hip: contexts and seam 1;
 // rc_reader.hip: the batched reader; rc_codec_api.hip: the stateless codec seams): status / error text, device guard, device
 // scratch helpers, and the per-GPU utility context the stateless entry points share.  The few globals are defined in rc_api.hip.
+// The library has no experiment switches.  What it reads from the environment are settings that tests use and that cannot produce a
+// wrong record - RC_REDUCE_GUARDED_LOADS, RC_ZSTD_LITS_ALWAYS / RC_ZSTD_SEQ_ALWAYS - and plain tuning / measurement settings - RC_DEVICE,
+// RC_DECODE_THREADS, RC_READ_THREADS, RC_PROFILE_ALL_STAGES, RC_READ_TIMING, RC_READ_SERIAL.
 #pragma once
 #include <hip/hip_runtime.h>
 

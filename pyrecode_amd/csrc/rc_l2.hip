@@ -490,12 +490,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void k_
 void launch_l2(const Scratch &sc, uint32_t B, uint32_t nx, uint32_t use_sum, uint32_t depth, hipStream_t s)
 {
     const uint32_t gpf = (sc.ntiles + 63) / 64, nitems = gpf * B;
-    static const char *wgs_env = RC_KNOB("RC_L2_WGS"), *lds_env = RC_KNOB("RC_L2_DYNLDS");   // (experiments: persistent grids, extra LDS per workgroup)
-    const uint32_t grid = wgs_env ? min(nitems, (uint32_t)atoi(wgs_env)) : nitems, dyn = lds_env ? (uint32_t)atoi(lds_env) : 0u;
-    hipLaunchKernelGGL(k_l2_dir, dim3(grid), dim3(64), 0, s, sc, nx, gpf, nitems);
-    hipLaunchKernelGGL(k_l2_link, dim3(grid), dim3(64), dyn, s, sc, nx, gpf, nitems);
-    hipLaunchKernelGGL(k_l2_stats, dim3(grid), dim3(64), 0, s, sc, use_sum, gpf, nitems);
-    hipLaunchKernelGGL(k_l2_emit, dim3(grid), dim3(64), dyn, s, sc, use_sum, depth, gpf, nitems);
+    // a one-wave workgroup per item, no dynamic LDS (persistent grids and more LDS per workgroup: profiles/r05_exp20_level2_lds_room.log)
+    hipLaunchKernelGGL(k_l2_dir, dim3(nitems), dim3(64), 0, s, sc, nx, gpf, nitems);
+    hipLaunchKernelGGL(k_l2_link, dim3(nitems), dim3(64), 0, s, sc, nx, gpf, nitems);
+    hipLaunchKernelGGL(k_l2_stats, dim3(nitems), dim3(64), 0, s, sc, use_sum, gpf, nitems);
+    hipLaunchKernelGGL(k_l2_emit, dim3(nitems), dim3(64), 0, s, sc, use_sum, depth, gpf, nitems);
 }
 
 // ---- validation frames (reference recode_writer.py:402-415): the dose-rate count on the streaming path ---------------------

@@ -24,9 +24,6 @@ __device__ unsigned long long g_phase[16];
 
 namespace rc {
 
-// Profiling builds only (tools/build_ablate.sh): -DRC_ABLATE=<bits> drops one kind of global store of the reduce kernel while
-// keeping every computation alive (a value is "stored" only if it equals a magic number).
-//   1: residual lines   2: encoded block lines   4: the 4-byte count / size stores
 // -DRC_PHASE_TIMING (tools/build_def.sh): lane 0 of every wavefront adds the s_memtime cycles of each phase of reduce_one_frame to
 // g_phase[] (rc_debug_phases reads and clears them).  s_memtime waits for the wave's outstanding LDS / scalar traffic, so the phases do
 // not overlap as they do in the product build: the SHARES are what the numbers are good for.
@@ -39,18 +36,7 @@ namespace rc {
 #define RC_PHASE_BEGIN
 #define RC_PHASE(i) do { } while (0)
 #endif
-#ifndef RC_BZ
-#define RC_BZ 4   // frames a wavefront keeps its tile (and the threshold registers) for
-#endif
-#ifndef RC_ABLATE
-#define RC_ABLATE 0
-#endif
-#ifndef RC_FUSED12
-#define RC_FUSED12 1   // d = 12: compaction and bit packing in one step (compact_pack12); 0 = compact, then pack_stage (A/B builds)
-#endif
-constexpr bool FUSED12 = RC_FUSED12 != 0;
-__device__ uint32_t g_ablate_sink;
-#define RC_ST(bit, lhs, v) do { if (RC_ABLATE & (bit)) { if ((uint32_t)(v) == 0x9E3779B9u) g_ablate_sink = 1; } else { lhs = (v); } } while (0)
+constexpr int REDUCE_BZ = 4;   // frames a wavefront keeps its tile (and the threshold registers) for
 
 __device__ __forceinline__ uint32_t pk_sub_sat_u16(uint32_t a, uint32_t b)
 {
@@ -151,7 +137,7 @@ __device__ __forceinline__ typename Src<SB>::X load8(const typename Src<SB>::T *
 // needs to cover the loads only: `s_waitcnt vmcnt(k)` with k = the number of store instructions issued behind them.  The
 // compiler cannot know k (the stores sit in loops) and waits with vmcnt(0), i.e. for the stores as well - under a saturated
 // read stream a store's acknowledgement takes as long as a load, and that whole latency was exposed once per frame
-// (0.445 ms; 0.324 ms with every store dropped, everything else kept: tools/prof_ablate.sh, profiles/r02_reduce_stores.md).
+// (0.445 ms; 0.324 ms with every store dropped, everything else kept: profiles/r02_reduce_stores.md).
 // So the steady-state loads are issued by inline assembly (invisible to the compiler's wait insertion), flush_pending counts
 // the store instructions it issues, and vm_wait_loads waits with exactly that k.
 // Where the stores are issued matters as well (same box, LZ4, 64 frames): at the end of the frame's processing 0.428 ms;
@@ -250,10 +236,7 @@ __device__ __forceinline__ void vm_wait_loads(uint32_t later, X (&x)[R])
 // lane); sparse tiles are compacted from there into `out`, tiles with more than STAGE_CAP set pixels are compacted inside `val`,
 // group by group (compact_dense_in_place).  STAGE_CAP = 256 (6.25 % of a tile) is what lets FIVE workgroups of
 // three waves share a CU's 160 KB: 3 x (this + Lz4Lds) = 31.9 KB.
-#ifndef RC_STAGE_CAP
-#define RC_STAGE_CAP 256
-#endif
-constexpr int STAGE_CAP = RC_STAGE_CAP;   // (experiments: a smaller stage - 16 waves per CU)
+constexpr int STAGE_CAP = 256;
 struct __attribute__((aligned(16))) WaveStage {
     uint16_t val[TILE_PX];
     uint16_t out[STAGE_CAP];
@@ -325,15 +308,13 @@ __device__ __forceinline__ uint32_t flush_pending(const Pending &p, uint32_t til
             else { q1 = ro16; q0 = ((ro16 + r16 + 7u) & ~7u) - ro16; }              // ONE run: block units, then residual units up to the line's end
         }
     }
-    if (!(RC_ABLATE & 1) && !(RC_ABLATE & 2)) { if (q0 + q1) nst += store_lines2(s0, d0, q0, s1, d1, q1); }
-    else if (!(RC_ABLATE & 1)) { if (q0) nst += store_lines2(s0, d0, q0, s1, d1, 0); }
-    else if (!(RC_ABLATE & 2)) { if (q1) nst += store_lines2(s1, d1, q1, s0, d0, 0); }
+    if (q0 + q1) nst += store_lines2(s0, d0, q0, s1, d1, q1);
     if (KEEP_BITMAP) {
         *reinterpret_cast<u32x2 *>(bitmap + (uint64_t)p.f * nb_stride + (uint64_t)tile * TILE_BM + lane * 8) = p.own;
         nst += 1;
     }
     // the 4-byte results: lane 0 the count, lane 1 the block's size word, one instruction
-    if ((LEVEL1 || CODEC) && !(RC_ABLATE & 4)) {
+    if (LEVEL1 || CODEC) {
         const uint32_t word = CODEC == 1 || CODEC == 3 ? p.csize : bsz;   // zstd: the tokenizer's word (k_zstd_fse finishes the block)
         // (deflate: one lane more, the tile's Adler-32 partials)
         if (LEVEL1 && CODEC == 5) {
@@ -401,7 +382,8 @@ __device__ __forceinline__ void compact_dense_in_place(WaveStage *st, const uint
 // its place in the stream and ORed into the zeroed stage (LDS atomics; neighbouring lanes share a dword).  The round loop is
 // wave-uniform: it runs while ANY lane has values left - two rounds at 5 % density where the value-at-a-time loop (above all its
 // serial LDS round trips, then pack_stage's own pass over the compact values) made `compaction + pack` the second longest phase of a
-// wave (profiles/r03_reduce_phase_shares.md: 2856 of 9904 ticks at 11520 x 8184, 5 %).  `out`: the wave's 512-byte stage = 341 fields.
+// wave (profiles/r03_reduce_phase_shares.md: 2856 of 9904 ticks at 11520 x 8184, 5 %; same-box A/B: profiles/r04_ab_fused12.log).
+// `out`: the wave's 512-byte stage = 341 fields.
 constexpr uint32_t FUSED12_CAP = (uint32_t)(STAGE_CAP * 16 / 12);   // 12-bit fields the stage holds
 __device__ __forceinline__ void compact_pack12(WaveStage *st, const u32x2 &own, uint32_t exc, uint32_t cnt)
 {
@@ -519,7 +501,7 @@ __device__ __forceinline__ void reduce_one_frame(typename Src<SB>::X (&x)[R], co
         const uint32_t inc = wave_incl_scan(cnt);
         const uint32_t wave_total = wave_last(inc);
         bool packed = false;
-        if (FUSED12 && pend.depth == 12 && wave_total <= FUSED12_CAP) {
+        if (pend.depth == 12 && wave_total <= FUSED12_CAP) {
             if (wave_total) compact_pack12(st, pend.own, inc - cnt, cnt);
             packed = true;
         } else if (wave_total <= (uint32_t)STAGE_CAP) {
@@ -619,9 +601,6 @@ __global__ __launch_bounds__(64 * RWAVES) __attribute__((amdgpu_waves_per_eu((AL
                                                        BatchStatus *__restrict__ status, ZmParams zm, uint32_t blk_stride, uint32_t comb,
                                                        uint32_t *__restrict__ blk_aux)
 {
-#ifdef RC_REDUCE_PRIO
-    __builtin_amdgcn_s_setprio(RC_REDUCE_PRIO);   // (experiment: the reduce kernel's waves in front of the second stage's at the issue arbiter)
-#endif
     // first kernel of a batch: clears the batch's status word (written later by k_layout / the level-2 kernels)
     if (blockIdx.x == 0 && threadIdx.x == 0) { status->code = 0; status->frame = 0; status->total = 0; }
     __shared__ uint16_t s_code[CODEC == 3 ? 256 : 2];                                           // modelled zstd: Huffman code table
@@ -680,14 +659,11 @@ __global__ __launch_bounds__(64 * RWAVES) __attribute__((amdgpu_waves_per_eu((AL
     flush_pending<LEVEL1, CODEC, KEEP_BITMAP>(pend, tile, n_blk, bitmap, nb_stride, pix_slots, tile_cnt, blk_slots, blk_size, lz, st, blk_stride, comb, blk_aux);
 }
 
-#ifndef RC_RW_ALT
-#define RC_RW_ALT 3   // waves per workgroup of the smaller form (experiments: 2)
-#endif
 template <int BZ, bool AL, bool L1, int CODEC, bool KEEP, bool RAW, int SB>
 static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames, uint32_t B, uint32_t depth, hipStream_t s, hipStream_t s_tail)
 {
     const uint32_t ngroups = (B + BZ - 1) / BZ;
-    // Workgroup size, measured (bench.py, pipelined, same box; tools/build_def.sh + tools/ab_bench.sh).  With ONE wavefront per
+    // Workgroup size, measured (bench.py, pipelined, same-box A/B).  With ONE wavefront per
     // workgroup a retiring wavefront frees exactly what the next one needs on its SIMD, and the kernel no longer slows down next to
     // the second stage of the previous batch (11520x8184 5 %: 0.67 ms instead of 0.81; LZ4 1 %: 0.43 instead of 0.46) - because the
     // second stage, whose workgroups need several free slots of one CU at once, is then starved until the reduce kernel has
@@ -700,14 +676,13 @@ static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames
     const ZmParams zm{reinterpret_cast<const uint16_t *>(sc.zm_lit_code), sc.zm_valid, sc.zm_budget, sc.zm_seq_bits};
     const uint32_t comb = (L1 && !RAW && CODEC) ? sc.comb : 0u;   // (level 2 keeps raw values in pix_slots: rc_l2.hip reads them there)
     // Workgroups of THREE waves let five of them (15 waves) share a CU's LDS where four-wave workgroups fit three (12 waves).  Same-box
-    // A/B against the two-register-set kernel of round 2 (tools/ab_configs.sh): LZ4 level 1 +1.3..3.5 %, d = 12 +4.5 %, 11520 x 8184
+    // A/B against the two-register-set kernel of round 2 (profiles/r04_ab_waves.log): LZ4 level 1 +1.3..3.5 %, d = 12 +4.5 %, 11520 x 8184
     // zstd +4.5 %; level 3 / mode 0 (nothing to gain from LDS, three-wave workgroups cost 2-4 %) and the configurations whose second
     // stage is long next to the following batch's reduce kernel (zstd at 4096^2, level 2, blosc: the STEP got 1-6 % longer although the
     // kernel got 5 % shorter) keep four-wave workgroups.
-    static const char *rw_env = RC_KNOB("RC_REDUCE_WG_WAVES");   // (experiments: 3 or 4)
     // (modelled zstd whose blocks carry literals only - dense maps, rc_zstd_model.h - has no FSE pass behind the reduce kernel: its
     // second stage is as short as LZ4's, and three-wave workgroups gain 0.5-3 % there as well)
-    const bool three = rw_env ? atoi(rw_env) == 3 : (L1 && !RAW && CODEC != 5 && (CODEC == 2 || CODEC == 4 || sc.ntiles > 8192 || (CODEC == 3 && (sc.zm_valid & ZM_LITS_ONLY))));
+    const bool three = L1 && !RAW && CODEC != 5 && (CODEC == 2 || CODEC == 4 || sc.ntiles > 8192 || (CODEC == 3 && (sc.zm_valid & ZM_LITS_ONLY)));
     auto go = [&](auto rw) {
         constexpr int RW = decltype(rw)::value;
         auto grid_for = [&](uint32_t nt) { return (((nt + RW - 1) / RW + 7) / 8) * 8 * ngroups; };
@@ -729,7 +704,7 @@ static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames
         }
     };
     if constexpr (SB == 2) {
-        if (three) { go(std::integral_constant<int, RC_RW_ALT>{}); return; }
+        if (three) { go(std::integral_constant<int, 3>{}); return; }   // (two-wave workgroups: profiles/r04_ab_two_wave_workgroups.log)
     }
     go(std::integral_constant<int, 4>{});   // (uint8 frames: four-wave workgroups only - half the instantiations)
 }
@@ -743,9 +718,6 @@ static void launch_reduce_c(const Scratch &sc, const typename Src<SB>::T *frames
         if (keep) launch_reduce_t<BZ, AL, L1, C, true, RAW, SB>(sc, frames, B, depth, s, s_tail);                \
         else if (!RAW && C != 0) launch_reduce_t<BZ, AL, L1, C, false, false, SB>(sc, frames, B, depth, s, s_tail); \
     } while (0)
-#ifdef RC_DEV_ONLY_CODEC   // (development: one codec's instantiations only - a translation unit that compiles in a quarter of the time, for reading its ISA)
-    if (codec == RC_DEV_ONLY_CODEC) RC_CODEC(RC_DEV_ONLY_CODEC);
-#else
     if (codec == 2) RC_CODEC(2);
     else if (codec == 4) RC_CODEC(4);
     else if (codec == 1) RC_CODEC(1);
@@ -753,7 +725,6 @@ static void launch_reduce_c(const Scratch &sc, const typename Src<SB>::T *frames
     else if (codec == 8) RC_CODEC(8);
     else if (codec == 5) RC_CODEC(5);
     else launch_reduce_t<BZ, AL, L1, 0, true, RAW, SB>(sc, frames, B, depth, s, s_tail);
-#endif
 #undef RC_CODEC
 }
 template <int BZ, bool AL, int SB>
@@ -789,13 +760,13 @@ void launch_reduce(const Scratch &sc, const void *frames, uint32_t B, uint32_t l
     const bool aligned = !sc.guarded_loads;
     if (src_bytes == 1) {   // uint8 frames (source_bit_depth <= 8)
         const uint8_t *f8 = static_cast<const uint8_t *>(frames);
-        if (aligned) launch_reduce_a<RC_BZ, true, 1>(sc, f8, B, level, codec, keep_bitmap, depth, s, s_tail);
-        else launch_reduce_a<RC_BZ, false, 1>(sc, f8, B, level, codec, keep_bitmap, depth, s, s_tail);
+        if (aligned) launch_reduce_a<REDUCE_BZ, true, 1>(sc, f8, B, level, codec, keep_bitmap, depth, s, s_tail);
+        else launch_reduce_a<REDUCE_BZ, false, 1>(sc, f8, B, level, codec, keep_bitmap, depth, s, s_tail);
         return;
     }
     const uint16_t *f16 = static_cast<const uint16_t *>(frames);
-    if (aligned) launch_reduce_a<RC_BZ, true, 2>(sc, f16, B, level, codec, keep_bitmap, depth, s, s_tail);
-    else launch_reduce_a<RC_BZ, false, 2>(sc, f16, B, level, codec, keep_bitmap, depth, s, s_tail);
+    if (aligned) launch_reduce_a<REDUCE_BZ, true, 2>(sc, f16, B, level, codec, keep_bitmap, depth, s, s_tail);
+    else launch_reduce_a<REDUCE_BZ, false, 2>(sc, f16, B, level, codec, keep_bitmap, depth, s, s_tail);
 }
 
 // ---- per-frame scans over tiles ---------------------------------------------------------------------------
@@ -805,10 +776,7 @@ void launch_reduce(const Scratch &sc, const void *frames, uint32_t B, uint32_t l
 // The workgroup is deliberately small: in pipelined mode this kernel is dispatched while the next batch's reduce kernel
 // owns the chip, and a 1024-thread workgroup (16 waves that must start on one CU together) waited there for hundreds of
 // microseconds (rocprofv3: 74 us with LZ4, 355 us with zstd, against 10 us when alone).
-#ifndef RC_SCAN_T
-#define RC_SCAN_T 256
-#endif
-constexpr int SCAN_T = RC_SCAN_T, SCAN_W = SCAN_T / 64;
+constexpr int SCAN_T = 256, SCAN_W = SCAN_T / 64;
 // entries per thread and round: 16 (one round for 4096 tiles), 32 for frames with many more tiles (half the rounds, each of which is a
 // dependent global round trip + two barriers: 11520x8184 has 23 018 tiles)
 

@@ -22,11 +22,8 @@
 
 namespace rc {
 
-#ifndef RC_R32_WAVES
-#define RC_R32_WAVES 1
-#endif
-constexpr int R32_WAVES = RC_R32_WAVES;   // wavefronts per workgroup (each with its own tile and LDS stage); 1 stays: 2 / 4 per workgroup ran LZ4 6-8 % slower
-                                          // (72.6 k -> 68.0 / 67.1 k frames/s), zstd the same (same box, -DRC_R32_WAVES)
+constexpr int R32_WAVES = 1;   // wavefronts per workgroup (each with its own tile and LDS stage); 1 stays: 2 / 4 per workgroup ran LZ4 6-8 % slower
+                               // (72.6 k -> 68.0 / 67.1 k frames/s), zstd the same (same-box A/B)
 constexpr int R32_FPW = 16;    // frames a wavefront keeps its tile for (the thresholds are read once per R32_FPW frames)
 struct __attribute__((aligned(16))) Stage32 {
     uint32_t out[TILE_PX];     // compacted residuals in pixel order, then packed in place

@@ -1,4 +1,4 @@
-"""-m gpu: compression_scheme 0 on the device (RC_SCHEME_ZLIB_DEVICE, rc_deflate_block.h / rc_deflate.hip) through the C ABI.  Every stream
+"""-m gpu: compression_scheme 0 on the device (RC_SCHEME_ZLIB_DEVICE, rc_deflate_block.h / rc_gather.hip) through the C ABI.  Every stream
 must be a zlib stream that STDLIB zlib - the decoder the reference's reader calls (pyrecode/recode_compressors.py:43) - expands to the
 oracle's bytes, its length must equal the record's metadata, and the device's bytes must equal the serial model's
 (tests/deflate_block_model.py, judged by zlib on the CPU) tile for tile."""

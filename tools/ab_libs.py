@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Same-box A/B of library builds / environments under bench.py, interleaved, with a warm-up first (boxes of this pool drift by several per
 cent within a call: read medians over rounds, never single lines).
+A variant is a build (a library path relative to the repository; none: the product build) and / or environment settings; `main` alone is
+the product build as it stands.  One configuration per call: loop in the shell over several.
 usage: tools/ab_libs.py [--rounds N] [--bench "<bench.py args>"] name[=lib.so][,ENV=VAL...] ...
-   e.g. tools/ab_libs.py --rounds 4 --bench "--config 5" old=ab_build/a.so,RC_OLD_ASSEMBLE=1 new=ab_build/a.so main"""
+   e.g. tools/ab_libs.py --rounds 4 --bench "--config 5" old=ab_build/librecode_hip_old.so main
+        tools/ab_libs.py --bench "--config 3" seq=RC_ZSTD_SEQ_ALWAYS=1 main"""
 import argparse
 import json
 import os

@@ -2,6 +2,21 @@
 # Same-box A/B of two TREES: an older commit exported to <old tree> with its own library built there (git archive <commit> | tar -x -C <old tree>;
 # make -C <old tree>/pyrecode_amd/csrc; make -C <old tree>/oracle) against this tree - interleaved rounds per configuration, medians at the end.
 # usage: tools/ab_trees.sh <old tree> <rounds> <<< "one bench.py argument line per configuration"
+#   e.g. the BASELINE configurations and the detector-like stacks:
+#     tools/ab_trees.sh ab_build/old_tree 3 <<'CFGS'
+#     --config 2
+#     --config 3
+#     --config 4
+#     --config 5
+#     --config 5 --batch 16 --stack 32
+#     --depth 12
+#     --scheme 1 --depth 12
+#     --clustered --sparsity-ppm 11000 --depth 12
+#     --clustered --sparsity-ppm 11000 --depth 12 --scheme 1
+#     --level 3
+#     --scheme 0
+#     --sparsity-ppm 100000 --stack 64
+#     CFGS
 OLD=$1; R=${2:-3}
 run() { tree=$1; shift; (cd $tree && python3 bench.py "$@" --steps 20 --warmup 5 --full --min-seconds 0.7 --no-cpu-baseline --no-ingest 2>/dev/null) | python3 -c "
 import sys, json

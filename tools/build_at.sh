@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build librecode_hip from a git revision into ab_build/librecode_hip_<name>.so (same-box A/B runs: tools/ab.sh).
+# Build librecode_hip from a git revision into ab_build/librecode_hip_<name>.so (same-box A/B runs: tools/ab_libs.py).
 # usage: tools/build_at.sh <git-ref> <name>
 set -e
 REF=$1; NAME=$2

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A build of the library with extra -D flags: tools/build_def.sh <name> <flags...>  ->  ab_build/librecode_hip_<name>.so
-# (select with RC_LIB_PATH, see pyrecode_amd/_lib.py; tools/ab_bench.sh runs bench.py over several builds on one box)
+# (select with RC_LIB_PATH, see pyrecode_amd/_lib.py; tools/ab_libs.py runs bench.py over several builds on one box).  The one
+# profiling build: tools/build_def.sh phase -DRC_PHASE_TIMING (tools/phase_timing.py)
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../pyrecode_amd/csrc"
