@@ -12,7 +12,7 @@ struct rc_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     uint32_t nx = 0, ny = 0, depth = 0, level = 0, op_mode = 0, scheme = 0, clevel = 0, max_batch = 0;
-    uint32_t emit = 0;  // 0: mode-0 record pieces, 2: LZ4 frames
+    uint32_t emit = rc::EMIT_RAW;
     // Per-batch scratch exists twice: batch i reduces into sets[i & 1] on `stream`; its scans / layout / assembly (small,
     // latency-bound kernels that leave most of the GPU idle) run on `pstream` and may overlap the next batch's reduce
     // kernel (rc_ctx_set_pipelined).  `sc` is the set of the most recent batch (same geometry and threshold in both).
@@ -37,7 +37,7 @@ struct rc_ctx {
     uint8_t *d_dark = nullptr;    uint64_t d_dark_cap = 0;
     uint64_t *d_rec_off = nullptr;
     uint32_t *d_md = nullptr;
-    void *d_ztab = nullptr;               // zstd FSE tables (emit == 1)
+    void *d_ztab = nullptr;               // zstd FSE tables (EMIT_ZSTD)
     // modelled zstd (compression_level >= 1): tables fitted to a sample of the ctx's first batch (rc_zstd_model.h)
     bool modelled = false, model_ready = false;
     rc::ZstdModel *d_model = nullptr, *h_model = nullptr;
@@ -129,21 +129,21 @@ static int alloc_set(rc_ctx *c, rc::Scratch &sc)
     HIP_TRY(hipMalloc((void **)&sc.scan_part, B * ((T + 255) / 256) * 32));   // (a row of partials per scan segment: room for segments of 256 tiles, more rows than k_scan_seg's 4096-tile ones need)
     HIP_TRY(hipMalloc((void **)&sc.status, sizeof(BatchStatus)));
     if (c->level != 3) HIP_TRY(hipMalloc((void **)&sc.pix_slots, B * T * TILE_PX * 2 + 64));
-    if (c->emit != 0) {
+    if (c->emit != EMIT_RAW) {
         if (c->level == 1) {   // combined slots (rc_launch.h, Scratch::comb; profiles/r04_ab_combined_slots.log)
-            sc.comb = c->emit == RC_SCHEME_ZSTD ? 2u : 1u;   // (zstd's blocks still grow behind the reduce kernel: form 1 would put residuals in their way)
+            sc.comb = c->emit == EMIT_ZSTD ? COMB_AT_BLK_SLOT : COMB_BEHIND_BLOCK;
             sc.blk_stride = 1536;                                  // 12 lines: the block image (<= 5) + 7 or more lines of residuals
         }
         HIP_TRY(hipMalloc((void **)&sc.blk_slots, B * T * (uint64_t)sc.blk_stride + 256));
         HIP_TRY(hipMalloc((void **)&sc.blk_size, B * T * 4));
         HIP_TRY(hipMalloc((void **)&sc.blk_off, B * T * 4));
-        if (c->emit == rc::EMIT_DEFLATE) {   // the zlib streams' Adler-32: per-tile partials of the map, per-frame sums (rc_deflate_block.h, k_gather)
+        if (c->emit == EMIT_DEFLATE) {   // the zlib streams' Adler-32: per-tile partials of the map, per-frame sums (rc_deflate_block.h, k_gather)
             HIP_TRY(hipMalloc((void **)&sc.blk_aux, B * T * 4));
             HIP_TRY(hipMalloc((void **)&sc.zl_acc, B * 32));
             HIP_TRY(hipMemset(sc.zl_acc, 0, B * 32));
         }
     }
-    if (c->emit == RC_SCHEME_ZSTD && c->clevel != 0 && c->level == 1) {   // modelled zstd: Huffman stage of the residual stream
+    if (c->emit == EMIT_ZSTD && c->clevel != 0 && c->level == 1) {   // modelled zstd: Huffman stage of the residual stream
         sc.pixraw_stride = ((sc.N * 2 + 15) & ~15ull) + 32;
         sc.nchunk_max = (uint32_t)((sc.N * 2 + PIX_CHUNK - 1) / PIX_CHUNK) + 1;
         HIP_TRY(hipMalloc((void **)&sc.pixraw, B * sc.pixraw_stride + 64));
@@ -210,7 +210,7 @@ static int ctx_alloc(rc_ctx *c)
         }
     }
     c->sc = c->sets[0];
-    if (c->emit == RC_SCHEME_ZSTD) {
+    if (c->emit == EMIT_ZSTD) {
         std::vector<uint8_t> tab(zstd_tables_bytes());
         zstd_tables_host(tab.data());
         HIP_TRY(hipMalloc(&c->d_ztab, tab.size()));
@@ -284,7 +284,7 @@ RC_EXPORT rc_ctx *rc_ctx_create(uint32_t nx, uint32_t ny, uint32_t src_bit_depth
     c->device = device_id;
     c->nx = nx; c->ny = ny; c->depth = src_bit_depth; c->level = reduction_level; c->op_mode = op_mode;
     c->scheme = scheme; c->clevel = clevel; c->max_batch = max_batch;
-    c->emit = (op_mode == 1 && rc_scheme_on_device(scheme)) ? scheme : 0;
+    c->emit = (op_mode == 1 && rc_scheme_on_device(scheme)) ? scheme : rc::EMIT_RAW;
     rc::Scratch &sc = c->sc;
     sc.N = (uint64_t)nx * ny;
     sc.ntiles = (uint32_t)((sc.N + rc::TILE_PX - 1) / rc::TILE_PX);
@@ -429,7 +429,7 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
         for (int k = 0; k < 2; ++k) {
             rc::Scratch *set = &c->sets[k];
             set->pix_slot_bytes = rc::TILE_PX * 4;
-            set->comb = 0;
+            set->comb = rc::COMB_OFF;
             if (c->level != 3) {
                 (void)hipFree(set->pix_slots);
                 set->pix_slots = slots[k];
@@ -451,7 +451,7 @@ RC_EXPORT uint64_t rc_out_capacity(const rc_ctx *c, uint32_t n) { return c ? (ui
 RC_EXPORT uint32_t rc_md_fields(const rc_ctx *c)
 {
     if (!c) return 0;
-    const bool comp = c->emit != 0;
+    const bool comp = c->emit != rc::EMIT_RAW;
     if (c->level != 3) return comp ? 3 : 1;
     return comp ? 1 : 0;
 }
@@ -468,7 +468,7 @@ static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
     for (int k = 0; k < 2; ++k)
         if (c->post_pending[k]) HIP_TRY(hipStreamWaitEvent(s, c->ev_post[k], 0));
     HIP_TRY(hipMemsetAsync(c->d_sample, 0, sizeof(ZstdSample), s));
-    launch_reduce(sc, frames_dev, ns, c->level == 3 ? 3u : 1u, 1u, true, c->depth, s, nullptr, c->src_bytes);   // (with the raw maps: the sample counts all their bytes)
+    launch_reduce(sc, frames_dev, ns, c->level == 3 ? 3u : 1u, CODEC_ZSTD_FAST, true, c->depth, s, nullptr, c->src_bytes);   // (with the raw maps: the sample counts all their bytes)
     launch_zstd_sample(sc, ns, c->level == 1, c->depth, c->d_sample, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_sample, c->d_sample, sizeof(ZstdSample), hipMemcpyDeviceToHost, s));
@@ -477,11 +477,11 @@ static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
     // level to libzstd (recode_writer.py:175-178), where 1 is the fast end too.  Level 1: up to 5 % of the binary-map stream, level 2: 2 %,
     // from 3 on the smaller form always.
     zstd_model_from_sample(c->h_sample, c->h_model, c->clevel == 1 ? 50u : (c->clevel == 2 ? 20u : 0u));
-    if (c->level != 1) c->h_model->valid &= ~2u;   // level 2 statistics / level 3: no residual-stream code
+    if (c->level != 1) c->h_model->valid &= ~ZM_PIX_CODE;   // level 2 statistics / level 3: no residual-stream code
     {   // a residual stream the byte-wise code cannot shrink (bit-packed depths) is stored instead, in 128 KiB Raw blocks
         uint64_t bits = 0, total = 0;
         for (int v = 0; v < 256; ++v) { bits += (uint64_t)c->h_sample->pix[v] * (c->h_model->pix_code[v] >> 12); total += c->h_sample->pix[v]; }
-        if (total == 0 || bits > total * 8 * 97 / 100) c->h_model->valid &= ~2u;
+        if (total == 0 || bits > total * 8 * 97 / 100) c->h_model->valid &= ~ZM_PIX_CODE;
     }
     HIP_TRY(hipMemcpyAsync(c->d_model, c->h_model, sizeof(ZstdModel), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -491,10 +491,24 @@ static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
         set->zm_lit_code = c->d_model->lit_code;
         set->zm_valid = M.valid;
         set->zm_budget = zm_block_budget(M, BLK_SLOT);
-        set->zm_seq_bits = (M.valid & 4u) ? M.seq.ll_log + M.seq.ml_log : 12u;
+        set->zm_seq_bits = (M.valid & ZM_SEQ_TABLES) ? M.seq.ll_log + M.seq.ml_log : 12u;
     }
     c->model_ready = true;
     return RC_OK;
+}
+
+// The block encoder fused into the reduce kernel for a ctx's record form.  uint32 sources (src_bytes 4, rc_reduce32.hip) have the fast zstd
+// encoder only (the modelled one is fitted inside the uint16 kernel).
+static uint32_t fused_codec(uint32_t emit, uint32_t clevel, bool modelled, uint32_t src_bytes)
+{
+    using namespace rc;
+    switch (emit) {
+    case EMIT_ZSTD: return modelled && src_bytes != 4 ? CODEC_ZSTD_MODELLED : CODEC_ZSTD_FAST;
+    case EMIT_LZ4: return clevel != 0 ? CODEC_LZ4_EVENTS : CODEC_LZ4_RUNS;
+    case EMIT_BLOSC: return CODEC_BLOSC;
+    case EMIT_DEFLATE: return CODEC_DEFLATE;
+    default: return CODEC_NONE;
+    }
 }
 
 static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t first_frame_id, uint8_t *out_dev,
@@ -543,23 +557,19 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     // every device codec's block encoder runs inside the reduce kernel (LZ4; blosc = bit-shuffle + LZ4; zstd: the
     // byte-parallel half - literals, sequence tokens - with the serial FSE half lane-per-block behind it)
-    const bool fitted_seq = c->modelled && (c->h_model->valid & 4u);
+    const bool fitted_seq = c->modelled && (c->h_model->valid & ZM_SEQ_TABLES);
     hipStream_t tail = nullptr;
     if (sc.N % TILE_PX) {   // a partial last tile: its small launch goes to the second-stage stream, behind "the frames are there"
         HIP_TRY(hipEventRecord(c->ev_in[k], s));
         HIP_TRY(hipStreamWaitEvent(ps, c->ev_in[k], 0));
         tail = ps;
     }
-    // codec of the fused block encoder: 1 zstd fast, 3 zstd modelled, 2 LZ4 runs (compression_level 0), 4 LZ4 events (>= 1), 8 blosc
-    const uint32_t codec = c->modelled ? 3u : (c->emit == RC_SCHEME_LZ4 && c->clevel != 0 ? 4u : (c->emit == EMIT_DEFLATE ? 5u : c->emit));
-    if (c->src_bytes == 4) {
-        // uint32 sources (rc_reduce32.hip): reduce + pack with the codec's block encoder inside the kernel, as in the uint16 path (zstd in its
-        // fast form)
-        launch_reduce32(sc, static_cast<const uint32_t *>(frames_dev), c->thr32, n, c->level, c->depth, s,
-                        c->emit == RC_SCHEME_LZ4 ? (c->clevel != 0 ? 4u : 2u) : (c->emit == RC_SCHEME_BLOSC_LZ4 ? 8u : (c->emit == RC_SCHEME_ZSTD ? 1u : 0u)),
-                        c->keep_bitmap || c->emit == 0);
-    } else
-        launch_reduce(sc, frames_dev, n, c->level, codec, c->keep_bitmap || c->emit == 0, c->depth, s, tail, c->src_bytes);
+    const uint32_t codec = fused_codec(c->emit, c->clevel, c->modelled, c->src_bytes);
+    const bool keep_maps = c->keep_bitmap || c->emit == EMIT_RAW;
+    if (c->src_bytes == 4)   // uint32 sources (rc_reduce32.hip): reduce + pack with the codec's block encoder inside the kernel, as in the uint16 path
+        launch_reduce32(sc, static_cast<const uint32_t *>(frames_dev), c->thr32, n, c->level, c->depth, s, codec, keep_maps);
+    else
+        launch_reduce(sc, frames_dev, n, c->level, codec, keep_maps, c->depth, s, tail, c->src_bytes);
     // every event costs a few microseconds of stream time: the asynchronous path records only the ones it needs
     // (start, end of the reduce kernel, end of the batch) unless RC_PROFILE_ALL_STAGES is set
     const bool all_ev = ev && (timed || c->profile_all);
@@ -569,19 +579,19 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     HIP_TRY(hipStreamWaitEvent(ps, red, 0));
     if (c->level == 2) launch_l2(sc, n, c->nx, c->l2_sum, c->depth, ps);   // the tiles' raw values -> their components' statistics (rc_l2.hip)
     const bool lits_only = c->modelled && (c->h_model->valid & ZM_LITS_ONLY);   // dense maps: no block has sequences, nothing for the FSE chain to do
-    if (c->emit == RC_SCHEME_ZSTD && !lits_only) launch_zstd_fse(sc, n, fitted_seq ? (const void *)&c->d_model->seq : c->d_ztab, fitted_seq, ps);
+    if (c->emit == EMIT_ZSTD && !lits_only) launch_zstd_fse(sc, n, fitted_seq ? (const void *)&c->d_model->seq : c->d_ztab, fitted_seq, ps);
     if (all_ev) HIP_TRY(hipEventRecord(ev[2], ps));
-    launch_scans(sc, n, c->level != 3, c->emit != 0, ps);
+    launch_scans(sc, n, c->level != 3, c->emit != EMIT_RAW, ps);
     if (all_ev) HIP_TRY(hipEventRecord(ev[3], ps));
     // modelled zstd, level 1: the residual stream is laid out flat, Huffman-coded in chunks, and placed behind the bitmap stream
     // (rc_pix_huff.hip); its encoded size is part of the record layout
-    const bool pix_huff = c->modelled && c->level == 1 && (c->h_model->valid & 2u) && sc.pixraw;
+    const bool pix_huff = c->modelled && c->level == 1 && (c->h_model->valid & ZM_PIX_CODE) && sc.pixraw;
     if (pix_huff) {
-        rp.pix_mode = 1;
+        rp.pix_mode = PIX_MODE_FLAT;
         launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
         launch_pix_huff(sc, n, c->depth, ps);
         launch_pix_scan(sc, n, c->depth, ps);
-        rp.pix_mode = 2;
+        rp.pix_mode = PIX_MODE_SKIP;
     }
     if (two && c->post_pending[k ^ 1]) {
         // Two chains run the second stages of batches i and i + 1 at the same time, which is why include/recode_hip.h asks a pipelined caller for
@@ -926,7 +936,7 @@ RC_EXPORT int rc_get_binary_map(rc_ctx *c, uint32_t i, uint8_t *bitmap_out)
 {
     if (!c || !bitmap_out) return fail(RC_ERR_BAD_ARG, "NULL argument");
     if (i >= c->last_n) return fail(RC_ERR_BAD_ARG, "frame index outside the most recent batch");
-    if (!c->keep_bitmap && c->emit != 0 && c->level != 2) return fail(RC_ERR_BAD_ARG, "binary maps are not kept (rc_ctx_keep_binary_maps(ctx, 0))");
+    if (!c->keep_bitmap && c->emit != rc::EMIT_RAW && c->level != 2) return fail(RC_ERR_BAD_ARG, "binary maps are not kept (rc_ctx_keep_binary_maps(ctx, 0))");
     RC_ON_DEVICE(c->device);
     int r = copy_out(bitmap_out, c->sc.bitmap + (uint64_t)i * c->sc.nb_stride, c->sc.nb, c->stream);
     if (r != RC_OK) return r;

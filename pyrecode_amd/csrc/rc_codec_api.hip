@@ -414,7 +414,7 @@ static int zstd_decompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_
     HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
     HIP_TRY(hipMemsetAsync(u.x[1], 0, bound + 64, s));   // the decoders store only what is not zero
     HIP_TRY(hipMemcpyAsync(d_prod, &none, 4, hipMemcpyHostToDevice, s));
-    if (!comp.empty()) launch_block_decode(1, (int)row, d_src, d_lists, 1, (uint32_t)comp.size(), u.x[3], u.zd_predef, u.x[1], d_base, d_err, s, d_prod);
+    if (!comp.empty()) launch_block_decode(rc::EMIT_ZSTD, (int)row, d_src, d_lists, 1, (uint32_t)comp.size(), u.x[3], u.zd_predef, u.x[1], d_base, d_err, s, d_prod);
     launch_block_copy(d_src, d_lists + 1, 1, (uint32_t)raw.size(), raw_max, u.x[1], d_base, s);
     HIP_TRY(hipGetLastError());
     int err = 0;

@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace rc {
+
+template <int V> using int_c = std::integral_constant<int, V>;   // a compile-time int for the launchers' generic lambdas
 
 // ---- geometry -----------------------------------------------------------------------------------
 // A frame of N = nx*ny uint16 pixels is cut, in row-major (linear) order, into tiles of TILE_PX pixels, one tile per

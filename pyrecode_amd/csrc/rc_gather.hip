@@ -128,9 +128,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
         return;
     }
     const uint32_t lane = (uint32_t)lane_id();
-    const bool flat = rp.pix_mode == 1, skip_pix = rp.pix_mode == 2;
+    const bool flat = rp.pix_mode == PIX_MODE_FLAT, skip_pix = rp.pix_mode == PIX_MODE_SKIP;
     const bool pixp = rp.level == 1 && rp.packed_slots && !skip_pix;
-    const bool plain_pos = rp.emit == 0 || flat;
+    const bool plain_pos = rp.emit == EMIT_RAW || flat;
     const uint32_t d = rp.depth;
     const FrameFmt ff = frame_fmt(rp.emit);
     const uint32_t bhdr = bitmap_hdr(ff, rp.emit, sc.ntiles);
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
         uint64_t bitmap_pos = 0, pix_pos = 0;
         uint32_t cb = 0;
         if (!flat) {
-            if (rp.emit == 0) { bitmap_pos = rp.level == 1 ? 8 : 4; pix_pos = bitmap_pos + sc.nb; }
+            if (rp.emit == EMIT_RAW) { bitmap_pos = rp.level == 1 ? 8 : 4; pix_pos = bitmap_pos + sc.nb; }
             else { cb = bhdr + sc.frame_cbytes[f] + ff.end; bitmap_pos = rp.level == 1 ? 16 : 8; pix_pos = bitmap_pos + cb; }
         }
         if (g == 0 && lane == 0 && !flat) record_fixed_fields(sc, rp, f, rec, bitmap_pos, pix_pos, cb, npk, ff, skip_pix, lz4f_hdr_bitmap, lz4f_hdr_pix);
@@ -159,9 +159,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
         // behind it from cnt and a second read of tile_off: registers; `packed` carries two flags for it)
         uint32_t word = 0, bsz = 0, bdst = 0, cnt = 0, rn = 0, rdst = 0, rs = 0xFFFFFFFFu, ps0 = 0, flags = 0, blo = 0;
         AdlerAcc ad{0u, 0u};
-        if (have && rp.emit != 0 && (!flat || (sc.comb == 1 && pixp))) word = sc.blk_size[frow + t];
+        if (have && rp.emit != EMIT_RAW && (!flat || (sc.comb == COMB_BEHIND_BLOCK && pixp))) word = sc.blk_size[frow + t];
         if (have && !flat) {
-            if (rp.emit == 0) {
+            if (rp.emit == EMIT_RAW) {
                 const uint64_t b0 = (uint64_t)t * TILE_BM;
                 bsz = (uint32_t)min((uint64_t)TILE_BM, sc.nb - b0);
                 bdst = (uint32_t)(bitmap_pos + b0);
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
                 bsz = word;
                 const uint32_t boff = bhdr + sc.blk_off[frow + t];
                 bdst = (uint32_t)bitmap_pos + boff;
-                if (rp.emit == 8) store_u32_le(rec + bitmap_pos + 16 + 4 * (uint64_t)t, boff);   // blosc bstarts[t]
+                if (rp.emit == EMIT_BLOSC) store_u32_le(rec + bitmap_pos + 16 + 4 * (uint64_t)t, boff);   // blosc bstarts[t]
             }
         }
         if (have && pixp) {
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
                 ps0 = q.ps0;
                 if (ADLER) blo = q.b_lo;
                 if (sc.comb) {   // (rc_launch.h::residual_src)
-                    const uint32_t ro16 = sc.comb == 2 ? (uint32_t)BLK_SLOT / 16 : (word + 15) >> 4, r16 = (cnt * d + 127) >> 7;
+                    const uint32_t ro16 = sc.comb == COMB_AT_BLK_SLOT ? (uint32_t)BLK_SLOT / 16 : (word + 15) >> 4, r16 = (cnt * d + 127) >> 7;
                     if (16 * (ro16 + r16) <= sc.blk_stride) rs = 16 * ro16;
                 }
                 // a tile whose bytes straddle a stored-chunk header of the pixel frame is copied byte by byte behind the loop (bit 31)
@@ -193,10 +193,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
         if (BITS && pixp && t0 + tpi < sc.ntiles) {
             ext_cnt = sc.tile_cnt[frow + t0 + tpi];
             if (ext_cnt)
-                ext_first = *reinterpret_cast<const uint32_t *>(residual_src(sc, frow + t0 + tpi, sc.comb == 1 ? sc.blk_size[frow + t0 + tpi] : 0u, ext_cnt, d));
+                ext_first = *reinterpret_cast<const uint32_t *>(residual_src(sc, frow + t0 + tpi, sc.comb == COMB_BEHIND_BLOCK ? sc.blk_size[frow + t0 + tpi] : 0u, ext_cnt, d));
         }
-        const uint8_t *slot = rp.emit == 0 ? sc.bitmap + (uint64_t)f * sc.nb_stride + (uint64_t)t0 * TILE_BM : sc.blk_slots + (frow + t0) * sc.blk_stride;
-        const uint32_t slot_stride = rp.emit == 0 ? (uint32_t)TILE_BM : sc.blk_stride;
+        const uint8_t *slot = rp.emit == EMIT_RAW ? sc.bitmap + (uint64_t)f * sc.nb_stride + (uint64_t)t0 * TILE_BM : sc.blk_slots + (frow + t0) * sc.blk_stride;
+        const uint32_t slot_stride = rp.emit == EMIT_RAW ? (uint32_t)TILE_BM : sc.blk_stride;
         const uint8_t *rslot = pix_base + (frow + t0) * sc.pix_slot_bytes;
 
         // ---- pieces -------------------------------------------------------------------------------------------------------------------
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GATHER_WPE))
             uint32_t tt = cur == 65 ? (t0 + tpi - 1 < sc.ntiles ? sc.tile_next[frow + t0 + tpi - 1] : sc.ntiles) : (t0 + tpi < sc.ntiles ? sc.tile_next[frow + t0 + tpi] : sc.ntiles);
             while (tt < sc.ntiles) {
                 const uint32_t cc = sc.tile_cnt[frow + tt];
-                const uint32_t fd = *reinterpret_cast<const uint32_t *>(residual_src(sc, frow + tt, sc.comb == 1 ? sc.blk_size[frow + tt] : 0u, cc, d));
+                const uint32_t fd = *reinterpret_cast<const uint32_t *>(residual_src(sc, frow + tt, sc.comb == COMB_BEHIND_BLOCK ? sc.blk_size[frow + tt] : 0u, cc, d));
                 const uint32_t take = min(8u - got, cc * d);
                 byte |= (fd & ((1u << take) - 1u)) << got;
                 got += take;
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(64) void k_zlib_finish(GatherArgs sc, RecordParams 
     uint8_t *rec = out + rec_off[f];
     const uint32_t cb = bitmap_hdr(ff, rp.emit, sc.ntiles) + sc.frame_cbytes[f] + ff.end, bitmap_pos = rp.level == 1 ? 16u : 8u;
     store_u32_be(rec + bitmap_pos + cb - 4, adler_from_sums(sc.nb, acc[0], acc[1]));
-    if (rp.level == 1 && rp.pix_mode != 2) {
+    if (rp.level == 1 && rp.pix_mode != PIX_MODE_SKIP) {
         const uint32_t npk = packed_bytes(sc.frame_nnz[f], rp.depth);
         store_u32_be(rec + bitmap_pos + cb + stored_size(ff, npk) - 4, adler_from_sums(npk, acc[2], acc[3]));
     }
@@ -361,7 +361,7 @@ void launch_gather(const Scratch &sc, const RecordParams &rp, uint32_t B, uint8_
     if (rp.emit == EMIT_DEFLATE) {   // (the zlib streams' Adler-32 is summed up on the way: the ADLER instantiations)
         if (bits) hipLaunchKernelGGL((k_gather<true, GATHER_UB - 1, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
         else hipLaunchKernelGGL((k_gather<false, GATHER_U, true>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
-        if (rp.pix_mode != 1) hipLaunchKernelGGL(k_zlib_finish, dim3((B + 63) / 64), dim3(64), 0, s, ga, rp, out, rec_off, B);
+        if (rp.pix_mode != PIX_MODE_FLAT) hipLaunchKernelGGL(k_zlib_finish, dim3((B + 63) / 64), dim3(64), 0, s, ga, rp, out, rec_off, B);
     } else if (bits)
         hipLaunchKernelGGL((k_gather<true, GATHER_UB, false>), dim3(wgs), dim3(64), 0, s, ga, rp, out, rec_off, hdr_bitmap, hdr_pix, batch_seq, gpf, nitems, tpi);
     else

@@ -3,9 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/recode_hip.h"
 #include "rc_device.h"
 
 namespace rc {
+
+// Scratch::comb: where a tile's packed residual stream lives
+constexpr uint32_t COMB_OFF = 0u;          // in pix_slots
+constexpr uint32_t COMB_BEHIND_BLOCK = 1u; // in the block's slot, at the next 16-byte boundary behind the block image (LZ4 / blosc: the image is
+                                           // final when the reduce kernel writes it)
+constexpr uint32_t COMB_AT_BLK_SLOT = 2u;  // in the block's slot, at offset BLK_SLOT (zstd: the FSE pass and the frame's definitions still grow
+                                           // the block)
 
 // Device scratch of one ctx, laid out for a batch of up to max_batch frames (DESIGN.md "data layout in HBM").
 struct Scratch {
@@ -27,11 +35,10 @@ struct Scratch {
                                        //                           tile's residual stream in the same slot when both fit (`comb`)
     uint32_t blk_stride = BLK_SLOT;    // bytes between two tiles' block slots
     // Combined slots (a ctx with a device codec at level 1): the tile's packed residual stream sits BEHIND its encoded block in the block's
-    // slot - 1: at the next 16-byte boundary behind the block image (LZ4 / blosc: the image is final when the reduce kernel writes it),
-    // 2: at offset BLK_SLOT (zstd: the FSE pass and the frame's definitions still grow the block) - whenever block + residual lines fit
-    // blk_stride; a tile too dense for that keeps its residuals in pix_slots as before.  One run of lines per tile and frame instead of
-    // two runs 8 KiB apart: fewer lines written by the reduce kernel and read by k_gather (each run wastes half a line on average).
-    uint32_t comb = 0;
+    // slot (COMB_* forms) whenever block + residual lines fit blk_stride; a tile too dense for that keeps its residuals in pix_slots as before.
+    // One run of lines per tile and frame instead of two runs 8 KiB apart: fewer lines written by the reduce kernel and read by k_gather
+    // (each run wastes half a line on average).
+    uint32_t comb = COMB_OFF;
     uint32_t *blk_size = nullptr;      // [B][ntiles]               bytes used in each slot
     uint32_t *blk_aux = nullptr;       // [B][ntiles]               deflate: the tiles' Adler-32 partials (rc_deflate_block.h::deflate_adler_word)
     uint32_t *zl_acc = nullptr;        // [B][8]                    deflate: per frame {A, W of the map, A, W of the residual stream}
@@ -51,7 +58,7 @@ struct Scratch {
     uint32_t *chunk_off = nullptr;     // [B][nchunk_max]   exclusive prefix inside the frame
     uint32_t *frame_pbytes = nullptr;  // [B]               sum of chunk_size
     uint32_t nchunk_max = 0;
-    // modelled zstd (codec 3, rc_zstd_model.h): the ctx's model on the device and what the block encoders need of it
+    // modelled zstd (CODEC_ZSTD_MODELLED, rc_zstd_model.h): the ctx's model on the device and what the block encoders need of it
     const void *zm_model = nullptr;    // ZstdModel
     const void *zm_lit_code = nullptr; // &model->lit_code
     uint32_t zm_valid = 0, zm_budget = 0, zm_seq_bits = 12;
@@ -61,35 +68,54 @@ struct Scratch {
     uint16_t *l2_base = nullptr;       // [B][ntiles * 64] set pixels of a word's tile in front of the word (k_l2_dir)
 };
 
-// RecordParams::emit / rc_ctx::emit of the device DEFLATE encoder (include/recode_hip.h: RC_SCHEME_ZLIB_DEVICE); the others are the
-// reference's compression_scheme codes
-constexpr uint32_t EMIT_DEFLATE = 0x100u;
+// RecordParams::emit / rc_ctx::emit: the form of a record's two streams (rc_record.h).  Also the batched decoder's selector (rc_reader.hip,
+// rc_zstd_dec.hip).  rc_ctx_create sets emit = compression_scheme for a device codec, so the codecs' values are the scheme codes.
+constexpr uint32_t EMIT_RAW = 0u;          // raw pieces (a mode-0 record): NOT compression_scheme 0 (zlib)
+constexpr uint32_t EMIT_ZSTD = 1u;         // zstd frames
+constexpr uint32_t EMIT_LZ4 = 2u;          // LZ4 frames
+constexpr uint32_t EMIT_BLOSC = 8u;        // blosc1 chunks (bit-shuffle + LZ4)
+constexpr uint32_t EMIT_DEFLATE = 0x100u;  // zlib streams of the device DEFLATE encoder
+static_assert(EMIT_ZSTD == RC_SCHEME_ZSTD && EMIT_LZ4 == RC_SCHEME_LZ4 && EMIT_BLOSC == RC_SCHEME_BLOSC_LZ4 && EMIT_DEFLATE == RC_SCHEME_ZLIB_DEVICE,
+              "rc_ctx_create assigns emit = compression_scheme");
+
+// The block encoder fused into the reduce kernel (the CODEC template parameter, launch_reduce / launch_reduce32's codec); a ctx's one is
+// chosen by rc_api.hip::fused_codec
+constexpr int CODEC_NONE = 0;            // no encoded blocks: the raw binary maps only
+constexpr int CODEC_ZSTD_FAST = 1;       // zstd, compression_level 0: raw literals, predefined tables (k_zstd_fse finishes the blocks)
+constexpr int CODEC_LZ4_RUNS = 2;        // LZ4, compression_level 0: the run encoder (rc_lz4_block.h)
+constexpr int CODEC_ZSTD_MODELLED = 3;   // zstd, compression_level >= 1: Huffman-coded literals, tokens for the ctx's fitted tables (rc_zstd_wave.h)
+constexpr int CODEC_LZ4_EVENTS = 4;      // LZ4, compression_level >= 1: the event parser (rc_lz4_block.h)
+constexpr int CODEC_DEFLATE = 5;         // a fixed-Huffman block per tile + its Adler-32 partials (rc_deflate_block.h)
+constexpr int CODEC_BLOSC = 8;           // blosc1 block: bit-shuffle (typesize 8), then the LZ4 run encoder
+
+// RecordParams::pix_mode: what k_gather / k_layout do with the level-1 residual stream
+constexpr uint32_t PIX_MODE_STORED = 0u; // it goes into the record as it is (stored chunks)
+constexpr uint32_t PIX_MODE_FLAT = 1u;   // ONLY the residual stream, flat, into Scratch::pixraw (input of the Huffman stage, rc_pix_huff.hip)
+constexpr uint32_t PIX_MODE_SKIP = 2u;   // everything but the residual stream, whose encoded size is Scratch::frame_pbytes
+
 struct RecordParams {
     uint32_t level;        // 1 or 3
-    uint32_t emit;         // 0 = raw pieces (mode-0 record), 2 = LZ4 frames, 1 = zstd frames, 8 = blosc-lz4, EMIT_DEFLATE = zlib streams
+    uint32_t emit;         // EMIT_*
     uint32_t depth;        // source_bit_depth
     uint32_t packed_slots; // 1: the tiles' slots hold tile-local packed streams - level-1 residuals and, since round 5, level-2 statistics (k_l2_emit);
                            // 0: no value stream is gathered (no caller passes it any more)
     uint32_t first_frame_id;
     uint64_t frame_bytes;  // raw frame size = N * 2 (record upper bound, recode_writer.py:565-566)
-    uint32_t pix_mode = 0; // k_gather / k_layout: 0 = the residual stream goes into the record as it is (stored chunks);
-                           // 1 = ONLY the residual stream, flat, into Scratch::pixraw (input of the Huffman stage);
-                           // 2 = everything but the residual stream, whose encoded size is Scratch::frame_pbytes
+    uint32_t pix_mode = PIX_MODE_STORED;
 };
 
 // rc_reduce.hip
 void launch_threshold(const void *dark, int64_t eps, uint64_t N, uint16_t *thr, hipStream_t s, uint32_t src_bytes = 2);   // dark: uint16, or uint8 for src_bytes 1
-// codec: 0 none, 2 LZ4, 1 zstd (plain), 3 zstd (modelled), 8 blosc-lz4, 5 deflate (fixed-Huffman block per tile).
-// level: 1 residuals, 2 raw values of the set pixels (input of launch_l2), 3 bitmap only.  depth < 16 (level 1 only):
+// codec: CODEC_*.  level: 1 residuals, 2 raw values of the set pixels (input of launch_l2), 3 bitmap only.  depth < 16 (level 1 only):
 // every tile's residuals are left in its slot already bit-packed (tile-local LSB-first stream of depth-bit fields)
 // src_bytes: bytes per source pixel - 2 (uint16 frames) or 1 (uint8 frames, source_bit_depth <= 8)
 void launch_reduce(const Scratch &sc, const void *frames, uint32_t B, uint32_t level, uint32_t codec, bool keep_bitmap,
                    uint32_t depth, hipStream_t s, hipStream_t s_tail = nullptr, uint32_t src_bytes = 2);
-// rc_reduce32.hip: uint32 sources (source_bit_depth > 16) - reduce + d-bit pack, the block encoder of `codec` fused (2 / 4 LZ4 runs / events,
-// 8 blosc-lz4, 1 zstd fast form); raw binary maps only with keep_bitmap
+// rc_reduce32.hip: uint32 sources (source_bit_depth > 16) - reduce + d-bit pack, the block encoder of `codec` fused (every CODEC_* but
+// CODEC_ZSTD_MODELLED and CODEC_DEFLATE); raw binary maps only with keep_bitmap
 void launch_threshold32(const uint32_t *dark, int64_t eps, uint64_t N, uint32_t *thr, hipStream_t s);
 void launch_reduce32(const Scratch &sc, const uint32_t *frames, const uint32_t *thr32, uint32_t B, uint32_t level, uint32_t depth, hipStream_t s,
-                     uint32_t codec = 0, bool keep_bitmap = true);   // codec 2 / 4: the LZ4 block encoder (runs / events) fused
+                     uint32_t codec = CODEC_NONE, bool keep_bitmap = true);
 // rc_l2.hip
 void launch_l2(const Scratch &sc, uint32_t B, uint32_t nx, uint32_t use_sum, uint32_t depth, hipStream_t s);
 void launch_scans(const Scratch &sc, uint32_t B, bool with_counts, bool with_blocks, hipStream_t s);
@@ -134,12 +160,12 @@ size_t zstd_tables_bytes();
 void zstd_tables_host(void *dst);  // rc_reduce.hip: FLG | BD << 8 | HC << 16
 
 // where tile ft's packed residual stream starts (see Scratch::comb); bn: the tile's blk_size word as the reduce kernel wrote it
-// (combined form 1 only), cnt: its set pixels, d: bits per value
+// (COMB_BEHIND_BLOCK only), cnt: its set pixels, d: bits per value
 template <class S>
 __host__ __device__ inline const uint8_t *residual_src(const S &sc, uint64_t ft, uint32_t bn, uint32_t cnt, uint32_t d)
 {
     if (sc.comb) {
-        const uint32_t ro16 = sc.comb == 2 ? (uint32_t)BLK_SLOT / 16 : (bn + 15) >> 4, r16 = (cnt * d + 127) >> 7;
+        const uint32_t ro16 = sc.comb == COMB_AT_BLK_SLOT ? (uint32_t)BLK_SLOT / 16 : (bn + 15) >> 4, r16 = (cnt * d + 127) >> 7;
         if (16 * (ro16 + r16) <= sc.blk_stride) return sc.blk_slots + ft * sc.blk_stride + 16 * ro16;
     }
     return reinterpret_cast<const uint8_t *>(sc.pix_slots) + ft * sc.pix_slot_bytes;

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(WG) void k_pix_huff(Scratch sc, uint32_t B, uint32_
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t npk = pix_packed_bytes(sc.frame_nnz[f], depth);
     const uint32_t nch = npk ? (npk + PIX_CHUNK - 1) / PIX_CHUNK : 1u;
-    const bool can = (sc.zm_valid & 2u) != 0;
+    const bool can = (sc.zm_valid & ZM_PIX_CODE) != 0;
     const uint32_t desc_len = M->pix_desc_len;
     uint32_t *out32 = s_out[w];
     uint8_t *out8 = reinterpret_cast<uint8_t *>(out32);

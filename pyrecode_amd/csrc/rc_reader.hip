@@ -64,8 +64,9 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap)) return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
     if (level != 1 && level != 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1 or 3");
     if (level == 1 && (bit_depth == 0 || bit_depth > 64)) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    const int codec = op_mode == 0 ? 0 : (scheme == RC_SCHEME_LZ4 ? 2 : (scheme == RC_SCHEME_ZSTD ? 1 : -1));
-    if (codec < 0) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: scheme has no batched device decoder");
+    if (op_mode != 0 && scheme != RC_SCHEME_LZ4 && scheme != RC_SCHEME_ZSTD)
+        return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: scheme has no batched device decoder");
+    const uint32_t codec = op_mode == 0 ? EMIT_RAW : (scheme == RC_SCHEME_LZ4 ? EMIT_LZ4 : EMIT_ZSTD);
     const uint64_t N = (uint64_t)nx * ny, nb = (N + 7) / 8, nb8 = (nb + 7) / 8;
     static const bool timing = getenv("RC_READ_TIMING") != nullptr;   // development: phase times on stderr
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -106,7 +107,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     auto need = [&](int i, uint64_t bytes) { return ensure(u.x[i], u.x_cap[i], bytes); };
     // head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n][pv_bytes n] [base2 2n][pv_base n][src_base n], the
     // same layout in page-locked host memory and on the device: one copy
-    const uint64_t ntab = codec == 1 ? 2 * (uint64_t)n : 0;
+    const uint64_t ntab = codec == EMIT_ZSTD ? 2 * (uint64_t)n : 0;
     const uint64_t o_first = ntab * sizeof(ZdTables);
     const uint64_t o_base2 = (o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList) + (uint64_t)n * 4 + 15) & ~15ull;
     const uint64_t sz_head = o_base2 + (uint64_t)n * 4 * 8;
@@ -161,7 +162,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     // ---- host: walk the frames, build block tables and decoding tables (a few threads, each a contiguous range of frames) ----
     // (the copy-in reads the caller's memory: no return from here on without waiting for it)
     auto bail = [&](int code, const char *msg) { (void)hipStreamSynchronize(s); return fail(code, msg); };
-    ZdTables *bm_tab = reinterpret_cast<ZdTables *>(u.rd_head), *pv_tab = bm_tab + (codec == 1 ? n : 0);
+    ZdTables *bm_tab = reinterpret_cast<ZdTables *>(u.rd_head), *pv_tab = bm_tab + (codec == EMIT_ZSTD ? n : 0);
     // The block lists stay where the indexing threads wrote them, in page-locked host memory: the decoders read every entry once,
     // over the link (uploading them meant 3 small copies per thread, each a fixed ~15 us of stream time: 0.7 ms per call).
     ZdFrameList *bm_list = reinterpret_cast<ZdFrameList *>(u.rd_head + o_first), *pv_list = bm_list + n, *raw_list = pv_list + n;
@@ -189,7 +190,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             // in one allocation each; anything beyond still grows by doubling
             const uint64_t share = std::min<uint64_t>(n, 3ull * ((n + nthr - 1) / nthr));
             OFF.reserve(share * ((nb + TILE_BM - 1) / TILE_BM + 1));
-            if (level == 1 && codec == 1) PV.reserve(share * (max_npk / 1000 + 2));   // (value-stream chunks: PIX_CHUNK = 1008 bytes each)
+            if (level == 1 && codec == EMIT_ZSTD) PV.reserve(share * (max_npk / 1000 + 2));   // (value-stream chunks: PIX_CHUNK = 1008 bytes each)
         }
         // A binary-map stream whose blocks all regenerate TILE_BM bytes (the last one the rest), lie back to back and keep to one
         // set of sequence tables - what this library's encoders write - leaves one dword per block (k_bitmap_decode_c); any other
@@ -221,14 +222,14 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             uint64_t got = 0;
             int rr = ZD_OK;
             F.bm0 = (uint32_t)BM.size(); F.pv0 = (uint32_t)PV.size();
-            if (codec == 0) {
+            if (codec == EMIT_RAW) {
                 if (cb != nb || cp != npk) { F.status = ZD_CORRUPT; F.what = "rc_expand_frames: mode-0 sizes disagree with the frame shape"; continue; }
                 ZdBlock b;
                 memset(&b, 0, sizeof b);
                 b.frame = f; b.src = o; b.csize = b.regen = (uint32_t)nb; b.dst = 0;
                 RAW.push_back(b);
                 if (npk) { b.src = o + cb; b.csize = b.regen = (uint32_t)npk; b.frame = n + f; RAW.push_back(b); }
-            } else if (codec == 2) {
+            } else if (codec == EMIT_LZ4) {
                 all.clear();
                 rr = lz4_index_frame(walk, o, cb, f, TILE_BM, nb, all, all, &got);
                 if (rr == ZD_OK && got != nb) rr = ZD_CORRUPT;
@@ -299,7 +300,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (n_raw >= (1ull << 31)) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
     const double t_2 = now();
     // ---- device ----
-    ZdTables *d_bm_tab = reinterpret_cast<ZdTables *>(u.x[3]), *d_pv_tab = d_bm_tab + (codec == 1 ? n : 0);
+    ZdTables *d_bm_tab = reinterpret_cast<ZdTables *>(u.x[3]), *d_pv_tab = d_bm_tab + (codec == EMIT_ZSTD ? n : 0);
     const ZdFrameList *d_bm_list = reinterpret_cast<const ZdFrameList *>(u.x[3] + o_first), *d_pv_list = d_bm_list + n, *d_raw_list = d_pv_list + n;
     const ZdFrameList *d_cbm_list = d_raw_list + RC_READ_THREADS;
     uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.x[3] + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
@@ -308,15 +309,15 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const double t_3 = now();
     // the value streams' chunks (few, long serial chains) decode next to the binary maps' blocks (many, short), on a second stream
     static const bool serial = getenv("RC_READ_SERIAL") != nullptr;   // development: both decoders on one stream (clean per-kernel times)
-    if (n_pv && serial) launch_block_decode(1, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, s);
+    if (n_pv && serial) launch_block_decode(EMIT_ZSTD, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, s);
     else if (n_pv) {
         HIP_TRY(hipEventRecord(u.ev_a, s));
         HIP_TRY(hipStreamWaitEvent(u.stream2, u.ev_a, 0));
-        launch_block_decode(1, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, u.stream2);
+        launch_block_decode(EMIT_ZSTD, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, u.stream2);
         HIP_TRY(hipEventRecord(u.ev_b, u.stream2));
     }
-    if (cbm_max) launch_bitmap_decode_compact(codec == 1 ? 1 : 2, d_data, d_cbm_list, d_src_base, n, cbm_max, d_bm_tab, U.zd_predef, d_out, d_base2, nb, d_err, s);
-    if (n_bm) launch_block_decode(codec == 1 ? 1 : 2, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
+    if (cbm_max) launch_bitmap_decode_compact(codec, d_data, d_cbm_list, d_src_base, n, cbm_max, d_bm_tab, U.zd_predef, d_out, d_base2, nb, d_err, s);
+    if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
     launch_block_copy(d_data, d_raw_list, nthr, (uint32_t)n_raw, raw_max_regen, d_out, d_base2, s);
     if (n_pv && !serial) HIP_TRY(hipStreamWaitEvent(s, u.ev_b, 0));
     const uint8_t *d_bm = d_out, *d_pv = d_out + (uint64_t)n * bm_stride;

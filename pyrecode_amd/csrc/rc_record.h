@@ -19,12 +19,12 @@ namespace rc {
 struct FrameFmt { uint32_t hdr, end, chunk_shift, chunk_hdr, min_chunks; };
 __host__ __device__ inline FrameFmt frame_fmt(uint32_t emit)
 {
-    return emit == 1 ? FrameFmt{6, 0, 17, 3, 1} : emit == 8 ? FrameFmt{16, 0, 31, 0, 0} : emit == EMIT_DEFLATE ? FrameFmt{2, 4, 15, 5, 1} : FrameFmt{7, 4, 22, 4, 0};
+    return emit == EMIT_ZSTD ? FrameFmt{6, 0, 17, 3, 1} : emit == EMIT_BLOSC ? FrameFmt{16, 0, 31, 0, 0} : emit == EMIT_DEFLATE ? FrameFmt{2, 4, 15, 5, 1} : FrameFmt{7, 4, 22, 4, 0};
 }
 // bytes in front of the encoded bitmap blocks
 __host__ __device__ inline uint32_t bitmap_hdr(const FrameFmt &ff, uint32_t emit, uint32_t ntiles)
 {
-    return emit == 8 ? 16u + 4u * ntiles : ff.hdr;
+    return emit == EMIT_BLOSC ? 16u + 4u * ntiles : ff.hdr;
 }
 
 __host__ __device__ inline uint32_t packed_bytes(uint32_t nnz, uint32_t depth)
@@ -60,15 +60,15 @@ __device__ __forceinline__ void record_fixed_fields(const S &sc, const RecordPar
                                                     uint32_t cb, uint32_t npk, const FrameFmt &ff, bool skip_pix, uint32_t lz4f_hdr_bitmap, uint32_t lz4f_hdr_pix)
 {
     store_u32_le(rec, rp.first_frame_id + f);
-    if (rp.emit == 0) {
+    if (rp.emit == EMIT_RAW) {
         if (rp.level == 1) store_u32_le(rec + 4, npk);
     } else {
         store_u32_le(rec + 4, cb);
         uint8_t *bf = rec + bitmap_pos;
-        if (rp.emit == 1) {  // zstd: magic, Frame_Header_Descriptor 0 (no content size, window descriptor follows), 1 KiB window
+        if (rp.emit == EMIT_ZSTD) {  // zstd: magic, Frame_Header_Descriptor 0 (no content size, window descriptor follows), 1 KiB window
             store_u32_le(bf, 0xFD2FB528u);
             bf[4] = 0; bf[5] = 0x00;
-        } else if (rp.emit == 8) {  // blosc1 header: version 2, LZ4 format version 1, bit-shuffle | not split | LZ4, typesize 8
+        } else if (rp.emit == EMIT_BLOSC) {  // blosc1 header: version 2, LZ4 format version 1, bit-shuffle | not split | LZ4, typesize 8
             bf[0] = 2; bf[1] = 1; bf[2] = 0x34; bf[3] = 8;
             store_u32_le(bf + 4, (uint32_t)sc.nb);
             store_u32_le(bf + 8, (uint32_t)min((uint64_t)TILE_BM, sc.nb));
@@ -90,7 +90,7 @@ __device__ __forceinline__ void record_fixed_fields(const S &sc, const RecordPar
             store_u32_le(rec + 12, npk);
             uint8_t *pf = rec + pix_pos;
             const uint32_t chunk = 1u << ff.chunk_shift, nch = stored_chunks(ff, npk);
-            if (rp.emit == 8) {  // blosc1 header with the "memcpyed" flag: the packed residuals follow unchanged
+            if (rp.emit == EMIT_BLOSC) {  // blosc1 header with the "memcpyed" flag: the packed residuals follow unchanged
                 pf[0] = 2; pf[1] = 1; pf[2] = 0x36; pf[3] = 8;
                 store_u32_le(pf + 4, npk);
                 store_u32_le(pf + 8, npk);
@@ -103,7 +103,7 @@ __device__ __forceinline__ void record_fixed_fields(const S &sc, const RecordPar
                     q[0] = k + 1 == nch ? 1 : 0;
                     q[1] = (uint8_t)len; q[2] = (uint8_t)(len >> 8); q[3] = (uint8_t)~len; q[4] = (uint8_t)(~len >> 8);
                 }
-            } else if (rp.emit == 1) {  // 128 KiB window so that 128 KiB raw blocks are legal
+            } else if (rp.emit == EMIT_ZSTD) {  // 128 KiB window so that 128 KiB raw blocks are legal
                 store_u32_le(pf, 0xFD2FB528u);
                 pf[4] = 0; pf[5] = 7u << 3;
                 for (uint32_t k = 0; k < nch; ++k) {

@@ -284,15 +284,15 @@ __device__ __forceinline__ uint32_t flush_pending(const Pending &p, uint32_t til
         d0 = reinterpret_cast<uint8_t *>(pix_slots + p.ft * SLOT_PX);   // slots are 8 KiB aligned
         q0 = ((((p.cnt * p.depth + 31) >> 5) + 31u) & ~31u) >> 2;       // whole lines, in 16-byte units
     }
-    if (CODEC == 2 || CODEC == 4 || CODEC == 8) {
-        const uint64_t bytes = CODEC != 8 ? ((uint64_t)p.own[0] | ((uint64_t)p.own[1] << 32)) : p.cown;
-        bsz = lz4_stage_slot(bytes, n_blk, p.csize, *lz, CODEC == 8);
+    if (CODEC == CODEC_LZ4_RUNS || CODEC == CODEC_LZ4_EVENTS || CODEC == CODEC_BLOSC) {
+        const uint64_t bytes = CODEC != CODEC_BLOSC ? ((uint64_t)p.own[0] | ((uint64_t)p.own[1] << 32)) : p.cown;
+        bsz = lz4_stage_slot(bytes, n_blk, p.csize, *lz, CODEC == CODEC_BLOSC);
     }
-    if (CODEC == 1 || CODEC == 3) {
+    if (CODEC == CODEC_ZSTD_FAST || CODEC == CODEC_ZSTD_MODELLED) {
         (void)zstd_stage_slot(n_blk, p.last, p.staged, *lz);
         bsz = p.staged ? p.staged : 4u;
     }
-    if (CODEC == 5) bsz = p.csize;   // deflate: the tile's share of the stream stands complete in the stage (rc_deflate_block.h)
+    if (CODEC == CODEC_DEFLATE) bsz = p.csize;   // the tile's share of the stream stands complete in the stage (rc_deflate_block.h)
     if (CODEC) {
         s1 = lz->out;
         d1 = blk_slots + p.ft * blk_stride;
@@ -301,10 +301,10 @@ __device__ __forceinline__ uint32_t flush_pending(const Pending &p, uint32_t til
     if (LEVEL1 && CODEC && comb) {
         // combined slot (Scratch::comb, rc_launch.h::residual_src is the reader's side of this rule): the residual stream behind the
         // block image, in the block's slot, when both fit it
-        const uint32_t ro16 = comb == 2 ? (uint32_t)BLK_SLOT / 16 : (bsz + 15) >> 4, r16 = (p.cnt * p.depth + 127) >> 7;
+        const uint32_t ro16 = comb == COMB_AT_BLK_SLOT ? (uint32_t)BLK_SLOT / 16 : (bsz + 15) >> 4, r16 = (p.cnt * p.depth + 127) >> 7;
         if (16 * (ro16 + r16) <= blk_stride) {
             d0 = d1 + 16 * ro16;
-            if (comb == 2) q0 = (r16 + 7u) & ~7u;                                   // two runs of whole lines in one slot
+            if (comb == COMB_AT_BLK_SLOT) q0 = (r16 + 7u) & ~7u;                    // two runs of whole lines in one slot
             else { q1 = ro16; q0 = ((ro16 + r16 + 7u) & ~7u) - ro16; }              // ONE run: block units, then residual units up to the line's end
         }
     }
@@ -315,15 +315,15 @@ __device__ __forceinline__ uint32_t flush_pending(const Pending &p, uint32_t til
     }
     // the 4-byte results: lane 0 the count, lane 1 the block's size word, one instruction
     if (LEVEL1 || CODEC) {
-        const uint32_t word = CODEC == 1 || CODEC == 3 ? p.csize : bsz;   // zstd: the tokenizer's word (k_zstd_fse finishes the block)
+        const uint32_t word = CODEC == CODEC_ZSTD_FAST || CODEC == CODEC_ZSTD_MODELLED ? p.csize : bsz;   // zstd: the tokenizer's word (k_zstd_fse finishes the block)
         // (deflate: one lane more, the tile's Adler-32 partials)
-        if (LEVEL1 && CODEC == 5) {
+        if (LEVEL1 && CODEC == CODEC_DEFLATE) {
             if (lane < 3) *(lane == 0 ? &tile_cnt[p.ft] : (lane == 1 ? &blk_size[p.ft] : &blk_aux[p.ft])) = lane == 0 ? p.cnt : (lane == 1 ? word : p.aux);
         } else if (LEVEL1 && CODEC) {
             if (lane < 2) *(lane == 0 ? &tile_cnt[p.ft] : &blk_size[p.ft]) = lane == 0 ? p.cnt : word;
         } else if (LEVEL1) {
             if (lane == 0) tile_cnt[p.ft] = p.cnt;
-        } else if (CODEC == 5) {
+        } else if (CODEC == CODEC_DEFLATE) {
             if (lane < 2) *(lane == 0 ? &blk_size[p.ft] : &blk_aux[p.ft]) = lane == 0 ? word : p.aux;
         } else {
             if (lane == 0) blk_size[p.ft] = word;
@@ -533,28 +533,28 @@ __device__ __forceinline__ void reduce_one_frame(typename Src<SB>::X (&x)[R], co
         if (!packed && pend.depth < 16 && wave_total) pack_stage(pend.buf, wave_total, pend.depth);
     }
     RC_PHASE(4);
-    if (CODEC == 2) {
+    if (CODEC == CODEC_LZ4_RUNS) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.csize = lz4_encode_block<false>(bytes, n_blk, *s_lz);
     }
-    if (CODEC == 4) {  // LZ4, compression_level >= 1: the event parser (rc_lz4_block.h)
+    if (CODEC == CODEC_LZ4_EVENTS) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.csize = lz4_encode_block<true>(bytes, n_blk, *s_lz);
     }
-    if (CODEC == 1) {
+    if (CODEC == CODEC_ZSTD_FAST) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.csize = zstd_tokenize_block(bytes, n_blk, pend.last, *s_lz, pend.staged);
     }
-    if (CODEC == 3) {  // zstd, modelled: Huffman-coded literals + tokens for the ctx's fitted tables (rc_zstd_wave.h)
+    if (CODEC == CODEC_ZSTD_MODELLED) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.csize = zstd_tokenize_block_m(bytes, n_blk, pend.last, *s_lz, pend.staged, zp);
     }
-    if (CODEC == 5) {  // deflate (compression_scheme 0 on the device): a fixed-Huffman block per tile + its Adler-32 partials (rc_deflate_block.h)
+    if (CODEC == CODEC_DEFLATE) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.aux = deflate_adler_word(bytes, tile);
         pend.csize = deflate_encode_block<true>(bytes, n_blk, pend.last, *s_lz);
     }
-    if (CODEC == 8) {  // blosc1 block: bit-shuffle (typesize 8), then the LZ4 block encoder
+    if (CODEC == CODEC_BLOSC) {
         const uint64_t bytes = (uint64_t)pend.own[0] | ((uint64_t)pend.own[1] << 32);
         pend.cown = bitshuffle_block(bytes, n_blk, *s_lz);
         pend.csize = lz4_encode_block(pend.cown, n_blk, *s_lz);
@@ -578,8 +578,7 @@ __device__ __forceinline__ void reduce_one_frame(typename Src<SB>::X (&x)[R], co
 //   -> bitmap bytes transposed through wave-private LDS (8 contiguous bytes = the mask of 64 consecutive pixels per lane)
 //   -> [LEVEL1] one DPP prefix sum of the per-lane popcounts, each lane moves its set pixels into the compact buffer,
 //      [depth < 16] packed in place to the tile-local d-bit stream
-//   -> [CODEC 2 / 1 / 8] the 512-byte bitmap block is LZ4-encoded / zstd-tokenized / bit-shuffled + LZ4-encoded in LDS
-//      (rc_lz4_block.h, rc_zstd_wave.h)
+//   -> [CODEC] the 512-byte bitmap block is encoded in LDS (rc_lz4_block.h, rc_zstd_wave.h, rc_deflate_block.h)
 //   -> all global stores (residuals, encoded block, raw bitmap, counts) go out last, as whole 128-byte lines (flush_pending)
 //
 // ASMLOAD instantiation (aligned frames, every tile of the launch lies wholly inside the frame): the frames are read through
@@ -603,8 +602,8 @@ __global__ __launch_bounds__(64 * RWAVES) __attribute__((amdgpu_waves_per_eu((AL
 {
     // first kernel of a batch: clears the batch's status word (written later by k_layout / the level-2 kernels)
     if (blockIdx.x == 0 && threadIdx.x == 0) { status->code = 0; status->frame = 0; status->total = 0; }
-    __shared__ uint16_t s_code[CODEC == 3 ? 256 : 2];                                           // modelled zstd: Huffman code table
-    if (CODEC == 3) {   // (the only barrier of the kernel, in front of every early exit)
+    __shared__ uint16_t s_code[CODEC == CODEC_ZSTD_MODELLED ? 256 : 2];                          // modelled zstd: Huffman code table
+    if (CODEC == CODEC_ZSTD_MODELLED) {   // (the only barrier of the kernel, in front of every early exit)
         for (uint32_t i = threadIdx.x; i < 128; i += 64 * RWAVES) reinterpret_cast<uint32_t *>(s_code)[i] = reinterpret_cast<const uint32_t *>(zm.lit_code)[i];
         __syncthreads();
         zm.lit_code = s_code;
@@ -674,7 +673,7 @@ static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames
     // tile (N not a multiple of TILE_PX) gets a second, tiny launch of the plain one
     const uint32_t nfull = AL ? (uint32_t)(sc.N / TILE_PX) : 0u;
     const ZmParams zm{reinterpret_cast<const uint16_t *>(sc.zm_lit_code), sc.zm_valid, sc.zm_budget, sc.zm_seq_bits};
-    const uint32_t comb = (L1 && !RAW && CODEC) ? sc.comb : 0u;   // (level 2 keeps raw values in pix_slots: rc_l2.hip reads them there)
+    const uint32_t comb = (L1 && !RAW && CODEC) ? sc.comb : COMB_OFF;   // (level 2 keeps raw values in pix_slots: rc_l2.hip reads them there)
     // Workgroups of THREE waves let five of them (15 waves) share a CU's LDS where four-wave workgroups fit three (12 waves).  Same-box
     // A/B against the two-register-set kernel of round 2 (profiles/r04_ab_waves.log): LZ4 level 1 +1.3..3.5 %, d = 12 +4.5 %, 11520 x 8184
     // zstd +4.5 %; level 3 / mode 0 (nothing to gain from LDS, three-wave workgroups cost 2-4 %) and the configurations whose second
@@ -682,7 +681,8 @@ static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames
     // kernel got 5 % shorter) keep four-wave workgroups.
     // (modelled zstd whose blocks carry literals only - dense maps, rc_zstd_model.h - has no FSE pass behind the reduce kernel: its
     // second stage is as short as LZ4's, and three-wave workgroups gain 0.5-3 % there as well)
-    const bool three = L1 && !RAW && CODEC != 5 && (CODEC == 2 || CODEC == 4 || sc.ntiles > 8192 || (CODEC == 3 && (sc.zm_valid & ZM_LITS_ONLY)));
+    const bool three = L1 && !RAW && CODEC != CODEC_DEFLATE &&
+                       (CODEC == CODEC_LZ4_RUNS || CODEC == CODEC_LZ4_EVENTS || sc.ntiles > 8192 || (CODEC == CODEC_ZSTD_MODELLED && (sc.zm_valid & ZM_LITS_ONLY)));
     auto go = [&](auto rw) {
         constexpr int RW = decltype(rw)::value;
         auto grid_for = [&](uint32_t nt) { return (((nt + RW - 1) / RW + 7) / 8) * 8 * ngroups; };
@@ -704,28 +704,24 @@ static void launch_reduce_t(const Scratch &sc, const typename Src<SB>::T *frames
         }
     };
     if constexpr (SB == 2) {
-        if (three) { go(std::integral_constant<int, 3>{}); return; }   // (two-wave workgroups: profiles/r04_ab_two_wave_workgroups.log)
+        if (three) { go(int_c<3>{}); return; }   // (two-wave workgroups: profiles/r04_ab_two_wave_workgroups.log)
     }
-    go(std::integral_constant<int, 4>{});   // (uint8 frames: four-wave workgroups only - half the instantiations)
+    go(int_c<4>{});   // (uint8 frames: four-wave workgroups only - half the instantiations)
 }
 template <int BZ, bool AL, bool L1, bool RAW, int SB>
 static void launch_reduce_c(const Scratch &sc, const typename Src<SB>::T *frames, uint32_t B, uint32_t codec, bool keep, uint32_t depth, hipStream_t s, hipStream_t s_tail)
 {
     // raw-value (level 2) instantiations always keep the bitmap: the labelling kernels read it
     if (RAW) keep = true;
-#define RC_CODEC(C)                                                                                          \
-    do {                                                                                                     \
-        if (keep) launch_reduce_t<BZ, AL, L1, C, true, RAW, SB>(sc, frames, B, depth, s, s_tail);                \
-        else if (!RAW && C != 0) launch_reduce_t<BZ, AL, L1, C, false, false, SB>(sc, frames, B, depth, s, s_tail); \
-    } while (0)
-    if (codec == 2) RC_CODEC(2);
-    else if (codec == 4) RC_CODEC(4);
-    else if (codec == 1) RC_CODEC(1);
-    else if (codec == 3) RC_CODEC(3);
-    else if (codec == 8) RC_CODEC(8);
-    else if (codec == 5) RC_CODEC(5);
-    else launch_reduce_t<BZ, AL, L1, 0, true, RAW, SB>(sc, frames, B, depth, s, s_tail);
+#define RC_CODEC(C)                                                                                      \
+    if (codec == C) {                                                                                    \
+        if (keep) launch_reduce_t<BZ, AL, L1, C, true, RAW, SB>(sc, frames, B, depth, s, s_tail);        \
+        else if (!RAW) launch_reduce_t<BZ, AL, L1, C, false, false, SB>(sc, frames, B, depth, s, s_tail); \
+        return;                                                                                          \
+    }
+    RC_CODEC(CODEC_LZ4_RUNS) RC_CODEC(CODEC_LZ4_EVENTS) RC_CODEC(CODEC_ZSTD_FAST) RC_CODEC(CODEC_ZSTD_MODELLED) RC_CODEC(CODEC_BLOSC) RC_CODEC(CODEC_DEFLATE)
 #undef RC_CODEC
+    launch_reduce_t<BZ, AL, L1, CODEC_NONE, true, RAW, SB>(sc, frames, B, depth, s, s_tail);   // (no encoder: the raw maps are the output, always kept)
 }
 template <int BZ, bool AL, int SB>
 static void launch_reduce_a(const Scratch &sc, const typename Src<SB>::T *frames, uint32_t B, uint32_t level, uint32_t codec, bool keep,
@@ -1158,14 +1154,14 @@ __global__ __launch_bounds__(LWG) void k_layout(const uint32_t *__restrict__ fra
         const uint32_t npk = rp.level == 1 ? packed_bytes(nnz, rp.depth) : 0;
         uint64_t sz;
         uint32_t m0 = 0, m1 = 0, m2 = 0;
-        if (rp.emit == 0) {
+        if (rp.emit == EMIT_RAW) {
             if (rp.level == 1) { sz = 8 + nb + npk; m0 = npk; }
             else sz = 4 + nb;
-        } else {  // LZ4 frames (emit == 2)
+        } else {
             const FrameFmt ff = frame_fmt(rp.emit);
             const uint32_t cb = bitmap_hdr(ff, rp.emit, ntiles) + frame_cbytes[f] + ff.end;
             if (rp.level == 1) {
-                const uint32_t cp = rp.pix_mode == 2 ? ff.hdr + frame_pbytes[f] : stored_size(ff, npk);
+                const uint32_t cp = rp.pix_mode == PIX_MODE_SKIP ? ff.hdr + frame_pbytes[f] : stored_size(ff, npk);
                 sz = 16 + (uint64_t)cb + cp; m0 = cb; m1 = cp; m2 = npk;
             } else { sz = 8 + (uint64_t)cb; m0 = cb; }
         }

@@ -27,7 +27,7 @@ constexpr int R32_WAVES = 1;   // wavefronts per workgroup (each with its own ti
 constexpr int R32_FPW = 16;    // frames a wavefront keeps its tile for (the thresholds are read once per R32_FPW frames)
 struct __attribute__((aligned(16))) Stage32 {
     uint32_t out[TILE_PX];     // compacted residuals in pixel order, then packed in place
-    Lz4Lds lz;                 // lz.raw: the tile's bitmap bytes in pixel order = the block image of the LZ4 encoder (fused: CODEC 2 / 4)
+    Lz4Lds lz;                 // lz.raw: the tile's bitmap bytes in pixel order = the block image of the fused encoder
 };
 
 __global__ void k_threshold32(const uint32_t *__restrict__ dark, uint32_t eps, uint64_t N, uint32_t *__restrict__ thr)
@@ -70,9 +70,8 @@ __device__ __forceinline__ void load_tile32(const uint32_t *__restrict__ base, u
 }
 
 // A2-A5 of one tile of one frame from registers
-// CODEC: 0 = none (only the raw map leaves), 1 = the zstd tokenizer (fast form), 2 / 4 = the LZ4 block encoder (runs / events), 8 = blosc1's
-// bit-shuffle + LZ4 runs - on the tile's map
-// here: the encoded block goes to the tile's block slot, the raw map only where the caller keeps binary maps (bm_dst != nullptr)
+// CODEC: the encoder run on the tile's map (CODEC_NONE: only the raw map leaves); the encoded block goes to the tile's block slot, the raw
+// map only where the caller keeps binary maps (bm_dst != nullptr)
 template <int CODEC>
 __device__ __forceinline__ void reduce_tile32(Stage32 &S, const u32x4 (&x)[2 * R], const u32x4 (&t)[2 * R], uint8_t *__restrict__ bm_dst,
                                               uint8_t *__restrict__ slot, uint32_t *__restrict__ cnt_dst, uint32_t depth, bool level1,
@@ -114,7 +113,7 @@ __device__ __forceinline__ void reduce_tile32(Stage32 &S, const u32x4 (&x)[2 * R
     __builtin_amdgcn_wave_barrier();
     const u32x2 ownv = *reinterpret_cast<const u32x2 *>(&S.lz.raw[lane * 8]);
     if (bm_dst) *reinterpret_cast<u32x2 *>(bm_dst + lane * 8) = ownv;
-    if (CODEC == 1) {   // zstd, the fast encoder's wave-collective half (k_zstd_fse finishes the block)
+    if (CODEC == CODEC_ZSTD_FAST) {   // the wave-collective half (k_zstd_fse finishes the block)
         uint32_t staged;
         const uint32_t word = zstd_tokenize_block((uint64_t)ownv[0] | ((uint64_t)ownv[1] << 32), n_blk, last_blk, S.lz, staged);
         zstd_store_block(blk_slot, n_blk, last_blk, word, staged, S.lz);
@@ -122,9 +121,9 @@ __device__ __forceinline__ void reduce_tile32(Stage32 &S, const u32x4 (&x)[2 * R
         __builtin_amdgcn_wave_barrier();
     } else if (CODEC) {
         uint64_t own = (uint64_t)ownv[0] | ((uint64_t)ownv[1] << 32);
-        if (CODEC == 8) own = bitshuffle_block(own, n_blk, S.lz);   // blosc1: the block's bit-shuffle in front of the LZ4 run encoder
-        const uint32_t csize = lz4_encode_block<CODEC == 4>(own, n_blk, S.lz);
-        const uint32_t used = lz4_store_block(blk_slot, own, n_blk, csize, S.lz, CODEC == 8);
+        if (CODEC == CODEC_BLOSC) own = bitshuffle_block(own, n_blk, S.lz);
+        const uint32_t csize = lz4_encode_block<CODEC == CODEC_LZ4_EVENTS>(own, n_blk, S.lz);
+        const uint32_t used = lz4_store_block(blk_slot, own, n_blk, csize, S.lz, CODEC == CODEC_BLOSC);
         if (lane == 0) *blk_size_dst = used;
         __builtin_amdgcn_wave_barrier();   // S.lz is the next frame's
     }
@@ -207,14 +206,13 @@ __global__ __launch_bounds__(64 * R32_WAVES) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
-// codec: 0 = the raw maps only (reduce-only records), 1 = zstd (fast form; k_zstd_fse follows), 2 / 4 = LZ4 runs / events, 8 = blosc-lz4
-// fused; keep_bitmap: the raw maps leave as well (validation frames, rc_get_binary_map)
+// keep_bitmap: the raw maps leave as well (validation frames, rc_get_binary_map)
 void launch_reduce32(const Scratch &sc, const uint32_t *frames, const uint32_t *thr32, uint32_t B, uint32_t level, uint32_t depth, hipStream_t s,
                      uint32_t codec, bool keep_bitmap)
 {
     const uint32_t nfull = (uint32_t)(sc.N / TILE_PX), fy = (B + R32_FPW - 1) / R32_FPW;
     uint8_t *slots = reinterpret_cast<uint8_t *>(sc.pix_slots);
-    uint8_t *bitmap = (codec == 0 || keep_bitmap) ? sc.bitmap : nullptr;
+    uint8_t *bitmap = (codec == CODEC_NONE || keep_bitmap) ? sc.bitmap : nullptr;
     auto go = [&](auto full, auto cd) {
         constexpr bool FULL = decltype(full)::value;
         constexpr int CODEC = decltype(cd)::value;
@@ -227,11 +225,11 @@ void launch_reduce32(const Scratch &sc, const uint32_t *frames, const uint32_t *
         if (nfull) go(std::true_type{}, cd);
         if (nfull < sc.ntiles) go(std::false_type{}, cd);
     };
-    if (codec == 2) both(std::integral_constant<int, 2>{});
-    else if (codec == 4) both(std::integral_constant<int, 4>{});
-    else if (codec == 8) both(std::integral_constant<int, 8>{});
-    else if (codec == 1) both(std::integral_constant<int, 1>{});
-    else both(std::integral_constant<int, 0>{});
+    if (codec == CODEC_LZ4_RUNS) both(int_c<CODEC_LZ4_RUNS>{});
+    else if (codec == CODEC_LZ4_EVENTS) both(int_c<CODEC_LZ4_EVENTS>{});
+    else if (codec == CODEC_BLOSC) both(int_c<CODEC_BLOSC>{});
+    else if (codec == CODEC_ZSTD_FAST) both(int_c<CODEC_ZSTD_FAST>{});
+    else both(int_c<CODEC_NONE>{});
 }
 
 }  // namespace rc

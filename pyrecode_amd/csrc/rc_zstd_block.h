@@ -53,11 +53,14 @@ struct ZstdModel {
     uint8_t pix_desc[ZM_DESC_MAX];
     uint8_t seq_desc[ZM_DESC_MAX];        // [LL FSE table description][0x00 = the offset code of RLE mode][ML description]
     uint32_t lit_desc_len, pix_desc_len, seq_desc_len;
-    uint32_t valid;                       // bit 0: lit, bit 1: pix, bit 2: seq usable; bit 3: LITERALS ONLY - the binary maps' blocks carry all
-                                          // their bytes as Huffman-coded literals and no sequences (dense maps: zm_build_model), lit_code
-                                          // is then fitted to ALL bytes of the non-empty blocks
+    uint32_t valid;                       // ZM_* bits
 };
-constexpr uint32_t ZM_LITS_ONLY = 8u;
+// ZstdModel::valid
+constexpr uint32_t ZM_LIT_CODE = 1u;      // lit_code / lit_desc usable
+constexpr uint32_t ZM_PIX_CODE = 2u;      // pix_code / pix_desc usable: the residual stream is Huffman-coded (rc_pix_huff.hip)
+constexpr uint32_t ZM_SEQ_TABLES = 4u;    // seq / seq_desc usable: the blocks' sequences use the fitted FSE tables
+constexpr uint32_t ZM_LITS_ONLY = 8u;     // the binary maps' blocks carry all their bytes as Huffman-coded literals and no sequences (dense maps:
+                                          // zm_build_model), lit_code is then fitted to ALL bytes of the non-empty blocks
 struct ZstdSample {   // histograms gathered by k_zstd_sample over a sample of frames
     uint32_t lit[256], pix[256], ll[64], ml[64];
     uint32_t all[256];                    // every byte of the sample's binary-map blocks that are not all zero (those are RLE blocks either way)
@@ -349,7 +352,7 @@ RC_HD uint32_t zm_raw_lit_header(uint8_t *p, uint32_t nlit)
 // a compressed block may take part only if it still fits its slot once BOTH descriptions have been inserted into it
 RC_HD uint32_t zm_block_budget(const ZstdModel &M, uint32_t slot_bytes)
 {
-    return slot_bytes - 8u - ((M.valid & 1u) ? M.lit_desc_len : 0u) - ((M.valid & 4u) ? M.seq_desc_len : 0u);
+    return slot_bytes - 8u - ((M.valid & ZM_LIT_CODE) ? M.lit_desc_len : 0u) - ((M.valid & ZM_SEQ_TABLES) ? M.seq_desc_len : 0u);
 }
 
 // One block, serial (host only): the same parse as zstd_encode_block (zero runs >= 4 -> [literal 00][match: repeat offset 1]).
@@ -388,8 +391,8 @@ inline uint32_t zstd_encode_block_model(const uint8_t *src, uint32_t n, uint8_t 
     }
     uint8_t *p = dst + 3;
     uint32_t hb = 0;
-    if (M.valid & 1u) hb = zm_huf_stream(lits, nlit, M.lit_code, hbuf);
-    if ((M.valid & 1u) && 3 + hb < zm_raw_lit_header(p, nlit) + nlit) {   // Huffman pays
+    if (M.valid & ZM_LIT_CODE) hb = zm_huf_stream(lits, nlit, M.lit_code, hbuf);
+    if ((M.valid & ZM_LIT_CODE) && 3 + hb < zm_raw_lit_header(p, nlit) + nlit) {   // Huffman pays
         zm_lit_header(p, 3, nlit, hb);
         p += 3;
         for (uint32_t i = 0; i < hb; ++i) *p++ = hbuf[i];
@@ -400,7 +403,7 @@ inline uint32_t zstd_encode_block_model(const uint8_t *src, uint32_t n, uint8_t 
     if (nseq < 128) *p++ = (uint8_t)nseq;
     else { *p++ = (uint8_t)(128 + (nseq >> 8)); *p++ = (uint8_t)nseq; }
     if (nseq) {
-        const bool fitted = (M.valid & 4u) != 0;
+        const bool fitted = (M.valid & ZM_SEQ_TABLES) != 0;
         ZstdTables pre;
         if (!fitted) zstd_build_tables(pre);
         const ZstdTables &T = fitted ? M.seq : pre;
@@ -504,9 +507,9 @@ RC_HD uint32_t zm_encode_pix_chunk(const uint8_t *src, uint32_t n, uint8_t *dst,
 {
     const uint32_t lastbit = last ? 1u : 0u;
     uint32_t hb = 0;
-    if ((M.valid & 2u) && n) hb = zm_huf_stream(src, n, M.pix_code, hbuf);
+    if ((M.valid & ZM_PIX_CODE) && n) hb = zm_huf_stream(src, n, M.pix_code, hbuf);
     const uint32_t budget = n > M.pix_desc_len + 8u ? n - M.pix_desc_len - 8u : 0u;   // must still beat Raw with the tree inserted
-    if (!(M.valid & 2u) || n == 0 || 3 + hb + 1 >= budget) {
+    if (!(M.valid & ZM_PIX_CODE) || n == 0 || 3 + hb + 1 >= budget) {
         const uint32_t h = lastbit | (n << 3);
         dst[0] = (uint8_t)h; dst[1] = (uint8_t)(h >> 8); dst[2] = (uint8_t)(h >> 16);
         for (uint32_t i = 0; i < n; ++i) dst[3 + i] = src[i];

@@ -277,7 +277,7 @@ __device__ uint32_t lz4_block_decode(const uint8_t *src, uint32_t n, Sink<true> 
 // memory each of them is a full memory latency.  (Before: rows of regenerated bytes in LDS, compressed bytes from global memory -
 // 1.18 ms for the 262 144 binary-map blocks of 64 frames of 4096 x 4096.)  The regenerated bytes go straight to global memory
 // (Sink), which the caller has zeroed.
-// CODEC 1: zstd Compressed blocks, 2: LZ4 compressed blocks.  SPAN: staged bytes (multiple of 16).
+// CODEC: EMIT_ZSTD (zstd Compressed blocks) or EMIT_LZ4 (LZ4 compressed blocks).  SPAN: staged bytes (multiple of 16).
 template <int CODEC, bool SPARSE, int T, int SPAN>
 __global__ __launch_bounds__(T) void k_block_decode(const uint8_t *__restrict__ data, const ZdFrameList *__restrict__ lists,
                                                       const ZdTables *__restrict__ tables,
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(T) void k_block_decode(const uint8_t *__restrict__ 
     const uint32_t i0 = blockIdx.x * T;
     if (i0 >= hi) return;
     const uint32_t tid = threadIdx.x;
-    if (CODEC == 1) {
+    if (CODEC == EMIT_ZSTD) {
         if (tid < 36) s_llx[tid] = c_ll_base[tid] | ((uint32_t)c_ll_bits[tid] << 16);
         if (tid < 53) s_mlx[tid] = c_ml_base[tid] | ((uint32_t)c_ml_bits[tid] << 16);
         const uint32_t *src = reinterpret_cast<const uint32_t *>(tables + f);
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(T) void k_block_decode(const uint8_t *__restrict__ 
     // flat load, which is ordered behind the lane's outstanding global stores (flat and global memory instructions share vmcnt) -
     // a full store latency per few symbols (measured: 300 ns per literal of a value-stream chunk).
     auto run = [&](const uint8_t *c) {
-        if (CODEC == 1) {
+        if (CODEC == EMIT_ZSTD) {
             const bool fr = b.seq_tables != 0;
             return zstd_block_decode<SPARSE>(c, b.csize, b, s_t.huf, s_t.huf_log, fr ? s_t.ll : s_pll, fr ? s_t.ll_log : 6u, fr ? s_t.ml : s_pml,
                                              fr ? s_t.ml_log : 6u, s_llx, s_mlx, o, b.regen, &e);
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(T) void k_block_decode(const uint8_t *__restrict__ 
 // table modes from the block itself.  The lists are read over the link (page-locked host memory, once): 1 MB instead of 8 MB per 64
 // frames of 4096 x 4096 - with full entries the link, not the decoder, set this kernel's time (315 us; entries in device memory: 159).
 //   lists[f].p   const uint32_t *: header offsets relative to src_base[f];  lists[f].pad = tree_skip | seq_skip << 8
-// CODEC 1: zstd (3-byte block headers; Raw and RLE blocks are handled in line), 2: LZ4 frame blocks (4-byte size words, bit 31 = stored).
+// CODEC: EMIT_ZSTD (3-byte block headers; Raw and RLE blocks are handled in line) or EMIT_LZ4 (4-byte size words, bit 31 = stored).
 template <int CODEC, int T, int SPAN>
 __global__ __launch_bounds__(T) void k_bitmap_decode_c(const uint8_t *__restrict__ data, const ZdFrameList *__restrict__ lists,
                                                          const uint64_t *__restrict__ src_base, const ZdTables *__restrict__ tables,
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(T) void k_bitmap_decode_c(const uint8_t *__restrict
     const uint32_t i0 = blockIdx.x * T;
     if (i0 >= hi) return;
     const uint32_t tid = threadIdx.x;
-    if (CODEC == 1) {
+    if (CODEC == EMIT_ZSTD) {
         if (tid < 36) s_llx[tid] = c_ll_base[tid] | ((uint32_t)c_ll_bits[tid] << 16);
         if (tid < 53) s_mlx[tid] = c_ml_base[tid] | ((uint32_t)c_ml_bits[tid] << 16);
         const uint32_t *src = reinterpret_cast<const uint32_t *>(tables + f);
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(T) void k_bitmap_decode_c(const uint8_t *__restrict
     const uint32_t bi = i0 + tid;
     if (bi >= hi) return;
     const uint64_t h0 = fb + offs[bi], h1 = fb + offs[bi + 1];
-    constexpr uint32_t HDR = CODEC == 1 ? 3u : 4u;
+    constexpr uint32_t HDR = CODEC == EMIT_ZSTD ? 3u : 4u;
     int e = 0;
     if (h1 < h0 + HDR) e = 1;
     const uint32_t regen = (uint32_t)min<uint64_t>((uint64_t)TILE_BM, nb - (uint64_t)bi * TILE_BM);
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(T) void k_bitmap_decode_c(const uint8_t *__restrict
         b.src = h0 + HDR; b.csize = (uint32_t)(h1 - h0) - HDR; b.dst = 0; b.regen = regen; b.frame = f; b.flex = 0;
         b.tree_skip = (uint8_t)skips; b.seq_skip = (uint8_t)(skips >> 8); b.seq_tables = 2;
         const uint8_t *c = h + HDR;
-        if (CODEC == 1) {
+        if (CODEC == EMIT_ZSTD) {
             const uint32_t hd = (uint32_t)h[0] | ((uint32_t)h[1] << 8) | ((uint32_t)h[2] << 16);
             const uint32_t type = (hd >> 1) & 3u, bs = hd >> 3;
             if (type == 2) {
@@ -455,14 +455,14 @@ void launch_block_decode(int codec, int row, const uint8_t *data, const void *fr
     const ZdFrameList *l = reinterpret_cast<const ZdFrameList *>(frame_lists);
     const ZdTables *t = reinterpret_cast<const ZdTables *>(tables), *p = reinterpret_cast<const ZdTables *>(predef);
     auto grid = [&](uint32_t per) { return dim3((max_blocks_per_frame + per - 1) / per, nframes); };
-    if (codec == 1 && row <= 512)
-        hipLaunchKernelGGL((k_block_decode<1, true, 256, 20480>), grid(256), dim3(256), 0, s, data, l, t, p, out, out_base, err, produced_out);
-    else if (codec == 1)
-        hipLaunchKernelGGL((k_block_decode<1, false, 64, 55296>), grid(64), dim3(64), 0, s, data, l, t, p, out, out_base, err, produced_out);
+    if (codec == EMIT_ZSTD && row <= 512)
+        hipLaunchKernelGGL((k_block_decode<EMIT_ZSTD, true, 256, 20480>), grid(256), dim3(256), 0, s, data, l, t, p, out, out_base, err, produced_out);
+    else if (codec == EMIT_ZSTD)
+        hipLaunchKernelGGL((k_block_decode<EMIT_ZSTD, false, 64, 55296>), grid(64), dim3(64), 0, s, data, l, t, p, out, out_base, err, produced_out);
     else
-        hipLaunchKernelGGL((k_block_decode<2, true, 128, 32768>), grid(128), dim3(128), 0, s, data, l, t, p, out, out_base, err, produced_out);
+        hipLaunchKernelGGL((k_block_decode<EMIT_LZ4, true, 128, 32768>), grid(128), dim3(128), 0, s, data, l, t, p, out, out_base, err, produced_out);
 }
-// compact lists (k_bitmap_decode_c): codec 1 zstd, 2 LZ4; nb = bytes of one binary map
+// compact lists (k_bitmap_decode_c); nb = bytes of one binary map
 void launch_bitmap_decode_compact(int codec, const uint8_t *data, const void *frame_lists, const uint64_t *src_base, uint32_t nframes,
                                   uint32_t max_blocks_per_frame, const void *tables, const void *predef, uint8_t *out, const uint64_t *out_base,
                                   uint64_t nb, int *err, hipStream_t s)
@@ -470,11 +470,11 @@ void launch_bitmap_decode_compact(int codec, const uint8_t *data, const void *fr
     if (!max_blocks_per_frame) return;
     const ZdFrameList *l = reinterpret_cast<const ZdFrameList *>(frame_lists);
     const ZdTables *t = reinterpret_cast<const ZdTables *>(tables), *p = reinterpret_cast<const ZdTables *>(predef);
-    if (codec == 1)
-        hipLaunchKernelGGL((k_bitmap_decode_c<1, 256, 20480>), dim3((max_blocks_per_frame + 255) / 256, nframes), dim3(256), 0, s, data, l, src_base, t, p, out,
+    if (codec == EMIT_ZSTD)
+        hipLaunchKernelGGL((k_bitmap_decode_c<EMIT_ZSTD, 256, 20480>), dim3((max_blocks_per_frame + 255) / 256, nframes), dim3(256), 0, s, data, l, src_base, t, p, out,
                            out_base, nb, err);
     else
-        hipLaunchKernelGGL((k_bitmap_decode_c<2, 128, 32768>), dim3((max_blocks_per_frame + 127) / 128, nframes), dim3(128), 0, s, data, l, src_base, t, p, out,
+        hipLaunchKernelGGL((k_bitmap_decode_c<EMIT_LZ4, 128, 32768>), dim3((max_blocks_per_frame + 127) / 128, nframes), dim3(128), 0, s, data, l, src_base, t, p, out,
                            out_base, nb, err);
 }
 // lists: nlists block lists with nblocks entries in all

@@ -319,11 +319,11 @@ inline void zm_build_model(const ZstdSample &h, ZstdModel &m, uint32_t speed_per
         }
     }
     zm_huf_codes(len, m.lit_code);
-    if (zm_huf_write_desc(len, m.lit_desc, sizeof m.lit_desc, &m.lit_desc_len)) m.valid |= 1u;
+    if (zm_huf_write_desc(len, m.lit_desc, sizeof m.lit_desc, &m.lit_desc_len)) m.valid |= ZM_LIT_CODE;
     else m.valid &= ~ZM_LITS_ONLY;
     zm_huf_lengths(h.pix, len);
     zm_huf_codes(len, m.pix_code);
-    if (zm_huf_write_desc(len, m.pix_desc, sizeof m.pix_desc, &m.pix_desc_len)) m.valid |= 2u;
+    if (zm_huf_write_desc(len, m.pix_desc, sizeof m.pix_desc, &m.pix_desc_len)) m.valid |= ZM_PIX_CODE;
     // literal-length codes 0..27 and match-length codes 0..44 are what a 512-byte block can produce; all of them stay
     // encodable (one slot each at least)
     bool need_ll[ZM_LL_SYMS], need_ml[ZM_ML_SYMS];
@@ -341,7 +341,7 @@ inline void zm_build_model(const ZstdSample &h, ZstdModel &m, uint32_t speed_per
         zm_fse_ctable(nml, ZM_ML_SYMS, ml_log, m.seq.ml_state, m.seq.ml_dnb, m.seq.ml_dfs);
         m.seq.ll_log = ll_log;
         m.seq.ml_log = ml_log;
-        if (!(m.valid & ZM_LITS_ONLY)) m.valid |= 4u;   // (literals only: no block carries sequences, and none has to leave room for their tables)
+        if (!(m.valid & ZM_LITS_ONLY)) m.valid |= ZM_SEQ_TABLES;   // (literals only: no block carries sequences, and none has to leave room for their tables)
     }
 }
 
