@@ -230,10 +230,13 @@ int rc_ctx_get_profile(rc_ctx *ctx, double sum_ms[5], uint64_t *batches);
  * when it returns RC_ERR_OUT_TOO_SMALL (dst may then be NULL with dst_cap 0: a size query).
  * Every scheme rc_scheme_on_device() reports (LZ4, zstd, blosc-lz4) is both encoded and decoded here.  Decoding covers
  * what this library writes and the stock encoders' frames of the same kind: LZ4 frames (independent or linked blocks),
- * blosc1-LZ4 chunks; zstd frames inside the device decoder's subset (rc_zstd_dec.h: single-stream Huffman or raw literals,
- * predefined / described / repeated sequence tables, repeat-offset matches) - for a zstd frame outside it (a stock
- * encoder's 4-stream literals, real offsets) rc_decompress returns RC_ERR_UNSUPPORTED before doing any work and the caller
- * uses the stock decoder (pyrecode_amd/recode_compressors.py::de_compress does).
+ * blosc1-LZ4 chunks; zstd frames inside the device decoder's subset, whoever wrote them (rc_zstd_dec.h: Raw, RLE and Compressed
+ * blocks; raw, RLE or single-stream Huffman literals; predefined / described / repeated sequence tables; repeat-offset matches
+ * behind at least one literal; 512 regenerated bytes per block with sequences, at most 1024 per Compressed block) - for a zstd
+ * frame outside it (a stock encoder's 4-stream literals, real offsets) rc_decompress returns RC_ERR_UNSUPPORTED before doing any
+ * work, and RC_ERR_CORRUPT where only the decoding lanes can see the departure (a sequence without literals, a block with
+ * sequences of another size in mid-frame) or the frame is damaged; for both codes the caller uses the stock decoder
+ * (pyrecode_amd/recode_compressors.py::de_compress does).
  * Runs on the caller's current GPU, or on `RC_DEVICE` (env) when that is set. */
 int rc_compress(uint32_t scheme, uint32_t level, const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t dst_cap,
                 uint64_t *out_n);
@@ -263,8 +266,8 @@ int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_depth, con
  *                 [nnz_prefix[i], nnz_prefix[i+1]))
  *   triplets      uint64[cap][3] out (host or device): (row, col, value) in row-major order per frame, frames in order;
  *                 may be NULL with cap 0 (a counting call)
- * Device decoders: mode 0 (stored pieces), LZ4 frames with independent blocks, zstd frames inside the subset this library
- * writes (rc_zstd_dec.h).  Anything else returns RC_ERR_UNSUPPORTED before any work is done and the caller falls back to
+ * Device decoders: mode 0 (stored pieces), LZ4 frames with independent blocks, zstd frames inside the subset rc_zstd_dec.h
+ * describes (wider than what this library writes).  Anything else returns RC_ERR_UNSUPPORTED before any work is done and the caller falls back to
  * the per-frame path with the stock decoder; a stream that is inside the subset on its face but does not decode to the frame's
  * shape (a foreign encoder's larger blocks, or damage) returns RC_ERR_CORRUPT - callers that can fall back should do so for both
  * codes and let the stock decoder judge.  RC_ERR_OUT_TOO_SMALL: nnz_prefix is valid, triplets untouched.  At reduction level 1

@@ -355,7 +355,8 @@ static int blosc_decompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64
     return RC_OK;
 }
 
-// zstd frame of the subset the device decoders cover (rc_zstd_dec.h: everything rc_compress / the ctx write): the host walks
+// zstd frame of the subset the device decoders cover (rc_zstd_dec.h: everything rc_compress / the ctx write, and any other encoder's
+// frame that keeps to the same forms): the host walks
 // the block headers and builds the tables, one lane decodes one block.  The decoded size is not in the frame: the last block
 // is decoded "up to" a block's size and reports what it produced.
 static int zstd_decompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t dst_cap, uint64_t *out_n)
