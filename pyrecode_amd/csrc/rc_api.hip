@@ -15,10 +15,16 @@ struct rc_ctx {
     uint32_t emit = rc::EMIT_RAW;
     // Per-batch scratch exists twice: batch i reduces into sets[i & 1] on `stream`; its scans / layout / assembly (small,
     // latency-bound kernels that leave most of the GPU idle) run on `pstream` and may overlap the next batch's reduce
-    // kernel (rc_ctx_set_pipelined).  `sc` is the set of the most recent batch (same geometry and threshold in both).
-    rc::Scratch sc, sets[2];
+    // kernel (rc_ctx_set_pipelined).  Geometry, threshold and fitted model are the same in both.
+    rc::Scratch sets[2];
     int cur = 0;                          // set the NEXT batch uses
     int last = 0;                         // set of the most recent batch
+    const rc::Scratch &geo() const { return sets[0]; }       // N, ntiles, nb, nb_stride, thr
+    const rc::Scratch &recent() const { return sets[last]; } // the most recent batch's status word and binary maps
+    // Every device and page-locked allocation of the ctx - scratch sets, pipe slots, staging - is on one of these lists (rc_host.h);
+    // model_mem: the modelled zstd encoder's residual-stream scratch of each set, which rc_ctx_set_source_bytes(ctx, 4) gives back.
+    DevMem dmem, model_mem[2];
+    PinMem hmem;
     hipStream_t pstream = nullptr;        // carries everything behind the reduce kernel
     hipStream_t pstream_b = nullptr;      // two chains (pipelined, level 2): the second stage of the batches on scratch set 1
     hipStream_t last_ps = nullptr;        // the stream the most recent batch's second stage went to
@@ -29,12 +35,10 @@ struct rc_ctx {
     bool thr_set = false;
     bool keep_bitmap = true;  // also store the raw binary maps when a device codec is active (rc_get_binary_map)
     uint32_t src_bytes = 2;   // bytes per source pixel: 2 (uint16 frames and dark), 1 (uint8) or 4 (uint32): rc_ctx_set_source_bytes
-    uint32_t *thr32 = nullptr;   // uint32 sources: the threshold frame (sc.thr is the uint16 one)
+    uint32_t *thr32 = nullptr;   // uint32 sources: the threshold frame (geo().thr is the uint16 one)
     uint32_t last_n = 0;
     // staging for host callers
-    uint8_t *d_frames = nullptr;  uint64_t d_frames_cap = 0;
-    uint8_t *d_out = nullptr;     uint64_t d_out_cap = 0;
-    uint8_t *d_dark = nullptr;    uint64_t d_dark_cap = 0;
+    DevBuf d_frames, d_out, d_dark;
     uint64_t *d_rec_off = nullptr;
     uint32_t *d_md = nullptr;
     void *d_ztab = nullptr;               // zstd FSE tables (EMIT_ZSTD)
@@ -70,7 +74,7 @@ struct rc_ctx {
         bool has_val = false;
         uint32_t n = 0;
         bool zero_copy = false;
-        int state = 0;   // 0 free, 1 submitted, 2 result taken, 3 fetching
+        enum State { FREE, SUBMITTED, RESULT_TAKEN, FETCHING } state = FREE;
     } pipe[RC_PIPE_SLOTS];
     hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
     uint32_t val_gap = 0, val_x0 = 0, val_y0 = 0, val_w = 0, val_h = 0;   // rc_ctx_set_validation
@@ -116,41 +120,42 @@ RC_EXPORT int rc_scheme_on_device(uint32_t scheme)
 }
 
 // ---- seam 1 --------------------------------------------------------------------------------------------------
-static int alloc_set(rc_ctx *c, rc::Scratch &sc)
+static int alloc_set(rc_ctx *c, rc::Scratch &sc, DevMem &model_mem)
 {
     using namespace rc;
+    DevMem &m = c->dmem;
     const uint64_t B = c->max_batch, T = sc.ntiles;
-    HIP_TRY(hipMalloc((void **)&sc.bitmap, B * sc.nb_stride + 64));  // + slack: k_gather reads whole 16-byte pieces
-    HIP_TRY(hipMalloc((void **)&sc.tile_cnt, B * T * 4));
-    HIP_TRY(hipMalloc((void **)&sc.tile_off, B * T * 4));
-    HIP_TRY(hipMalloc((void **)&sc.tile_next, B * T * 4));
-    HIP_TRY(hipMalloc((void **)&sc.frame_nnz, B * 4));
-    HIP_TRY(hipMalloc((void **)&sc.frame_cbytes, B * 4));
-    HIP_TRY(hipMalloc((void **)&sc.scan_part, B * ((T + 255) / 256) * 32));   // (a row of partials per scan segment: room for segments of 256 tiles, more rows than k_scan_seg's 4096-tile ones need)
-    HIP_TRY(hipMalloc((void **)&sc.status, sizeof(BatchStatus)));
-    if (c->level != 3) HIP_TRY(hipMalloc((void **)&sc.pix_slots, B * T * TILE_PX * 2 + 64));
+    RC_ALLOC(m, sc.bitmap, B * sc.nb_stride + 64);  // + slack: k_gather reads whole 16-byte pieces
+    RC_ALLOC(m, sc.tile_cnt, B * T * 4);
+    RC_ALLOC(m, sc.tile_off, B * T * 4);
+    RC_ALLOC(m, sc.tile_next, B * T * 4);
+    RC_ALLOC(m, sc.frame_nnz, B * 4);
+    RC_ALLOC(m, sc.frame_cbytes, B * 4);
+    RC_ALLOC(m, sc.scan_part, B * ((T + 255) / 256) * 32);   // (a row of partials per scan segment: room for segments of 256 tiles, more rows than k_scan_seg's 4096-tile ones need)
+    RC_ALLOC(m, sc.status, sizeof(BatchStatus));
+    if (c->level != 3) RC_ALLOC(m, sc.pix_slots, B * T * TILE_PX * 2 + 64);
     if (c->emit != EMIT_RAW) {
         if (c->level == 1) {   // combined slots (rc_launch.h, Scratch::comb; profiles/r04_ab_combined_slots.log)
             sc.comb = c->emit == EMIT_ZSTD ? COMB_AT_BLK_SLOT : COMB_BEHIND_BLOCK;
             sc.blk_stride = 1536;                                  // 12 lines: the block image (<= 5) + 7 or more lines of residuals
         }
-        HIP_TRY(hipMalloc((void **)&sc.blk_slots, B * T * (uint64_t)sc.blk_stride + 256));
-        HIP_TRY(hipMalloc((void **)&sc.blk_size, B * T * 4));
-        HIP_TRY(hipMalloc((void **)&sc.blk_off, B * T * 4));
+        RC_ALLOC(m, sc.blk_slots, B * T * (uint64_t)sc.blk_stride + 256);
+        RC_ALLOC(m, sc.blk_size, B * T * 4);
+        RC_ALLOC(m, sc.blk_off, B * T * 4);
         if (c->emit == EMIT_DEFLATE) {   // the zlib streams' Adler-32: per-tile partials of the map, per-frame sums (rc_deflate_block.h, k_gather)
-            HIP_TRY(hipMalloc((void **)&sc.blk_aux, B * T * 4));
-            HIP_TRY(hipMalloc((void **)&sc.zl_acc, B * 32));
+            RC_ALLOC(m, sc.blk_aux, B * T * 4);
+            RC_ALLOC(m, sc.zl_acc, B * 32);
             HIP_TRY(hipMemset(sc.zl_acc, 0, B * 32));
         }
     }
     if (c->emit == EMIT_ZSTD && c->clevel != 0 && c->level == 1) {   // modelled zstd: Huffman stage of the residual stream
         sc.pixraw_stride = ((sc.N * 2 + 15) & ~15ull) + 32;
         sc.nchunk_max = (uint32_t)((sc.N * 2 + PIX_CHUNK - 1) / PIX_CHUNK) + 1;
-        HIP_TRY(hipMalloc((void **)&sc.pixraw, B * sc.pixraw_stride + 64));
-        HIP_TRY(hipMalloc((void **)&sc.pix_chunks, B * (uint64_t)sc.nchunk_max * PIX_SLOT + 64));
-        HIP_TRY(hipMalloc((void **)&sc.chunk_size, B * (uint64_t)sc.nchunk_max * 4));
-        HIP_TRY(hipMalloc((void **)&sc.chunk_off, B * (uint64_t)sc.nchunk_max * 4));
-        HIP_TRY(hipMalloc((void **)&sc.frame_pbytes, B * 4));
+        RC_ALLOC(model_mem, sc.pixraw, B * sc.pixraw_stride + 64);
+        RC_ALLOC(model_mem, sc.pix_chunks, B * (uint64_t)sc.nchunk_max * PIX_SLOT + 64);
+        RC_ALLOC(model_mem, sc.chunk_size, B * (uint64_t)sc.nchunk_max * 4);
+        RC_ALLOC(model_mem, sc.chunk_off, B * (uint64_t)sc.nchunk_max * 4);
+        RC_ALLOC(model_mem, sc.frame_pbytes, B * 4);
         HIP_TRY(hipMemset(sc.frame_pbytes, 0, B * 4));
     }
     HIP_TRY(hipMemset(sc.frame_nnz, 0, B * 4));
@@ -180,15 +185,15 @@ static int ctx_alloc(rc_ctx *c)
     }
     c->last_ps = c->pstream;
     c->stream = c->own_stream;
-    HIP_TRY(hipMalloc((void **)&c->sc.thr, c->sc.N * 2));
-    HIP_TRY(hipMalloc((void **)&c->d_first_err, sizeof(BatchStatus)));
+    DevMem &m = c->dmem;
+    int r;
+    RC_ALLOC(m, c->sets[0].thr, c->geo().N * 2);
+    RC_ALLOC(m, c->d_first_err, sizeof(BatchStatus));
     HIP_TRY(hipMemset(c->d_first_err, 0, sizeof(BatchStatus)));
-    c->sc.first_err = c->d_first_err;
-    for (Scratch &set : c->sets) {
-        set = c->sc;  // geometry + the shared threshold
-        int r = alloc_set(c, set);
-        if (r != RC_OK) return r;
-    }
+    c->sets[0].first_err = c->d_first_err;
+    c->sets[1] = c->sets[0];  // geometry + the shared threshold
+    for (int k = 0; k < 2; ++k)
+        if ((r = alloc_set(c, c->sets[k], c->model_mem[k])) != RC_OK) return r;
     // Two chains (level 2): the second stage of a level-2 batch - directory, links, statistics, emit, then the level-1 stages - is a chain of
     // latency-bound kernels about as long as the reduce kernel itself; on ONE stream it paces the batches (step 0.70 ms against a reduce kernel
     // of 0.58).  The batches on scratch set 1 take a second stream and a second workspace (nodes + directory), so two consecutive
@@ -200,34 +205,30 @@ static int ctx_alloc(rc_ctx *c)
         // which only the entries of set pixels with neighbours are ever touched), at rest - zero - between batches, and the directory of
         // rank bases (2 bytes per 64 pixels) - sized by the geometry, so no batch can exceed it.  One workspace per chain: a ctx that is
         // never pipelined has one chain and one workspace.
-        const uint64_t ids = (uint64_t)c->sc.ntiles * rc::TILE_PX;
-        HIP_TRY(hipMalloc((void **)&c->d_l2_node[0], B * ids * 8));
+        const uint64_t ids = (uint64_t)c->geo().ntiles * rc::TILE_PX;
+        RC_ALLOC(m, c->d_l2_node[0], B * ids * 8);
         HIP_TRY(hipMemset(c->d_l2_node[0], 0, B * ids * 8));
-        HIP_TRY(hipMalloc((void **)&c->d_l2_base[0], B * (uint64_t)c->sc.ntiles * 64 * 2));   // (written by k_l2_dir before anything reads it)
+        RC_ALLOC(m, c->d_l2_base[0], B * (uint64_t)c->geo().ntiles * 64 * 2);   // (written by k_l2_dir before anything reads it)
         for (int i = 0; i < 2; ++i) {
             Scratch &set = c->sets[i];
             set.l2_node = c->d_l2_node[0]; set.l2_ids_per_frame = ids; set.l2_base = c->d_l2_base[0];
         }
     }
-    c->sc = c->sets[0];
     if (c->emit == EMIT_ZSTD) {
-        std::vector<uint8_t> tab(zstd_tables_bytes());
-        zstd_tables_host(tab.data());
-        HIP_TRY(hipMalloc(&c->d_ztab, tab.size()));
-        HIP_TRY(hipMemcpy(c->d_ztab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+        if ((r = zstd_encoder_tables(m, c->d_ztab)) != RC_OK) return r;
         // compression_level 0 = the fast encoder (raw literals, predefined tables, stored residuals); any other level = the
         // modelled one.  (The reference hands the level to libzstd, recode_writer.py:175-178; the device encoders have these two.)
         c->modelled = c->clevel != 0;
         if (c->modelled) {
-            HIP_TRY(hipMalloc((void **)&c->d_model, sizeof(ZstdModel)));
-            HIP_TRY(hipMalloc((void **)&c->d_sample, sizeof(ZstdSample)));
-            HIP_TRY(hipHostMalloc((void **)&c->h_model, sizeof(ZstdModel), hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc((void **)&c->h_sample, sizeof(ZstdSample), hipHostMallocDefault));
+            RC_ALLOC(m, c->d_model, sizeof(ZstdModel));
+            RC_ALLOC(m, c->d_sample, sizeof(ZstdSample));
+            RC_ALLOC(c->hmem, c->h_model, sizeof(ZstdModel));
+            RC_ALLOC(c->hmem, c->h_sample, sizeof(ZstdSample));
         }
     }
-    HIP_TRY(hipMalloc((void **)&c->d_rec_off, (B + 1) * 8));
-    HIP_TRY(hipMalloc((void **)&c->d_md, B * 3 * 4));
-    HIP_TRY(hipHostMalloc((void **)&c->h_status, 2 * sizeof(BatchStatus), hipHostMallocDefault));
+    RC_ALLOC(m, c->d_rec_off, (B + 1) * 8);
+    RC_ALLOC(m, c->d_md, B * 3 * 4);
+    RC_ALLOC(c->hmem, c->h_status, 2 * sizeof(BatchStatus));
     for (auto &e : c->ev) HIP_TRY(hipEventCreate(&e));
     for (auto &e : c->ev_red) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto &e : c->ev_post) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -285,7 +286,7 @@ RC_EXPORT rc_ctx *rc_ctx_create(uint32_t nx, uint32_t ny, uint32_t src_bit_depth
     c->nx = nx; c->ny = ny; c->depth = src_bit_depth; c->level = reduction_level; c->op_mode = op_mode;
     c->scheme = scheme; c->clevel = clevel; c->max_batch = max_batch;
     c->emit = (op_mode == 1 && rc_scheme_on_device(scheme)) ? scheme : rc::EMIT_RAW;
-    rc::Scratch &sc = c->sc;
+    rc::Scratch &sc = c->sets[0];   // (ctx_alloc copies the geometry to the other set)
     sc.N = (uint64_t)nx * ny;
     sc.ntiles = (uint32_t)((sc.N + rc::TILE_PX - 1) / rc::TILE_PX);
     sc.nb = (sc.N + 7) / 8;
@@ -308,43 +309,21 @@ RC_EXPORT int rc_ctx_destroy(rc_ctx *c)
     if (!c) return RC_OK;
     DeviceGuard dev_guard_;
     (void)dev_guard_.enter(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->pstream) (void)hipStreamSynchronize(c->pstream);
-    if (c->pstream_b) (void)hipStreamSynchronize(c->pstream_b);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    for (rc::Scratch &sc : c->sets) {
-        void *per_set[] = {sc.bitmap, sc.pix_slots, sc.tile_cnt, sc.tile_off, sc.tile_next, sc.blk_slots, sc.blk_size, sc.blk_aux, sc.zl_acc,
-                           sc.blk_off, sc.frame_nnz, sc.frame_cbytes, sc.scan_part, sc.status, sc.pixraw, sc.pix_chunks, sc.chunk_size, 
-                           sc.chunk_off, sc.frame_pbytes};
-        for (void *b : per_set)
-            if (b) (void)hipFree(b);
-    }
-    for (auto &p : c->pipe) {
-        void *dev[] = {p.d_in, p.d_out, p.d_rec, p.d_md, p.d_val};
-        for (void *b : dev) if (b) (void)hipFree(b);
-        void *host[] = {p.h_rec, p.h_md, p.h_stat, p.h_val};
-        for (void *b : host) if (b) (void)hipHostFree(b);
-        hipEvent_t evs[] = {p.ev_h2d, p.ev_done, p.ev_fetch, p.ev_val};
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    }
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    if (c->d2h_stream) { (void)hipStreamSynchronize(c->d2h_stream); (void)hipStreamDestroy(c->d2h_stream); }
-    if (c->h_model) (void)hipHostFree(c->h_model);
-    if (c->h_sample) (void)hipHostFree(c->h_sample);
-    void *bufs[] = {c->sc.thr, c->thr32, c->d_first_err, c->d_frames, c->d_out, c->d_dark, c->d_rec_off,
-                    c->d_md, c->d_ztab, c->d_model, c->d_sample, c->d_l2_node[0], c->d_l2_node[1], c->d_l2_base[0], c->d_l2_base[1]};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    hipEvent_t sync_ev[] = {c->ev_red[0], c->ev_red[1], c->ev_post[0], c->ev_post[1], c->ev_in[0], c->ev_in[1]};
-    for (hipEvent_t e : sync_ev)
+    for (hipStream_t st : {c->stream, c->pstream, c->pstream_b, c->own_stream, c->copy_stream, c->d2h_stream})
+        if (st) (void)hipStreamSynchronize(st);
+    c->dmem.release_all();
+    for (DevMem &m : c->model_mem) m.release_all();
+    c->hmem.release_all();
+    for (auto &p : c->pipe)
+        for (hipEvent_t e : {p.ev_h2d, p.ev_done, p.ev_fetch, p.ev_val})
+            if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_red[0], c->ev_red[1], c->ev_post[0], c->ev_post[1], c->ev_in[0], c->ev_in[1]})
         if (e) (void)hipEventDestroy(e);
-    if (c->pstream) (void)hipStreamDestroy(c->pstream);
-    if (c->pstream_b) (void)hipStreamDestroy(c->pstream_b);
-    if (c->h_status) (void)hipHostFree(c->h_status);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->prof_ev) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    for (hipStream_t st : {c->copy_stream, c->d2h_stream, c->pstream, c->pstream_b, c->own_stream})
+        if (st) (void)hipStreamDestroy(st);
     delete c;
     return RC_OK;
 }
@@ -362,7 +341,7 @@ RC_EXPORT int rc_set_threshold(rc_ctx *c, const void *thr)
     if (c->depth > 16 && c->src_bytes != 4) return fail(RC_ERR_BAD_ARG, "src_bit_depth > 16 means uint32 sources: rc_ctx_set_source_bytes(ctx, 4) first");
     RC_ON_DEVICE(c->device);
     // (uint16 thresholds for uint16 AND uint8 sources - the device keeps them as uint16 -, uint32 ones for uint32 sources)
-    HIP_TRY(hipMemcpyAsync(c->src_bytes == 4 ? (void *)c->thr32 : (void *)c->sc.thr, thr, c->sc.N * (c->src_bytes == 4 ? 4 : 2),
+    HIP_TRY(hipMemcpyAsync(c->src_bytes == 4 ? (void *)c->thr32 : (void *)c->geo().thr, thr, c->geo().N * (c->src_bytes == 4 ? 4 : 2),
                            is_device_ptr(thr) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -375,16 +354,16 @@ RC_EXPORT int rc_set_dark(rc_ctx *c, const void *dark, int64_t epsilon)
     if (!c || !dark) return fail(RC_ERR_BAD_ARG, "ctx / dark is NULL");
     RC_ON_DEVICE(c->device);
     const void *src = dark;
-    const uint64_t bytes = c->sc.N * c->src_bytes;
+    const uint64_t bytes = c->geo().N * c->src_bytes;
     if (!is_device_ptr(dark)) {
-        int r = ensure(c->d_dark, c->d_dark_cap, bytes);
+        int r = c->d_dark.ensure(c->dmem, bytes);
         if (r != RC_OK) return r;
-        HIP_TRY(hipMemcpyAsync(c->d_dark, dark, bytes, hipMemcpyHostToDevice, c->stream));
-        src = c->d_dark;
+        HIP_TRY(hipMemcpyAsync(c->d_dark.p, dark, bytes, hipMemcpyHostToDevice, c->stream));
+        src = c->d_dark.p;
     }
     if (c->depth > 16 && c->src_bytes != 4) return fail(RC_ERR_BAD_ARG, "src_bit_depth > 16 means uint32 sources: rc_ctx_set_source_bytes(ctx, 4) first");
-    if (c->src_bytes == 4) rc::launch_threshold32(static_cast<const uint32_t *>(src), epsilon, c->sc.N, c->thr32, c->stream);
-    else rc::launch_threshold(src, epsilon, c->sc.N, c->sc.thr, c->stream, c->src_bytes);
+    if (c->src_bytes == 4) rc::launch_threshold32(static_cast<const uint32_t *>(src), epsilon, c->geo().N, c->thr32, c->stream);
+    else rc::launch_threshold(src, epsilon, c->geo().N, c->geo().thr, c->stream, c->src_bytes);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->thr_set = true;
@@ -400,7 +379,7 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
     if (bytes_per_pixel == 1 && c->depth > 8) return fail(RC_ERR_BAD_ARG, "rc_ctx_set_source_bytes: uint8 sources need src_bit_depth <= 8");
     if (bytes_per_pixel == 2 && c->depth > 16) return fail(RC_ERR_BAD_ARG, "rc_ctx_set_source_bytes: uint16 sources need src_bit_depth <= 16");
     if (c->batch_seq || c->thr_set) return fail(RC_ERR_BAD_ARG, "rc_ctx_set_source_bytes: call before rc_set_dark / rc_set_threshold and the first batch");
-    if (c->sc.N * bytes_per_pixel >= (1ull << 32))
+    if (c->geo().N * bytes_per_pixel >= (1ull << 32))
         return fail(RC_ERR_UNSUPPORTED, "rc_ctx_set_source_bytes: a raw frame of 4 GiB or more (nx*ny*bytes_per_pixel >= 2^32) does not fit the format's u32 size fields");
     if (bytes_per_pixel == 4) {
         // uint32 sources (source_bit_depth > 16, misc.py:41-49): rc_reduce32.hip.  Levels 1 and 3; the residual fields are depth bits wide, or
@@ -414,13 +393,13 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
         // allocation leaves the uint16 ctx as it was).
         uint32_t *thr32 = nullptr;
         uint16_t *slots[2] = {nullptr, nullptr};
-        bool ok = hipMalloc((void **)&thr32, c->sc.N * 4) == hipSuccess;
+        bool ok = c->dmem.try_alloc(thr32, c->geo().N * 4) == hipSuccess;
         for (int k = 0; ok && k < 2 && c->level != 3; ++k)
-            ok = hipMalloc((void **)&slots[k], (uint64_t)c->max_batch * c->sets[k].ntiles * rc::TILE_PX * 4 + 64) == hipSuccess;
+            ok = c->dmem.try_alloc(slots[k], (uint64_t)c->max_batch * c->geo().ntiles * rc::TILE_PX * 4 + 64) == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
-            if (thr32) (void)hipFree(thr32);
-            for (uint16_t *p : slots) if (p) (void)hipFree(p);
+            c->dmem.free_one(thr32);
+            for (uint16_t *&p : slots) c->dmem.free_one(p);
             return fail(RC_ERR_DEVICE, "rc_ctx_set_source_bytes: out of device memory for the uint32 threshold / residual slots");
         }
         if (c->depth % 8 == 0) c->depth = 32;
@@ -431,22 +410,21 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
             set->pix_slot_bytes = rc::TILE_PX * 4;
             set->comb = rc::COMB_OFF;
             if (c->level != 3) {
-                (void)hipFree(set->pix_slots);
+                c->dmem.free_one(set->pix_slots);
                 set->pix_slots = slots[k];
             }
             // the modelled zstd encoder's residual-stream scratch (alloc_set sized it for uint16 sources): not used by this path
-            void **unused[] = {(void **)&set->pixraw, (void **)&set->pix_chunks, (void **)&set->chunk_size, (void **)&set->chunk_off, (void **)&set->frame_pbytes};
-            for (void **q : unused) { if (*q) (void)hipFree(*q); *q = nullptr; }
+            c->model_mem[k].release_all();
+            set->pixraw = nullptr; set->pix_chunks = nullptr; set->chunk_size = nullptr; set->chunk_off = nullptr; set->frame_pbytes = nullptr;
             set->pixraw_stride = 0; set->nchunk_max = 0;
         }
-        c->sc = c->sets[0];
     }
     c->src_bytes = bytes_per_pixel;
     return RC_OK;
 }
 RC_EXPORT uint32_t rc_ctx_source_bytes(const rc_ctx *c) { return c ? c->src_bytes : 0; }
 
-RC_EXPORT uint64_t rc_out_capacity(const rc_ctx *c, uint32_t n) { return c ? (uint64_t)n * c->sc.N * c->src_bytes : 0; }
+RC_EXPORT uint64_t rc_out_capacity(const rc_ctx *c, uint32_t n) { return c ? (uint64_t)n * c->geo().N * c->src_bytes : 0; }
 
 RC_EXPORT uint32_t rc_md_fields(const rc_ctx *c)
 {
@@ -486,12 +464,12 @@ static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
     HIP_TRY(hipMemcpyAsync(c->d_model, c->h_model, sizeof(ZstdModel), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     const ZstdModel &M = *c->h_model;
-    for (Scratch *set : {&c->sets[0], &c->sets[1], &c->sc}) {
-        set->zm_model = c->d_model;
-        set->zm_lit_code = c->d_model->lit_code;
-        set->zm_valid = M.valid;
-        set->zm_budget = zm_block_budget(M, BLK_SLOT);
-        set->zm_seq_bits = (M.valid & ZM_SEQ_TABLES) ? M.seq.ll_log + M.seq.ml_log : 12u;
+    for (Scratch &set : c->sets) {
+        set.zm_model = c->d_model;
+        set.zm_lit_code = c->d_model->lit_code;
+        set.zm_valid = M.valid;
+        set.zm_budget = zm_block_budget(M, BLK_SLOT);
+        set.zm_seq_bits = (M.valid & ZM_SEQ_TABLES) ? M.seq.ll_log + M.seq.ml_log : 12u;
     }
     c->model_ready = true;
     return RC_OK;
@@ -524,7 +502,7 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     rp.level = c->level == 3 ? 3u : 1u;  // level 2 records are framed exactly like level 1 (statistics in place of residuals)
     rp.emit = c->emit; rp.depth = c->depth; rp.first_frame_id = first_frame_id;
     rp.packed_slots = 1u;   // (level 2: k_l2_emit leaves its statistics as tile-local packed streams, like level-1 residuals)
-    rp.frame_bytes = c->sc.N * c->src_bytes;   // a record may not exceed the raw frame (recode_writer.py:565-566)
+    rp.frame_bytes = c->geo().N * c->src_bytes;   // a record may not exceed the raw frame (recode_writer.py:565-566)
     hipEvent_t *ev = nullptr;
     if (timed) ev = c->ev;
     else if (c->profiling && (c->prof_phase++ % c->prof_every) == 0) {
@@ -545,7 +523,6 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     const int k = c->cur;
     c->cur ^= 1;
     c->last = k;
-    c->sc = c->sets[k];
     const rc::Scratch &sc = c->sets[k];
     // (two chains: consecutive batches' second stages on two streams - they overlap each other as well as the reduce kernels)
     const bool two = c->pipelined && c->two_chains;
@@ -641,21 +618,19 @@ RC_EXPORT int rc_reduce_compress_batch_async(rc_ctx *c, const void *frames_dev, 
 static void l2_second_chain(rc_ctx *c)
 {
     if (c->level != 2 || c->two_chains) return;
-    const uint64_t B = c->max_batch, ids = (uint64_t)c->sc.ntiles * rc::TILE_PX;
+    const uint64_t B = c->max_batch, ids = (uint64_t)c->geo().ntiles * rc::TILE_PX;
     if (!c->d_l2_node[1]) {
-        bool ok = hipMalloc((void **)&c->d_l2_node[1], B * ids * 8) == hipSuccess && hipMemset(c->d_l2_node[1], 0, B * ids * 8) == hipSuccess &&
-                  hipMalloc((void **)&c->d_l2_base[1], B * (uint64_t)c->sc.ntiles * 64 * 2) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        bool ok = c->dmem.try_alloc(c->d_l2_node[1], B * ids * 8) == hipSuccess && hipMemset(c->d_l2_node[1], 0, B * ids * 8) == hipSuccess &&
+                  c->dmem.try_alloc(c->d_l2_base[1], B * (uint64_t)c->geo().ntiles * 64 * 2) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
-            if (c->d_l2_node[1]) (void)hipFree(c->d_l2_node[1]);
-            if (c->d_l2_base[1]) (void)hipFree(c->d_l2_base[1]);
-            c->d_l2_node[1] = nullptr; c->d_l2_base[1] = nullptr;
+            c->dmem.free_one(c->d_l2_node[1]);
+            c->dmem.free_one(c->d_l2_base[1]);
             return;
         }
     }
     c->sets[1].l2_node = c->d_l2_node[1];
     c->sets[1].l2_base = c->d_l2_base[1];
-    if (c->last == 1) c->sc = c->sets[1];
     c->two_chains = true;
 }
 
@@ -683,7 +658,7 @@ RC_EXPORT int rc_ctx_sync(rc_ctx *c)
     if (!c) return fail(RC_ERR_BAD_ARG, "ctx is NULL");
     RC_ON_DEVICE(c->device);
     HIP_TRY(hipStreamSynchronize(c->pstream_b));
-    HIP_TRY(hipMemcpyAsync(&c->h_status[0], c->sc.status, sizeof(rc::BatchStatus), hipMemcpyDeviceToHost, c->pstream));
+    HIP_TRY(hipMemcpyAsync(&c->h_status[0], c->recent().status, sizeof(rc::BatchStatus), hipMemcpyDeviceToHost, c->pstream));
     HIP_TRY(hipMemcpyAsync(&c->h_status[1], c->d_first_err, sizeof(rc::BatchStatus), hipMemcpyDeviceToHost, c->pstream));
     HIP_TRY(hipMemsetAsync(c->d_first_err, 0, sizeof(rc::BatchStatus), c->pstream));
     HIP_TRY(hipStreamSynchronize(c->pstream));
@@ -720,13 +695,13 @@ RC_EXPORT int rc_reduce_compress_batch(rc_ctx *c, const void *frames, uint32_t n
     int r = check_batch_args(c, frames, n, out, rec_offsets, md);
     if (r != RC_OK) return r;
     RC_ON_DEVICE(c->device);
-    const uint64_t frame_bytes = c->sc.N * c->src_bytes;
+    const uint64_t frame_bytes = c->geo().N * c->src_bytes;
     const void *fdev = frames;
     if (!is_device_ptr(frames)) {
-        r = ensure(c->d_frames, c->d_frames_cap, (uint64_t)n * frame_bytes);
+        r = c->d_frames.ensure(c->dmem, (uint64_t)n * frame_bytes);
         if (r != RC_OK) return r;
-        HIP_TRY(hipMemcpyAsync(c->d_frames, frames, (uint64_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream));
-        fdev = c->d_frames;
+        HIP_TRY(hipMemcpyAsync(c->d_frames.p, frames, (uint64_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream));
+        fdev = c->d_frames.p;
     }
     uint8_t *odev = out;
     uint64_t cap = out_cap;
@@ -734,9 +709,9 @@ RC_EXPORT int rc_reduce_compress_batch(rc_ctx *c, const void *frames, uint32_t n
     if (out_host) {
         const uint64_t worst = (uint64_t)n * frame_bytes;
         cap = out_cap < worst ? out_cap : worst;
-        r = ensure(c->d_out, c->d_out_cap, cap);
+        r = c->d_out.ensure(c->dmem, cap);
         if (r != RC_OK) return r;
-        odev = c->d_out;
+        odev = c->d_out.p;
     }
     r = enqueue_batch(c, fdev, n, first_frame_id, odev, cap, c->d_rec_off, c->d_md, true);
     if (r != RC_OK) return r;
@@ -746,7 +721,7 @@ RC_EXPORT int rc_reduce_compress_batch(rc_ctx *c, const void *frames, uint32_t n
     if (r != RC_OK) return r;
     int r2 = copy_out(rec_offsets, c->d_rec_off, (uint64_t)(n + 1) * 8, c->stream);
     if (r2 == RC_OK) r2 = copy_out(md, c->d_md, (uint64_t)n * 12, c->stream);
-    if (r2 == RC_OK && out_host) r2 = copy_out(out, c->d_out, c->h_status->total, c->stream);
+    if (r2 == RC_OK && out_host) r2 = copy_out(out, c->d_out.p, c->h_status->total, c->stream);
     if (r2 != RC_OK) return r2;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RC_OK;
@@ -785,19 +760,19 @@ static int pipe_slot_init(rc_ctx *c, rc_ctx::PipeSlot &p)
     const uint64_t B = c->max_batch;
     if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!c->d2h_stream) HIP_TRY(hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void **)&p.d_in, B * c->sc.N * c->src_bytes + 64));
-    HIP_TRY(hipMalloc((void **)&p.d_out, rc_out_capacity(c, (uint32_t)B) + 64));
-    HIP_TRY(hipMalloc((void **)&p.d_rec, (B + 1) * 8));
-    HIP_TRY(hipMalloc((void **)&p.d_md, B * 12));
-    HIP_TRY(hipHostMalloc((void **)&p.h_rec, (B + 1) * 8, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&p.h_md, B * 12, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&p.h_stat, sizeof(rc::BatchStatus), hipHostMallocDefault));
+    RC_ALLOC(c->dmem, p.d_in, B * c->geo().N * c->src_bytes + 64);
+    RC_ALLOC(c->dmem, p.d_out, rc_out_capacity(c, (uint32_t)B) + 64);
+    RC_ALLOC(c->dmem, p.d_rec, (B + 1) * 8);
+    RC_ALLOC(c->dmem, p.d_md, B * 12);
+    RC_ALLOC(c->hmem, p.h_rec, (B + 1) * 8);
+    RC_ALLOC(c->hmem, p.h_md, B * 12);
+    RC_ALLOC(c->hmem, p.h_stat, sizeof(rc::BatchStatus));
     HIP_TRY(hipEventCreateWithFlags(&p.ev_h2d, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&p.ev_done, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&p.ev_fetch, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&p.ev_val, hipEventDisableTiming));
-    HIP_TRY(hipMalloc((void **)&p.d_val, B * 4 + 64));
-    HIP_TRY(hipHostMalloc((void **)&p.h_val, B * 4 + 64, hipHostMallocDefault));
+    RC_ALLOC(c->dmem, p.d_val, B * 4 + 64);
+    RC_ALLOC(c->hmem, p.h_val, B * 4 + 64);
     return RC_OK;
 }
 
@@ -814,7 +789,7 @@ RC_EXPORT int rc_pipe_validation(rc_ctx *c, uint32_t slot, uint32_t *counts)
 {
     if (!c || slot >= RC_PIPE_SLOTS || !counts) return fail(RC_ERR_BAD_ARG, "NULL argument / slot out of range");
     rc_ctx::PipeSlot &p = c->pipe[slot];
-    if (p.state != 1 && p.state != 2) return fail(RC_ERR_BAD_ARG, "nothing submitted on this slot");
+    if (p.state != p.SUBMITTED && p.state != p.RESULT_TAKEN) return fail(RC_ERR_BAD_ARG, "nothing submitted on this slot");
     if (!p.has_val) { for (uint32_t i = 0; i < p.n; ++i) counts[i] = 0xFFFFFFFFu; return RC_OK; }
     HIP_TRY(hipEventSynchronize(p.ev_val));
     memcpy(counts, p.h_val, (uint64_t)p.n * 4);
@@ -828,7 +803,7 @@ RC_EXPORT int rc_pipe_submit(rc_ctx *c, uint32_t slot, const void *frames_host, 
     if (!c->thr_set) return fail(RC_ERR_BAD_ARG, "threshold not set (rc_set_threshold / rc_set_dark)");
     RC_ON_DEVICE(c->device);
     rc_ctx::PipeSlot &p = c->pipe[slot];
-    if (p.state != 0) return fail(RC_ERR_BAD_ARG, "slot is still in use (result / fetch_wait not called)");
+    if (p.state != p.FREE) return fail(RC_ERR_BAD_ARG, "slot is still in use (result / fetch_wait not called)");
     if (!p.d_in) {
         int r = pipe_slot_init(c, p);
         if (r != RC_OK) return r;
@@ -849,7 +824,7 @@ RC_EXPORT int rc_pipe_submit(rc_ctx *c, uint32_t slot, const void *frames_host, 
     } else (void)hipGetLastError();
     p.zero_copy = fdev != nullptr;
     if (!fdev) {
-        HIP_TRY(hipMemcpyAsync(p.d_in, frames_host, (uint64_t)n * c->sc.N * c->src_bytes, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(hipMemcpyAsync(p.d_in, frames_host, (uint64_t)n * c->geo().N * c->src_bytes, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(hipEventRecord(p.ev_h2d, c->copy_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, p.ev_h2d, 0));
         fdev = p.d_in;
@@ -858,7 +833,7 @@ RC_EXPORT int rc_pipe_submit(rc_ctx *c, uint32_t slot, const void *frames_host, 
     if (r != RC_OK) return r;
     p.has_val = c->val_gap != 0;
     if (p.has_val) {   // validation frames of this batch: the dose-rate count, from the frames the reduce kernel has just read
-        rc::launch_roi_components(fdev, c->src_bytes == 4 ? (const void *)c->thr32 : (const void *)c->sc.thr, c->sc.N, c->nx, n, first_frame_id, c->val_gap, c->val_x0, c->val_y0, c->val_w, c->val_h, p.d_val, c->stream, c->src_bytes);
+        rc::launch_roi_components(fdev, c->src_bytes == 4 ? (const void *)c->thr32 : (const void *)c->geo().thr, c->geo().N, c->nx, n, first_frame_id, c->val_gap, c->val_x0, c->val_y0, c->val_w, c->val_h, p.d_val, c->stream, c->src_bytes);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(p.h_val, p.d_val, (uint64_t)n * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipEventRecord(p.ev_val, c->stream));
@@ -867,17 +842,17 @@ RC_EXPORT int rc_pipe_submit(rc_ctx *c, uint32_t slot, const void *frames_host, 
     hipStream_t ps = c->last_ps;   // carries the batch's assembly: the metadata follows it
     HIP_TRY(hipMemcpyAsync(p.h_rec, p.d_rec, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, ps));
     HIP_TRY(hipMemcpyAsync(p.h_md, p.d_md, (uint64_t)n * 12, hipMemcpyDeviceToHost, ps));
-    HIP_TRY(hipMemcpyAsync(p.h_stat, c->sc.status, sizeof(rc::BatchStatus), hipMemcpyDeviceToHost, ps));
+    HIP_TRY(hipMemcpyAsync(p.h_stat, c->recent().status, sizeof(rc::BatchStatus), hipMemcpyDeviceToHost, ps));
     HIP_TRY(hipEventRecord(p.ev_done, ps));
     p.n = n;
-    p.state = 1;
+    p.state = p.SUBMITTED;
     return RC_OK;
 }
 
 RC_EXPORT int rc_pipe_input_done(rc_ctx *c, uint32_t slot)
 {
     if (!c || slot >= RC_PIPE_SLOTS) return fail(RC_ERR_BAD_ARG, "NULL argument / slot out of range");
-    if (c->pipe[slot].state == 0) return RC_OK;
+    if (c->pipe[slot].state == rc_ctx::PipeSlot::FREE) return RC_OK;
     HIP_TRY(hipEventSynchronize(c->pipe[slot].ev_h2d));
     return RC_OK;
 }
@@ -886,13 +861,13 @@ RC_EXPORT int rc_pipe_result(rc_ctx *c, uint32_t slot, uint64_t *rec_offsets, ui
 {
     if (!c || slot >= RC_PIPE_SLOTS || !rec_offsets || !md || !total) return fail(RC_ERR_BAD_ARG, "NULL argument / slot out of range");
     rc_ctx::PipeSlot &p = c->pipe[slot];
-    if (p.state != 1) return fail(RC_ERR_BAD_ARG, "nothing submitted on this slot");
+    if (p.state != p.SUBMITTED) return fail(RC_ERR_BAD_ARG, "nothing submitted on this slot");
     HIP_TRY(hipEventSynchronize(p.ev_done));
-    p.state = 2;
+    p.state = p.RESULT_TAKEN;
     if (p.h_stat->code != 0) {
         char msg[128];
         snprintf(msg, sizeof msg, "%s (frame %u of the batch)", rc_strerror(p.h_stat->code), p.h_stat->frame);
-        p.state = 0;
+        p.state = p.FREE;
         return fail(p.h_stat->code, msg);
     }
     memcpy(rec_offsets, p.h_rec, (uint64_t)(p.n + 1) * 8);
@@ -905,12 +880,12 @@ RC_EXPORT int rc_pipe_fetch(rc_ctx *c, uint32_t slot, uint8_t *dst_host, uint64_
 {
     if (!c || slot >= RC_PIPE_SLOTS || (!dst_host && bytes)) return fail(RC_ERR_BAD_ARG, "NULL argument / slot out of range");
     rc_ctx::PipeSlot &p = c->pipe[slot];
-    if (p.state != 2) return fail(RC_ERR_BAD_ARG, "rc_pipe_result has not been called for this slot");
+    if (p.state != p.RESULT_TAKEN) return fail(RC_ERR_BAD_ARG, "rc_pipe_result has not been called for this slot");
     if (bytes > p.h_stat->total) return fail(RC_ERR_BAD_ARG, "more bytes than the batch's records hold");
     RC_ON_DEVICE(c->device);
     if (bytes) HIP_TRY(hipMemcpyAsync(dst_host, p.d_out, bytes, hipMemcpyDeviceToHost, c->d2h_stream));
     HIP_TRY(hipEventRecord(p.ev_fetch, c->d2h_stream));
-    p.state = 3;
+    p.state = p.FETCHING;
     return RC_OK;
 }
 
@@ -918,10 +893,10 @@ RC_EXPORT int rc_pipe_fetch_wait(rc_ctx *c, uint32_t slot)
 {
     if (!c || slot >= RC_PIPE_SLOTS) return fail(RC_ERR_BAD_ARG, "NULL argument / slot out of range");
     rc_ctx::PipeSlot &p = c->pipe[slot];
-    if (p.state == 2) { p.state = 0; return RC_OK; }   // nothing fetched: the slot is simply released
-    if (p.state != 3) return fail(RC_ERR_BAD_ARG, "rc_pipe_fetch has not been called for this slot");
+    if (p.state == p.RESULT_TAKEN) { p.state = p.FREE; return RC_OK; }   // nothing fetched: the slot is simply released
+    if (p.state != p.FETCHING) return fail(RC_ERR_BAD_ARG, "rc_pipe_fetch has not been called for this slot");
     HIP_TRY(hipEventSynchronize(p.ev_fetch));
-    p.state = 0;
+    p.state = p.FREE;
     return RC_OK;
 }
 
@@ -938,7 +913,7 @@ RC_EXPORT int rc_get_binary_map(rc_ctx *c, uint32_t i, uint8_t *bitmap_out)
     if (i >= c->last_n) return fail(RC_ERR_BAD_ARG, "frame index outside the most recent batch");
     if (!c->keep_bitmap && c->emit != rc::EMIT_RAW && c->level != 2) return fail(RC_ERR_BAD_ARG, "binary maps are not kept (rc_ctx_keep_binary_maps(ctx, 0))");
     RC_ON_DEVICE(c->device);
-    int r = copy_out(bitmap_out, c->sc.bitmap + (uint64_t)i * c->sc.nb_stride, c->sc.nb, c->stream);
+    int r = copy_out(bitmap_out, c->recent().bitmap + (uint64_t)i * c->geo().nb_stride, c->geo().nb, c->stream);
     if (r != RC_OK) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RC_OK;
@@ -998,15 +973,15 @@ RC_EXPORT int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_
     const uint64_t N = (uint64_t)nx * ny, nb = (N + 7) / 8, nb8 = (nb + 7) / 8;
     const uint32_t nblk = (uint32_t)((nb8 + rc::WG - 1) / rc::WG);
     const uint8_t *d_bm = nullptr, *d_px = nullptr;
-    r = stage_in(bitmap, nb, u.a, u.a_cap, d_bm, nb8 * 8 - nb + 8);
+    r = stage_in(bitmap, nb, u.a, d_bm, nb8 * 8 - nb + 8);
     if (r != RC_OK) return r;
     if (reduction_level == 1 && pixvals_bytes) {
-        r = stage_in(pixvals, pixvals_bytes, u.b, u.b_cap, d_px);
+        r = stage_in(pixvals, pixvals_bytes, u.b, d_px);
         if (r != RC_OK) return r;
     }
-    r = ensure(u.w, u.w_cap, (uint64_t)nblk * 8 + 16);
+    r = u.w.ensure(u.dmem, (uint64_t)nblk * 8 + 16);
     if (r != RC_OK) return r;
-    uint32_t *blk_cnt = reinterpret_cast<uint32_t *>(u.w), *blk_off = blk_cnt + nblk;
+    uint32_t *blk_cnt = u.w.as<uint32_t>(), *blk_off = blk_cnt + nblk;
     uint64_t *nnz_dev = reinterpret_cast<uint64_t *>(blk_cnt + 2 * (uint64_t)nblk);
     // pass 1: count, so the output can be bounds-checked (and sized) before anything is written
     rc::launch_expand_count(d_bm, nb8, N, blk_cnt, blk_off, nnz_dev, u.stream);
@@ -1018,17 +993,11 @@ RC_EXPORT int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_
     if (reduction_level == 1 && (nnz * bit_depth + 7) / 8 > pixvals_bytes)
         return fail(RC_ERR_CORRUPT, "pixvals shorter than popcount(bitmap) * bit_depth bits");
     if (nnz == 0) return 0;
-    uint64_t *d_out = out;
-    const bool out_host = !is_device_ptr(out);
-    if (out_host) {
-        r = ensure(u.o, u.o_cap, nnz * 24);
-        if (r != RC_OK) return r;
-        d_out = reinterpret_cast<uint64_t *>(u.o);
-    }
-    rc::launch_expand_emit(d_bm, nb8, N, nx, blk_off, d_px, pixvals_bytes, bit_depth, reduction_level, nnz, d_out, u.stream);
+    StagedOut so;
+    if ((r = so.begin(out, nnz * 24)) != RC_OK) return r;
+    rc::launch_expand_emit(d_bm, nb8, N, nx, blk_off, d_px, pixvals_bytes, bit_depth, reduction_level, nnz, so.as<uint64_t>(), u.stream);
     HIP_TRY(hipGetLastError());
-    if (out_host) HIP_TRY(hipMemcpyAsync(out, d_out, nnz * 24, hipMemcpyDeviceToHost, u.stream));
-    HIP_TRY(hipStreamSynchronize(u.stream));
+    if ((r = so.finish(out, nnz * 24)) != RC_OK) return r;
     return (int64_t)nnz;
 }
 
@@ -1043,20 +1012,13 @@ RC_EXPORT int rc_bit_pack(const uint16_t *pixvals, uint64_t n, uint32_t bit_dept
     if (r != RC_OK) return r;
     Util &u = g_util;
     const uint16_t *d_in = nullptr;
-    r = stage_in(pixvals, n * 2, u.a, u.a_cap, d_in);
+    r = stage_in(pixvals, n * 2, u.a, d_in);
     if (r != RC_OK) return r;
-    uint8_t *d_out = out;
-    const bool out_host = !is_device_ptr(out);
-    if (out_host) {
-        r = ensure(u.o, u.o_cap, out_n);
-        if (r != RC_OK) return r;
-        d_out = u.o;
-    }
-    rc::launch_bit_pack(d_in, n, bit_depth, d_out, out_n, u.stream);
+    StagedOut so;
+    if ((r = so.begin(out, out_n)) != RC_OK) return r;
+    rc::launch_bit_pack(d_in, n, bit_depth, so.as<uint8_t>(), out_n, u.stream);
     HIP_TRY(hipGetLastError());
-    if (out_host) HIP_TRY(hipMemcpyAsync(out, d_out, out_n, hipMemcpyDeviceToHost, u.stream));
-    HIP_TRY(hipStreamSynchronize(u.stream));
-    return RC_OK;
+    return so.finish(out, out_n);
 }
 
 RC_EXPORT int rc_bit_unpack(const uint8_t *packed, uint64_t packed_bytes, uint64_t n, uint32_t bit_depth, uint64_t *out)
@@ -1070,20 +1032,13 @@ RC_EXPORT int rc_bit_unpack(const uint8_t *packed, uint64_t packed_bytes, uint64
     if (r != RC_OK) return r;
     Util &u = g_util;
     const uint8_t *d_in = nullptr;
-    r = stage_in(packed, packed_bytes, u.a, u.a_cap, d_in);
+    r = stage_in(packed, packed_bytes, u.a, d_in);
     if (r != RC_OK) return r;
-    uint64_t *d_out = out;
-    const bool out_host = !is_device_ptr(out);
-    if (out_host) {
-        r = ensure(u.o, u.o_cap, n * 8);
-        if (r != RC_OK) return r;
-        d_out = reinterpret_cast<uint64_t *>(u.o);
-    }
-    rc::launch_bit_unpack(d_in, packed_bytes, n, bit_depth, d_out, u.stream);
+    StagedOut so;
+    if ((r = so.begin(out, n * 8)) != RC_OK) return r;
+    rc::launch_bit_unpack(d_in, packed_bytes, n, bit_depth, so.as<uint64_t>(), u.stream);
     HIP_TRY(hipGetLastError());
-    if (out_host) HIP_TRY(hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, u.stream));
-    HIP_TRY(hipStreamSynchronize(u.stream));
-    return RC_OK;
+    return so.finish(out, n * 8);
 }
 
 // ---- synthetic stacks -------------------------------------------------------------------------------------------

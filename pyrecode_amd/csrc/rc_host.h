@@ -1,6 +1,8 @@
 // rc_host.h - host-side plumbing shared by the translation units behind the C ABI (rc_api.hip: contexts and seam 1;
-// rc_reader.hip: the batched reader; rc_codec_api.hip: the stateless codec seams): status / error text, device guard, device
-// scratch helpers, and the per-GPU utility context the stateless entry points share.  The few globals are defined in rc_api.hip.
+// rc_reader.hip: the batched reader; rc_codec_api.hip: the stateless codec seams): status / error text, device guard, the owners of
+// device and page-locked memory (DevMem / PinMem: every allocation of a ctx or a utility context is on its owner's list, so none can be
+// forgotten when it is freed) with their growable buffers (DevBuf / PinBuf), the per-GPU utility context the stateless entry points
+// share, and the staging helpers of those entry points (stage_in, StagedOut, HostView).  The few globals are defined in rc_api.hip.
 // The library has no experiment switches.  What it reads from the environment are settings that tests use and that cannot produce a
 // wrong record - RC_REDUCE_GUARDED_LOADS, RC_ZSTD_LITS_ALWAYS / RC_ZSTD_SEQ_ALWAYS - and plain tuning / measurement settings - RC_DEVICE,
 // RC_DECODE_THREADS, RC_READ_THREADS, RC_PROFILE_ALL_STAGES, RC_READ_TIMING, RC_READ_SERIAL.
@@ -33,13 +35,12 @@
 
 extern thread_local std::string g_last_error;   // rc_last_error(): one per thread, whichever translation unit failed
 
-namespace {
-int fail(int code, const char *what)
+inline int fail(int code, const char *what)
 {
     g_last_error = what ? what : "";
     return code;
 }
-int hip_fail(hipError_t e, const char *where)
+inline int hip_fail(hipError_t e, const char *where)
 {
     g_last_error = std::string(where) + ": " + hipGetErrorString(e);
     if (e == hipErrorOutOfMemory) {   // the workspace does not fit this GPU's free memory: a status of its own, and no sticky HIP error left behind
@@ -54,6 +55,75 @@ int hip_fail(hipError_t e, const char *where)
         if (e_ != hipSuccess) return hip_fail(e_, #expr);     \
     } while (0)
 
+// ---- owners of device and page-locked memory -----------------------------------------------------------------------------
+// Everything one object (a ctx, a utility context, a PinnedVec) allocated, as a list: alloc() writes the pointer into a plain field - a
+// rc::Scratch member, say: the kernel argument stays a POD and its owner sits beside it -, free_one() gives one allocation back and
+// clears the field, release_all() gives back the rest.  No destructor: rc_ctx_destroy releases a ctx's memory explicitly, behind its
+// device guard and stream synchronisation, and the utility contexts (g_utils) are never freed - no HIP call may run during static
+// destruction.
+template <bool Device>
+struct MemOwner {
+    std::vector<void *> held;
+    template <class T>
+    hipError_t try_alloc(T *&field, uint64_t bytes, unsigned flags = hipHostMallocDefault)   // (flags: page-locked memory only)
+    {
+        void *p = nullptr;
+        hipError_t e = Device ? hipMalloc(&p, bytes) : hipHostMalloc(&p, bytes, flags);
+        if (e != hipSuccess) return e;
+        held.push_back(p);
+        field = static_cast<T *>(p);
+        return hipSuccess;
+    }
+    // what: names the buffer in rc_last_error() when the allocation fails (RC_ALLOC passes the field and its size as written)
+    template <class T>
+    int alloc(T *&field, uint64_t bytes, const char *what = "a growable buffer", unsigned flags = hipHostMallocDefault)
+    {
+        hipError_t e = try_alloc(field, bytes, flags);
+        return e == hipSuccess ? RC_OK : hip_fail(e, (std::string(Device ? "hipMalloc(" : "hipHostMalloc(") + what + ")").c_str());
+    }
+    static void release(void *p) { if (Device) (void)hipFree(p); else (void)hipHostFree(p); }
+    template <class T>
+    void free_one(T *&field)
+    {
+        auto it = std::find(held.begin(), held.end(), (void *)field);
+        if (it != held.end()) { release(*it); held.erase(it); }
+        field = nullptr;
+    }
+    void release_all()
+    {
+        for (void *p : held) release(p);
+        held.clear();
+    }
+};
+using DevMem = MemOwner<true>;
+using PinMem = MemOwner<false>;
+
+// A buffer of its owner that grows on demand and keeps its capacity: ensure(m, need) leaves at least `need` bytes (contents are not
+// kept; a new allocation is need + extra bytes, so that a slowly growing demand does not allocate every call).
+template <class Mem>
+struct Buf {
+    uint8_t *p = nullptr;
+    uint64_t cap = 0;
+    int ensure(Mem &m, uint64_t need, uint64_t extra = 0)
+    {
+        if (p && need <= cap) return RC_OK;
+        m.free_one(p);
+        cap = 0;
+        int r = m.alloc(p, (need + extra) ? (need + extra) : 16);
+        if (r == RC_OK) cap = need + extra;
+        return r;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+using DevBuf = Buf<DevMem>;
+using PinBuf = Buf<PinMem>;
+#define RC_ALLOC(owner, field, bytes)                         \
+    do {                                                      \
+        int r_ = (owner).alloc(field, bytes, #field ", " #bytes); \
+        if (r_ != RC_OK) return r_;                           \
+    } while (0)
+
+namespace {
 // true when p is memory the GPU kernels can dereference (device or managed); false for ordinary host memory
 bool is_device_ptr(const void *p)
 {
@@ -65,18 +135,6 @@ bool is_device_ptr(const void *p)
         return false;
     }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-template <class T>
-int ensure(T *&buf, uint64_t &cap, uint64_t need)
-{
-    if (need <= cap && buf) return RC_OK;
-    if (buf) HIP_TRY(hipFree(buf));
-    buf = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&buf), need ? need : 16));
-    cap = need;
-    return RC_OK;
 }
 
 int copy_out(void *dst, const void *src_dev, uint64_t bytes, hipStream_t s)
@@ -192,6 +250,7 @@ extern WorkerPool *g_pool;
 // Growable array in page-locked host memory (a hipMemcpyAsync from it is a real asynchronous copy; capacity is kept).
 template <class T>
 struct PinnedVec {
+    PinMem mem;                         // its own owner: the indexing threads grow their vectors side by side
     T *p = nullptr; size_t n = 0, cap = 0;
     bool ok = true;                     // false: an allocation failed (checked by the caller after the indexing threads have joined)
     void clear() { n = 0; ok = true; }
@@ -200,9 +259,9 @@ struct PinnedVec {
     bool grow(size_t nc)
     {
         T *q = nullptr;
-        if (hipHostMalloc((void **)&q, nc * sizeof(T), hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); ok = false; return false; }
+        if (mem.try_alloc(q, nc * sizeof(T), hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); ok = false; return false; }
         if (n) memcpy(q, p, n * sizeof(T));
-        if (p) (void)hipHostFree(p);
+        mem.free_one(p);
         p = q; cap = nc;
         return true;
     }
@@ -224,13 +283,14 @@ constexpr int RC_READ_SLOTS = 2;
 struct ReadRes {
     hipStream_t stream = nullptr, stream2 = nullptr;       // the two streams' decoders run side by side
     hipEvent_t ev_a = nullptr, ev_b = nullptr, done = nullptr;
-    uint8_t *x[10] = {}; uint64_t x_cap[10] = {};          // device: data, decoded streams, -, head, -, counters, staged triplets
+    DevBuf d_data, d_streams, d_head, d_counters, d_triplets;   // device (the utility context's DevMem): the stored bytes, the decoded streams,
+                                                           // tables + per-frame index arrays, per-block counters, triplets staged for a host caller
     PinnedVec<rc::ZdBlock> rd_bm[RC_READ_THREADS], rd_pv[RC_READ_THREADS], rd_raw[RC_READ_THREADS];   // per indexing thread, page-locked
     std::vector<rc::ZdBlock> rd_tmp[RC_READ_THREADS];
     PinnedVec<uint32_t> rd_off[RC_READ_THREADS];           // compact lists of uniform binary-map streams: one header offset per block (k_bitmap_decode_c)
-    uint8_t *rd_head = nullptr; uint64_t rd_head_cap = 0;  // page-locked: decoding tables + per-frame index arrays
-    uint64_t *h_res = nullptr; uint64_t h_res_cap = 0;     // page-locked: nnz prefix (n + 1) and the error word, as the device left them
-    uint8_t *h_blob = nullptr; uint64_t h_blob_cap = 0;    // page-locked: host copy of a DEVICE-resident input, for the header walk
+    PinBuf rd_head;                                        // page-locked (the utility context's PinMem): decoding tables + per-frame index arrays
+    PinBuf h_res;                                          // ... nnz prefix (n + 1) and the error word, as the device left them (uint64)
+    PinBuf h_blob;                                         // ... host copy of a DEVICE-resident input, for the header walk
     // a submitted batch waiting for its rc_expand_frames_wait
     bool pending = false;
     uint32_t n = 0, level = 0, bit_depth = 0;
@@ -242,14 +302,13 @@ struct Util {
     std::mutex mu;
     int device = -1;
     hipStream_t stream = nullptr;
-    uint8_t *a = nullptr; uint64_t a_cap = 0;   // input 1
-    uint8_t *b = nullptr; uint64_t b_cap = 0;   // input 2
-    uint8_t *o = nullptr; uint64_t o_cap = 0;   // output
-    uint8_t *w = nullptr; uint64_t w_cap = 0;   // work
+    DevMem dmem;                                // owns every device allocation below and in rr[]; never released (see MemOwner)
+    PinMem hmem;                                // ... and the page-locked ones
+    DevBuf a, b, o, w;                          // input 1, input 2, output, work
     uint64_t *h_scalar = nullptr;               // pinned
-    void *ztab = nullptr;                       // zstd FSE tables
-    uint8_t *x[10] = {}; uint64_t x_cap[10] = {};   // rc_expand_frames: data, bitmaps, values, tables, block lists, counters
-    void *zd_predef = nullptr;                  // predefined zstd decoding tables
+    void *ztab = nullptr;                       // zstd FSE tables (zstd_encoder_tables)
+    DevBuf zd_out, zd_blocks, zd_tables, zd_ctl;   // rc_decompress(zstd): decoded bytes, block lists, the frame's tables, lists / base / error / produced
+    void *zd_predef = nullptr;                  // predefined zstd decoding tables (zstd_predefined_tables)
     ReadRes rr[RC_READ_SLOTS + 1];              // the submit / wait form's two slots, then the synchronous rc_expand_frames' own:
                                                 // a synchronous call (e.g. the reader's fallback for ONE batch) never meets a queued batch
 };
@@ -279,7 +338,7 @@ struct UtilScope {
         HIP_TRY(guard.enter(dev));
         if (t_util->device < 0) {
             HIP_TRY(hipStreamCreateWithFlags(&t_util->stream, hipStreamNonBlocking));
-            HIP_TRY(hipHostMalloc((void **)&t_util->h_scalar, 64, hipHostMallocDefault));
+            RC_ALLOC(t_util->hmem, t_util->h_scalar, 64);
             t_util->device = dev;
         }
         return RC_OK;
@@ -288,19 +347,88 @@ struct UtilScope {
 
 // device-visible view of caller memory: the pointer itself, or a staged copy in `buf`
 template <class T>
-int stage_in(const T *src, uint64_t bytes, uint8_t *&buf, uint64_t &cap, const T *&dev, uint64_t pad = 0)
+int stage_in(const T *src, uint64_t bytes, DevBuf &buf, const T *&dev, uint64_t pad = 0)
 {
     if (is_device_ptr(src) && pad == 0) {
         dev = src;
         return RC_OK;
     }
-    int r = ensure(buf, cap, bytes + pad);
+    int r = buf.ensure(g_util.dmem, bytes + pad);
     if (r != RC_OK) return r;
-    if (pad) HIP_TRY(hipMemsetAsync(buf + bytes, 0, pad, g_util.stream));
+    if (pad) HIP_TRY(hipMemsetAsync(buf.p + bytes, 0, pad, g_util.stream));
     if (bytes)
-        HIP_TRY(hipMemcpyAsync(buf, src, bytes, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(buf.p, src, bytes, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                g_util.stream));
-    dev = reinterpret_cast<const T *>(buf);
+    dev = reinterpret_cast<const T *>(buf.p);
+    return RC_OK;
+}
+
+// Where a kernel of the utility context writes `bytes` of result the caller wants at `dst`: dst itself when the GPU can address it,
+// otherwise the staging buffer g_util.o; finish() copies a staged result back and waits for the stream either way.
+struct StagedOut {
+    void *dev = nullptr;
+    bool host = false;
+    int begin(void *dst, uint64_t bytes)
+    {
+        host = !is_device_ptr(dst);
+        dev = dst;
+        if (!host) return RC_OK;
+        int r = g_util.o.ensure(g_util.dmem, bytes);
+        dev = g_util.o.p;
+        return r;
+    }
+    template <class T> T *as() const { return static_cast<T *>(dev); }
+    int finish(void *dst, uint64_t bytes)
+    {
+        if (host) HIP_TRY(hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, g_util.stream));
+        HIP_TRY(hipStreamSynchronize(g_util.stream));
+        return RC_OK;
+    }
+};
+
+// Host view of a source that may lie in device memory (frame and block headers are walked on the host: sequential by format, a few
+// bytes per block), with a little-endian dword reader.
+struct HostView {
+    std::vector<uint8_t> copy;
+    const uint8_t *h = nullptr;
+    int open(const uint8_t *src, uint64_t n)
+    {
+        h = src;
+        if (!is_device_ptr(src)) return RC_OK;
+        copy.resize(n);
+        HIP_TRY(hipMemcpy(copy.data(), src, n, hipMemcpyDeviceToHost));
+        h = copy.data();
+        return RC_OK;
+    }
+    uint8_t operator[](uint64_t p) const { return h[p]; }
+    uint32_t rd32(uint64_t p) const { return (uint32_t)h[p] | ((uint32_t)h[p + 1] << 8) | ((uint32_t)h[p + 2] << 16) | ((uint32_t)h[p + 3] << 24); }
+};
+
+// The zstd encoder's FSE tables (rc_zstd_block.h) in device memory of `m`, uploaded when `tab` is still empty: a ctx has its own copy,
+// the utility context one per GPU.
+int zstd_encoder_tables(DevMem &m, void *&tab)
+{
+    if (tab) return RC_OK;
+    std::vector<uint8_t> t(rc::zstd_tables_bytes());
+    rc::zstd_tables_host(t.data());
+    void *d = nullptr;
+    int r = m.alloc(d, t.size(), "the zstd encoder tables");
+    if (r != RC_OK) return r;
+    HIP_TRY(hipMemcpy(d, t.data(), t.size(), hipMemcpyHostToDevice));
+    tab = d;
+    return RC_OK;
+}
+// The predefined zstd decoding tables (rc_zstd_dec.h) of the utility context, uploaded on first use.
+int zstd_predefined_tables(Util &u)
+{
+    if (u.zd_predef) return RC_OK;
+    std::vector<uint8_t> t(rc::zd_tables_bytes());
+    rc::zd_predefined_tables(t.data());
+    void *d = nullptr;
+    int r = u.dmem.alloc(d, t.size(), "the predefined zstd decoding tables");
+    if (r != RC_OK) return r;
+    HIP_TRY(hipMemcpy(d, t.data(), t.size(), hipMemcpyHostToDevice));
+    u.zd_predef = d;
     return RC_OK;
 }
 }  // namespace

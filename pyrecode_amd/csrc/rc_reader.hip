@@ -95,42 +95,27 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         HIP_TRY(hipEventCreateWithFlags(&u.ev_b, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
     }
-    if (u.h_res_cap < (uint64_t)n + 2) {
-        if (u.h_res) HIP_TRY(hipHostFree(u.h_res));
-        u.h_res = nullptr; u.h_res_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&u.h_res, ((uint64_t)n + 2) * 8, hipHostMallocDefault));
-        u.h_res_cap = (uint64_t)n + 2;
-    }
+    if ((r = u.h_res.ensure(U.hmem, ((uint64_t)n + 2) * 8)) != RC_OK) return r;
+    uint64_t *h_res = u.h_res.as<uint64_t>();
     hipStream_t s = u.stream;
     const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
     const uint64_t out_bytes = (uint64_t)n * (bm_stride + (level == 1 ? pv_stride : 0)) + 64;
-    auto need = [&](int i, uint64_t bytes) { return ensure(u.x[i], u.x_cap[i], bytes); };
     // head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n][pv_bytes n] [base2 2n][pv_base n][src_base n], the
     // same layout in page-locked host memory and on the device: one copy
     const uint64_t ntab = codec == EMIT_ZSTD ? 2 * (uint64_t)n : 0;
     const uint64_t o_first = ntab * sizeof(ZdTables);
     const uint64_t o_base2 = (o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList) + (uint64_t)n * 4 + 15) & ~15ull;
     const uint64_t sz_head = o_base2 + (uint64_t)n * 4 * 8;
-    if ((r = need(0, total_in + 64)) != RC_OK || (r = need(1, out_bytes)) != RC_OK || (r = need(3, sz_head)) != RC_OK ||
-        (r = need(5, (uint64_t)n * nblk * 8 + (uint64_t)(2 * n + 2) * 8 + 64)) != RC_OK)
+    if ((r = u.d_data.ensure(U.dmem, total_in + 64)) != RC_OK || (r = u.d_streams.ensure(U.dmem, out_bytes)) != RC_OK ||
+        (r = u.d_head.ensure(U.dmem, sz_head)) != RC_OK ||
+        (r = u.d_counters.ensure(U.dmem, (uint64_t)n * nblk * 8 + (uint64_t)(2 * n + 2) * 8 + 64)) != RC_OK ||
+        (r = u.rd_head.ensure(U.hmem, sz_head)) != RC_OK || (r = zstd_predefined_tables(U)) != RC_OK)
         return r;
-    if (u.rd_head_cap < sz_head) {
-        if (u.rd_head) HIP_TRY(hipHostFree(u.rd_head));
-        u.rd_head = nullptr; u.rd_head_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&u.rd_head, sz_head, hipHostMallocDefault));
-        u.rd_head_cap = sz_head;
-    }
-    if (!U.zd_predef) {
-        std::vector<uint8_t> t(zd_tables_bytes());
-        zd_predefined_tables(t.data());
-        HIP_TRY(hipMalloc(&U.zd_predef, t.size()));
-        HIP_TRY(hipMemcpy(U.zd_predef, t.data(), t.size(), hipMemcpyHostToDevice));
-    }
     // The compressed bytes: device memory is used where it lies; host memory is copied in, and the copy runs while the host walks the
     // streams.  (Letting the decoders read page-locked host memory in place - their staging loads as the transfer - was slower: the
     // transfer then sits inside the decoders' critical path, 1.3 ms against 0.7 ms behind a copy that hides under the host walk.)
-    const uint8_t *d_data = u.x[0];
-    uint8_t *d_out = u.x[1];
+    const uint8_t *d_data = u.d_data.p;
+    uint8_t *d_out = u.d_streams.p;
     bool copy_in = true;
     {
         // in place only if the decoders' 16-byte staging loads (and the bit readers' dword loads) can neither be misaligned nor leave
@@ -139,36 +124,31 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         const bool usable = ((uintptr_t)data & 15u) == 0 && (end & 4095u) != 0 && (end & 4095u) <= 4096u - 16u;
         if (usable && is_device_ptr(data)) { d_data = data; copy_in = false; }
     }
-    uint32_t *d_blk_cnt = reinterpret_cast<uint32_t *>(u.x[5]), *d_blk_off = d_blk_cnt + (uint64_t)n * nblk;
+    uint32_t *d_blk_cnt = u.d_counters.as<uint32_t>(), *d_blk_off = d_blk_cnt + (uint64_t)n * nblk;
     uint64_t *d_fnnz = reinterpret_cast<uint64_t *>(d_blk_off + (uint64_t)n * nblk), *d_fbase = d_fnnz + n;
     int *d_err = reinterpret_cast<int *>(d_fbase + n + 1);
     // The header walk below runs on the host.  Bytes that lie in device memory are fetched once into page-locked memory for it (the
     // host CAN read device memory through the PCIe aperture, a few hundred MB/s: 187 ms for 34 MB); the decoders read them where they are.
     const uint8_t *walk = data;
     if (is_device_ptr(data)) {
-        if (u.h_blob_cap < total_in + 64) {
-            if (u.h_blob) HIP_TRY(hipHostFree(u.h_blob));
-            u.h_blob = nullptr; u.h_blob_cap = 0;
-            HIP_TRY(hipHostMalloc((void **)&u.h_blob, total_in + 64 + total_in / 4, hipHostMallocDefault));
-            u.h_blob_cap = total_in + 64 + total_in / 4;
-        }
-        HIP_TRY(hipMemcpyAsync(u.h_blob, data, total_in, hipMemcpyDeviceToHost, s));
+        if ((r = u.h_blob.ensure(U.hmem, total_in + 64, total_in / 4)) != RC_OK) return r;
+        HIP_TRY(hipMemcpyAsync(u.h_blob.p, data, total_in, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        walk = u.h_blob;
+        walk = u.h_blob.p;
     }
-    if (copy_in) HIP_TRY(hipMemcpyAsync(u.x[0], data, total_in, hipMemcpyDefault, s));
+    if (copy_in) HIP_TRY(hipMemcpyAsync(u.d_data.p, data, total_in, hipMemcpyDefault, s));
     HIP_TRY(hipMemsetAsync(d_out, 0, out_bytes, s));   // bitmap padding and value-stream tails read as zero
     HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
     // ---- host: walk the frames, build block tables and decoding tables (a few threads, each a contiguous range of frames) ----
     // (the copy-in reads the caller's memory: no return from here on without waiting for it)
     auto bail = [&](int code, const char *msg) { (void)hipStreamSynchronize(s); return fail(code, msg); };
-    ZdTables *bm_tab = reinterpret_cast<ZdTables *>(u.rd_head), *pv_tab = bm_tab + (codec == EMIT_ZSTD ? n : 0);
+    ZdTables *bm_tab = u.rd_head.as<ZdTables>(), *pv_tab = bm_tab + (codec == EMIT_ZSTD ? n : 0);
     // The block lists stay where the indexing threads wrote them, in page-locked host memory: the decoders read every entry once,
     // over the link (uploading them meant 3 small copies per thread, each a fixed ~15 us of stream time: 0.7 ms per call).
-    ZdFrameList *bm_list = reinterpret_cast<ZdFrameList *>(u.rd_head + o_first), *pv_list = bm_list + n, *raw_list = pv_list + n;
+    ZdFrameList *bm_list = reinterpret_cast<ZdFrameList *>(u.rd_head.p + o_first), *pv_list = bm_list + n, *raw_list = pv_list + n;
     ZdFrameList *cbm_list = raw_list + RC_READ_THREADS;
     uint32_t *pv_bytes = reinterpret_cast<uint32_t *>(cbm_list + n);
-    uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n;
+    uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head.p + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n;
     // c0, c_n: the frame's range in its thread's compact offset list (c_n blocks = c_n + 1 offsets); c_skips: tree_skip | seq_skip << 8
     struct FrameIndex { uint32_t bm0 = 0, bm_n = 0, pv0 = 0, pv_n = 0, thread = 0, c0 = 0, c_n = 0, c_skips = 0; int status = ZD_OK; const char *what = nullptr; };
     std::vector<FrameIndex> fi(n);
@@ -300,12 +280,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (n_raw >= (1ull << 31)) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
     const double t_2 = now();
     // ---- device ----
-    ZdTables *d_bm_tab = reinterpret_cast<ZdTables *>(u.x[3]), *d_pv_tab = d_bm_tab + (codec == EMIT_ZSTD ? n : 0);
-    const ZdFrameList *d_bm_list = reinterpret_cast<const ZdFrameList *>(u.x[3] + o_first), *d_pv_list = d_bm_list + n, *d_raw_list = d_pv_list + n;
+    ZdTables *d_bm_tab = u.d_head.as<ZdTables>(), *d_pv_tab = d_bm_tab + (codec == EMIT_ZSTD ? n : 0);
+    const ZdFrameList *d_bm_list = reinterpret_cast<const ZdFrameList *>(u.d_head.p + o_first), *d_pv_list = d_bm_list + n, *d_raw_list = d_pv_list + n;
     const ZdFrameList *d_cbm_list = d_raw_list + RC_READ_THREADS;
-    uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.x[3] + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
-    uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.x[3] + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n;
-    HIP_TRY(hipMemcpyAsync(u.x[3], u.rd_head, sz_head, hipMemcpyHostToDevice, s));
+    uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.d_head.p + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
+    uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.d_head.p + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n;
+    HIP_TRY(hipMemcpyAsync(u.d_head.p, u.rd_head.p, sz_head, hipMemcpyHostToDevice, s));
     const double t_3 = now();
     // the value streams' chunks (few, long serial chains) decode next to the binary maps' blocks (many, short), on a second stream
     static const bool serial = getenv("RC_READ_SERIAL") != nullptr;   // development: both decoders on one stream (clean per-kernel times)
@@ -333,9 +313,9 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (submit_only && !dev_out) {
         hipPointerAttribute_t a;
         if (hipPointerGetAttributes(&a, triplets) == hipSuccess && a.type == hipMemoryTypeHost) {
-            if ((r = need(6, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+            if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
             host_async = triplets;
-            triplets = reinterpret_cast<uint64_t *>(u.x[6]);
+            triplets = u.d_triplets.as<uint64_t>();
             dev_out = true;
         } else (void)hipGetLastError();
     }
@@ -346,8 +326,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     } else
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(u.h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(u.h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
     if (host_async && cap) HIP_TRY(hipMemcpyAsync(host_async, triplets, cap * esz, hipMemcpyDeviceToHost, s));
     if (submit_only) {   // (dev_out is a precondition, checked above)
         HIP_TRY(hipEventRecord(u.done, s));
@@ -357,8 +337,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         return RC_OK;
     }
     HIP_TRY(hipStreamSynchronize(s));
-    const int err = (int)(uint32_t)u.h_res[n + 1];
-    memcpy(nnz_prefix, u.h_res, (size_t)(n + 1) * 8);
+    const int err = (int)(uint32_t)h_res[n + 1];
+    memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
     const double t_4 = now();
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     const uint64_t total = nnz_prefix[n];
@@ -377,18 +357,18 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (total == 0) return RC_OK;
     if (coo) {
         // the three arrays keep the caller's stride (cap) on the device as in the caller's buffer: three copies of `total` entries
-        if ((r = need(6, cap * esz + 64)) != RC_OK) return r;
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, cap, u.x[6], s, nullptr, true);
+        if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) return r;
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, cap, u.d_triplets.p, s, nullptr, true);
         HIP_TRY(hipGetLastError());
         uint8_t *h = reinterpret_cast<uint8_t *>(triplets);
-        HIP_TRY(hipMemcpyAsync(h, u.x[6], total * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h + cap * 4, u.x[6] + cap * 4, total * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h + cap * 8, u.x[6] + cap * 8, total * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h, u.d_triplets.p, total * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h + cap * 4, u.d_triplets.p + cap * 4, total * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * 2, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return RC_OK;
     }
-    if ((r = need(6, total * 24)) != RC_OK) return r;
-    uint64_t *d_trip = reinterpret_cast<uint64_t *>(u.x[6]);
+    if ((r = u.d_triplets.ensure(U.dmem, total * 24)) != RC_OK) return r;
+    uint64_t *d_trip = u.d_triplets.as<uint64_t>();
     launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, total, d_trip, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(triplets, d_trip, total * 24, hipMemcpyDeviceToHost, s));
@@ -440,8 +420,9 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
     u.pending = false;
     HIP_TRY(hipEventSynchronize(u.done));
     const uint32_t n = u.n;
-    const int err = (int)(uint32_t)u.h_res[n + 1];
-    memcpy(nnz_prefix, u.h_res, (size_t)(n + 1) * 8);
+    const uint64_t *h_res = u.h_res.as<uint64_t>();
+    const int err = (int)(uint32_t)h_res[n + 1];
+    memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     if (nnz_prefix[n] > u.cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
     if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
