@@ -256,7 +256,7 @@ int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_depth, con
  * with no host round trip in between.  Replaces, for n frames at once, ReCoDeReader._get_frame_sparse
  * (pyrecode/recode_reader.py:379-471: de_compress on the binary-map stream and on the value stream,
  * recode_compressors.py:40-79, then c_recode get_frame_sparse, pyrecode.cpp:95-119).
- *   nx, ny, bit_depth, reduction_level (1 or 3), op_mode, scheme    header fields of the file
+ *   nx, ny, bit_depth, reduction_level (1, 2 or 3), op_mode, scheme    header fields of the file
  *   data          host or device memory: the n frames' data blobs back to back, as they lie in a merged file (per frame: the
  *                 binary-map stream, then the value stream).  Host memory is copied in while the streams' block headers are
  *                 walked (page-locked memory - rc_host_alloc - makes that copy asynchronous); device memory is decoded where it lies
@@ -267,7 +267,13 @@ int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_depth, con
  *   triplets      uint64[cap][3] out (host or device): (row, col, value) in row-major order per frame, frames in order;
  *                 may be NULL with cap 0 (a counting call)
  * Device decoders: mode 0 (stored pieces), LZ4 frames with independent blocks, zstd frames inside the subset rc_zstd_dec.h
- * describes (wider than what this library writes).  Anything else returns RC_ERR_UNSUPPORTED before any work is done and the caller falls back to
+ * describes (wider than what this library writes), and blosc1-LZ4 chunks (RC_SCHEME_BLOSC_LZ4; replaces blosc.decompress,
+ * recode_compressors.py:61-76) of the shape this library writes: version 2, typesize 8, blocks of 512 bytes that are not split, bit-shuffled
+ * or not shuffled, or a "memcpyed" chunk of exactly 16 + nbytes bytes (either stream; the value stream only so).  A chunk whose header's
+ * nbytes / cbytes disagree with the frame, or whose block starts / sizes leave the stream or exceed a block's LZ4 bound, is RC_ERR_CORRUPT.
+ * reduction_level 2: the binary map expands exactly as at level 3 (value 1) and the statistics stream - sizes[i][1] bytes - is stepped
+ * over, as the reference's reader does (recode_reader.py:413-440: get_frame_sparse(level, map, None)); with triplets NULL this is the
+ * counting call that sizes the buffers of rc_expand_frames_l2.  Anything else returns RC_ERR_UNSUPPORTED before any work is done and the caller falls back to
  * the per-frame path with the stock decoder; a stream that is inside the subset on its face but does not decode to the frame's
  * shape (a foreign encoder's larger blocks, or damage) returns RC_ERR_CORRUPT - callers that can fall back should do so for both
  * codes and let the stock decoder judge.  RC_ERR_OUT_TOO_SMALL: nnz_prefix is valid, triplets untouched.  At reduction level 1
@@ -298,6 +304,25 @@ int rc_expand_frames_coo(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t 
                          const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap);
 int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
                                 uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap);
+/* A batch of reduction-level-2 frames in full: the set pixels AND every frame's summary statistics.  Replaces, for n frames at once, the
+ * level-2 branch of ReCoDeReader._get_frame_sparse (pyrecode/recode_reader.py:413-440 for the pixels, :473-481 for the statistics, whose
+ * unpacker is c_extensions/reader.h:74-99 - intended semantics) and the de_compress calls in front of it (:393-411).
+ *   rc            int32 rows[cap] | int32 columns[cap] (8 * cap bytes): the COO layout of rc_expand_frames_coo without the value array -
+ *                 every value is 1.  Frame i's entries are [nnz_prefix[i], nnz_prefix[i+1]) of both arrays; rc_expand_frames with
+ *                 reduction_level 2 and triplets NULL counts them beforehand
+ *   stats         uint16[stats_cap] out: the statistics, frame after frame.  Frame i holds floor(8 * sizes[i][2] / bit_depth) of them -
+ *                 the caller knows the prefix from the metadata table, so none is returned
+ *   bit_depth     8..16: narrower fields leave the count ambiguous (the per-frame reader settles it by labelling) and level 2 does not exist
+ *                 for wider sources - RC_ERR_UNSUPPORTED for both
+ * op_mode / scheme, data, sizes, nnz_prefix, host or device pointers and the status codes as for rc_expand_frames_coo;
+ * RC_ERR_OUT_TOO_SMALL (cap or stats_cap) leaves nnz_prefix valid and writes neither output.  rc_expand_frames_l2_submit queues the batch on
+ * a slot like rc_expand_frames_coo_submit (rc_dev and stats_dev: device or page-locked host memory; a stats_cap that is too small is
+ * reported at once, nothing left pending) and is waited for with rc_expand_frames_wait. */
+int rc_expand_frames_l2(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                        const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *rc, uint64_t cap, uint16_t *stats, uint64_t stats_cap);
+int rc_expand_frames_l2_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme,
+                               const uint8_t *data, const uint32_t *sizes, uint32_t n, void *rc_dev, uint64_t cap, uint16_t *stats_dev,
+                               uint64_t stats_cap);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

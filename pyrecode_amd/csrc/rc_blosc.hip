@@ -15,6 +15,7 @@
 // behind the shuffled part are copied unchanged (c-blosc's blosc_internal_bitshuffle).
 #include "rc_launch.h"
 #include "rc_lz4_block.h"
+#include "rc_zstd_dec.h"
 
 namespace rc {
 
@@ -100,6 +101,107 @@ void launch_blosc_unshuffle(const uint8_t *in, uint8_t *out, uint64_t nbytes, ui
     if (!nbytes) return;
     hipLaunchKernelGGL(k_blosc_unshuffle, dim3((uint32_t)((nbytes + 255) / 256)), dim3(256), 0, s, in, out, nbytes, blocksize,
                        typesize, shuffle);
+}
+
+// ---- decode side, batched reader (rc_expand_frames & co., scheme 8): ONE WAVEFRONT decodes ONE BLOCK of one frame's chunk - LZ4 block
+// (or stored bytes) -> LDS, bit-unshuffle inside the wave, tile -> its place in the frame's decoded image.  Replaces, for every block of
+// every frame of a batch at once, blosc.decompress on the frame's streams (pyrecode/recode_compressors.py:61-76, called from
+// recode_reader.py:393-411).  The host walk (rc_reader.hip::blosc_index_stream) has checked every block's place and size: csize is at
+// most the LZ4 bound of 512 bytes, so the compressed bytes always fit the wave's stage.
+constexpr uint32_t BLOSC_IN_DW = 136;   // dwords staged per block: LZ4 bound of TILE_BM (530 bytes) + up to 3 bytes of misalignment in front
+
+// One LZ4 block (lz4_Block_format.md), n bytes at `in`, into out[0 .. cap), both in the wave's LDS; returns the bytes produced.  The
+// sequence headers are read by all lanes alike (wave-uniform, through readfirstlane), literals and matches are copied by the lanes side by
+// side: a match's byte i is byte i % offset of the `offset` bytes in front of it, which are complete before the copy starts.
+__device__ __forceinline__ uint32_t lz4_block_decode_wave(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t cap, uint32_t lane, int *err)
+{
+    auto byte = [&](uint32_t i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)in[i]); };
+    uint32_t ip = 0, op = 0;
+    while (ip < n) {
+        const uint32_t token = byte(ip++);
+        uint32_t lit = token >> 4;
+        if (lit == 15) { uint32_t x; do { if (ip >= n) { *err = 1; return op; } x = byte(ip++); lit += x; } while (x == 255); }
+        if (ip + lit > n || op + lit > cap) { *err = 1; return op; }
+        for (uint32_t i = lane; i < lit; i += 64) out[op + i] = in[ip + i];
+        ip += lit;
+        op += lit;
+        if (ip >= n) break;
+        if (ip + 2 > n) { *err = 1; return op; }
+        const uint32_t off = byte(ip) | (byte(ip + 1) << 8);
+        ip += 2;
+        uint32_t ml = token & 15u;
+        if (ml == 15) { uint32_t x; do { if (ip >= n) { *err = 1; return op; } x = byte(ip++); ml += x; } while (x == 255); }
+        ml += 4;
+        if (off == 0 || off > op || op + ml > cap) { *err = 1; return op; }
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t i = lane; i < ml; i += 64) out[op + i] = out[op - off + i % off];
+        __builtin_amdgcn_wave_barrier();
+        op += ml;
+    }
+    return op;
+}
+
+// grid (ceil(max blocks per frame / WAVES), frames): wave w takes entry blockIdx.x * WAVES + w of lists[blockIdx.y] (ZdBlock: src / csize =
+// the block's bytes behind its int32 size word, dst / regen = its place and size in the decoded stream, type 0 stored / 2 LZ4,
+// seq_tables = the chunk's shuffle flag: 0 none, 4 bit-shuffle).  `out` is zeroed by the caller: only what is not zero is stored.
+// The shuffled block is 64 rows of S/8 bytes, row r = bit r of the S elements (see the head of this file): lane i gathers bit i of every
+// row - a 64 x 64 bit transpose out of LDS.
+__global__ __launch_bounds__(WG) void k_blosc_decode_blocks(const uint8_t *__restrict__ data, const ZdFrameList *__restrict__ lists,
+                                                              uint8_t *__restrict__ out, const uint64_t *__restrict__ out_base, int *__restrict__ err)
+{
+    __shared__ uint32_t s_in[WAVES][BLOSC_IN_DW];
+    __shared__ uint64_t s_out[WAVES][TILE_BM / 8];
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (uint32_t)lane_id();
+    const uint32_t f = blockIdx.y, bi = blockIdx.x * WAVES + w;
+    if (bi >= lists[f].n) return;
+    const ZdBlock b = lists[f].p[bi];
+    const uint32_t n = b.regen;
+    int e = 0;
+    if (n == 0 || n > (uint32_t)TILE_BM || b.csize == 0 || b.csize > n + n / 255u + 16u || (b.type != 2 && b.csize != n)) e = 1;   // (the host walk's own rules)
+    uint8_t *raw = reinterpret_cast<uint8_t *>(s_out[w]);
+    if (!e) {
+        const uint64_t src0 = b.src & ~3ull;
+        const uint32_t mis = (uint32_t)(b.src - src0), ndw = (mis + b.csize + 3u) >> 2;        // <= BLOSC_IN_DW
+        const uint32_t *g = reinterpret_cast<const uint32_t *>(data + src0);                    // (data is 16-byte aligned and padded behind its end)
+        for (uint32_t i = lane; i < ndw; i += 64) s_in[w][i] = g[i];
+        __builtin_amdgcn_wave_barrier();
+        const uint8_t *in = reinterpret_cast<const uint8_t *>(s_in[w]) + mis;
+        if (b.type == 2) {
+            if (lz4_block_decode_wave(in, b.csize, raw, n, lane, &e) != n) e = 1;
+        } else
+            for (uint32_t i = lane; i < n; i += 64) raw[i] = in[i];
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (e) {
+        if (lane == 0) *err = 1;
+        return;
+    }
+    uint8_t *dst = out + out_base[b.frame] + b.dst;                                          // 8-byte aligned: frame slots and tiles are
+    const uint32_t S = b.seq_tables == 4 ? (n >> 3) & ~7u : 0u, whole = n >> 3;                 // elements shuffled / whole elements
+    if (lane < whole) {
+        uint64_t v;
+        if (lane < S) {
+            const uint32_t rowb = S >> 3, col = lane >> 3, sh = lane & 7u;
+            uint32_t lo = 0, hi = 0;
+#pragma unroll
+            for (uint32_t r = 0; r < 32; ++r) {
+                lo |= (((uint32_t)raw[r * rowb + col] >> sh) & 1u) << r;
+                hi |= (((uint32_t)raw[(r + 32) * rowb + col] >> sh) & 1u) << r;
+            }
+            v = (uint64_t)lo | ((uint64_t)hi << 32);
+        } else
+            v = s_out[w][lane];
+        if (v) reinterpret_cast<uint64_t *>(dst)[lane] = v;
+    }
+    const uint32_t tail = whole * 8u + lane;                                                  // the bytes behind the last whole element (< 8)
+    if (tail < n && raw[tail]) dst[tail] = raw[tail];
+}
+void launch_blosc_decode_blocks(const uint8_t *data, const void *frame_lists, uint32_t nframes, uint32_t max_blocks_per_frame, uint8_t *out,
+                                const uint64_t *out_base, int *err, hipStream_t s)
+{
+    if (!max_blocks_per_frame) return;
+    hipLaunchKernelGGL(k_blosc_decode_blocks, dim3((max_blocks_per_frame + WAVES - 1) / WAVES, nframes), dim3(WG), 0, s, data,
+                       reinterpret_cast<const ZdFrameList *>(frame_lists), out, out_base, err);
 }
 
 }  // namespace rc

@@ -23,6 +23,12 @@ void launch_bitmap_decode_compact(int codec, const uint8_t *data, const void *fr
                                   uint64_t nb, int *err, hipStream_t s);
 void launch_block_copy(const uint8_t *data, const void *lists, uint32_t nlists, uint32_t nblocks, uint32_t max_regen, uint8_t *out,
                        const uint64_t *out_base, hipStream_t s);
+// rc_blosc.hip: the blocks of blosc1 chunks (entries: rc::ZdBlock, seq_tables = the chunk's shuffle flag)
+void launch_blosc_decode_blocks(const uint8_t *data, const void *frame_lists, uint32_t nframes, uint32_t max_blocks_per_frame, uint8_t *out,
+                                const uint64_t *out_base, int *err, hipStream_t s);
+// level-2 statistics: d-bit fields of every frame's decoded stream -> uint16 (8 <= d <= 16)
+void launch_stats_unpack(const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, const uint64_t *st_base, uint32_t n, uint32_t max_count,
+                         uint32_t d, uint16_t *out, const int *err, hipStream_t s);
 size_t zd_tables_bytes();
 size_t zd_block_bytes();
 void zd_predefined_tables(void *dst);

@@ -166,6 +166,7 @@ constexpr uint32_t EMIT_STAGE = 1024;   // triplets
 // COO = false: out = uint64_t[cap][3], the reference's (row, col, value) rows (pyrecode.cpp:95-119).
 // COO = true: out = int32 rows[cap] | int32 columns[cap] | uint16 values[cap] - the three arrays of the scipy COO matrix the reference's
 // reader wraps the rows into (recode_reader.py:466-469), 10 instead of 24 bytes per set pixel on the link and no split on the host.
+// COO with level 2 (rc_expand_frames_l2): rows and columns only - every value is 1 and the caller's buffer ends behind the columns.
 template <bool COO>
 __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict__ bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx,
                                                         uint32_t nblk, const uint32_t *__restrict__ blk_off, const uint64_t *__restrict__ frame_base,
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict_
                 else { s_trip[3 * r] = row; s_trip[3 * r + 1] = col; s_trip[3 * r + 2] = val; }
             } else {
                 if (base + rank >= cap) break;
-                if (COO) { o_row[base + rank] = (int32_t)row; o_col[base + rank] = (int32_t)col; o_val[base + rank] = (uint16_t)val; }
+                if (COO) { o_row[base + rank] = (int32_t)row; o_col[base + rank] = (int32_t)col; if (level != 2) o_val[base + rank] = (uint16_t)val; }
                 else {
                     uint64_t *o = out + 3 * (base + rank);
                     o[0] = row; o[1] = col; o[2] = val;
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict_
     __syncthreads();
     if (COO) {
         const uint64_t at = base + wg_rank;
-        for (uint32_t j = threadIdx.x; j < tot; j += WG) { o_row[at + j] = (int32_t)s_row[j]; o_col[at + j] = (int32_t)s_col[j]; o_val[at + j] = s_val[j]; }
+        for (uint32_t j = threadIdx.x; j < tot; j += WG) { o_row[at + j] = (int32_t)s_row[j]; o_col[at + j] = (int32_t)s_col[j]; if (level != 2) o_val[at + j] = s_val[j]; }
     } else {
         uint64_t *o = out + 3 * (base + wg_rank);
         for (uint32_t j = threadIdx.x; j < 3 * tot; j += WG) o[j] = s_trip[j];
@@ -247,6 +248,33 @@ void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb
     else
         hipLaunchKernelGGL(k_expand_emit_b<false>, dim3(nblk, n), dim3(WG), 0, s, bm, bm_stride, nb8, N, nx, nblk, blk_off, frame_base, pv, pv_stride,
                            pv_bytes, d, level, cap, out, err);
+}
+
+// ---- level-2 statistics of a batch (rc_expand_frames_l2): frame f's decoded statistics stream at pv + f * pv_stride -> its
+// floor(8 * pv_bytes[f] / d) fields as uint16 at out + st_base[f].  Replaces the reader's host-side unpack (recode_reader.py:473-481 with
+// the intended semantics of c_extensions/reader.h:74-99) for every frame of the batch at once.  One thread per field, 8 <= d <= 16: a
+// field lies inside the two dwords at its bit position, and the second one is still inside the frame's slot (pv_stride >= bytes + 16,
+// zeroed behind the stream).  Writes nothing once a decoder has raised *err.
+__global__ __launch_bounds__(WG) void k_stats_unpack(const uint8_t *__restrict__ pv, uint64_t pv_stride, const uint32_t *__restrict__ pv_bytes,
+                                                       const uint64_t *__restrict__ st_base, uint32_t d, uint16_t *__restrict__ out,
+                                                       const int *__restrict__ err)
+{
+    if (*err) return;
+    const uint32_t f = blockIdx.y;
+    const uint32_t cnt = (uint32_t)(8ull * pv_bytes[f] / d);
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(pv + f * pv_stride);   // (slots are 16-byte aligned)
+    const uint64_t bit = (uint64_t)i * d;
+    const uint64_t w = bit >> 5;
+    const uint64_t v = (uint64_t)p[w] | ((uint64_t)p[w + 1] << 32);
+    out[st_base[f] + i] = (uint16_t)((v >> (bit & 31u)) & ((1u << d) - 1u));
+}
+void launch_stats_unpack(const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, const uint64_t *st_base, uint32_t n, uint32_t max_count,
+                         uint32_t d, uint16_t *out, const int *err, hipStream_t s)
+{
+    if (!max_count) return;
+    hipLaunchKernelGGL(k_stats_unpack, dim3((max_count + WG - 1) / WG, n), dim3(WG), 0, s, pv, pv_stride, pv_bytes, st_base, d, out, err);
 }
 
 // ---- stand-alone pack / unpack ------------------------------------------------------------------------------

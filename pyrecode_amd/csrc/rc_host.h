@@ -283,6 +283,7 @@ constexpr int RC_READ_SLOTS = 2;
 struct ReadRes {
     hipStream_t stream = nullptr, stream2 = nullptr;       // the two streams' decoders run side by side
     hipEvent_t ev_a = nullptr, ev_b = nullptr, done = nullptr;
+    DevBuf d_stats;                                        // level-2 statistics staged for a host caller (rc_expand_frames_l2)
     DevBuf d_data, d_streams, d_head, d_counters, d_triplets;   // device (the utility context's DevMem): the stored bytes, the decoded streams,
                                                            // tables + per-frame index arrays, per-block counters, triplets staged for a host caller
     PinnedVec<rc::ZdBlock> rd_bm[RC_READ_THREADS], rd_pv[RC_READ_THREADS], rd_raw[RC_READ_THREADS];   // per indexing thread, page-locked

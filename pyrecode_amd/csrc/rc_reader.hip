@@ -51,22 +51,80 @@ int lz4_index_frame(const uint8_t *base, uint64_t off, uint64_t n, uint32_t fram
     *total = out;
     return ZD_OK;
 }
+
+// One stream of a scheme-8 frame: a blosc1 chunk (rc_blosc.hip's head has the layout) -> one entry per block in `blocks` (type 2: an LZ4
+// block, 0: csize == the block's bytes, stored; seq_tables = the chunk's shuffle flag, 0 or 4), or ONE stored entry in `raw` for a
+// "memcpyed" chunk.  map: the binary-map stream - the value stream is taken as a memcpyed chunk only (what this library writes and what
+// c-blosc itself emits for bytes it cannot compress).  The device subset: version 2, LZ4 format, typesize 8, blocks of TILE_BM bytes, not
+// split, bit-shuffled or not shuffled; anything else is ZD_FOREIGN.  Sizes that disagree with the frame, and block positions or sizes
+// that leave the stream or exceed the LZ4 bound of a block, are ZD_CORRUPT: the decoding wave stages csize <= bound bytes and relies on it.
+template <class V, class VR>
+int blosc_index_stream(const uint8_t *base, uint64_t off, uint64_t n, uint32_t frame_idx, uint64_t total_expected, bool map, V &blocks, VR &raw)
+{
+    using namespace rc;
+    const uint8_t *p = base + off;
+    auto rd32 = [&](uint64_t q) { return (uint32_t)p[q] | ((uint32_t)p[q + 1] << 8) | ((uint32_t)p[q + 2] << 16) | ((uint32_t)p[q + 3] << 24); };
+    if (n < 16) return ZD_CORRUPT;
+    const uint32_t version = p[0], versionlz = p[1], flags = p[2], typesize = p[3];
+    const uint32_t nbytes = rd32(4), blocksize = rd32(8), cbytes = rd32(12);
+    if (version != 2) return ZD_FOREIGN;
+    const bool memcpyed = flags & 0x02u;
+    if (!memcpyed) {
+        if (!map) return ZD_FOREIGN;
+        if ((flags >> 5) != 1 || versionlz != 1 || !(flags & 0x10u) || (flags & 0x09u) || typesize != 8) return ZD_FOREIGN;   // codec, split, byte shuffle
+        if (blocksize != std::min<uint64_t>((uint64_t)TILE_BM, std::max<uint32_t>(nbytes, 1u))) return ZD_FOREIGN;
+    }
+    if (nbytes != total_expected || cbytes != n) return ZD_CORRUPT;
+    ZdBlock b;
+    memset(&b, 0, sizeof b);
+    b.frame = frame_idx;
+    if (memcpyed) {
+        if (n != 16ull + nbytes) return ZD_CORRUPT;
+        b.src = off + 16; b.csize = b.regen = nbytes; b.dst = 0; b.type = 0;
+        if (nbytes) raw.push_back(b);
+        return ZD_OK;
+    }
+    const uint64_t nblocks = ((uint64_t)nbytes + TILE_BM - 1) / TILE_BM;
+    if (16 + 4 * nblocks > n) return ZD_CORRUPT;
+    b.seq_tables = (uint8_t)(flags & 0x04u);
+    for (uint64_t t = 0; t < nblocks; ++t) {
+        const uint64_t bs = rd32(16 + 4 * t);
+        const uint32_t bsize = (uint32_t)std::min<uint64_t>((uint64_t)TILE_BM, nbytes - t * TILE_BM);
+        if (bs < 16 + 4 * nblocks || bs + 4 > n) return ZD_CORRUPT;
+        const uint64_t csize = rd32(bs);
+        if (csize == 0 || csize > bsize + bsize / 255u + 16u || bs + 4 + csize > n) return ZD_CORRUPT;
+        b.src = off + bs + 4; b.csize = (uint32_t)csize; b.dst = (uint32_t)(t * TILE_BM); b.regen = bsize; b.type = csize == bsize ? 0 : 2;
+        blocks.push_back(b);
+    }
+    return ZD_OK;
+}
 }  // namespace
 
 // slot, submit_only: rc_expand_frames = (RC_READ_SLOTS - its own resources -, false); rc_expand_frames_submit = (slot, true): returns once everything is queued.
 // coo: the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] | uint16 values[cap]
 // (k_expand_emit_b<true>): 10 bytes per set pixel and capacity instead of 24.
+// l2out (rc_expand_frames_l2, level 2 only): rows and columns alone (coo without the value array: 8 bytes per set pixel), and every frame's
+// statistics - the fields of its value stream - as uint16 into stats[stats_cap].  Without it a level-2 frame's statistics stream is
+// stepped over and the frame expands like a level-3 one.
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
-                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, bool coo = false)
+                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, bool coo = false,
+                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0)
 {
-    const uint64_t esz = coo ? 10 : 24;      // bytes per entry of the output
+    const uint64_t esz = l2out ? 8 : coo ? 10 : 24;      // bytes per entry of the output
     using namespace rc;
-    if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap)) return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
-    if (level != 1 && level != 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1 or 3");
+    if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
+        return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
+    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
     if (level == 1 && (bit_depth == 0 || bit_depth > 64)) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    if (op_mode != 0 && scheme != RC_SCHEME_LZ4 && scheme != RC_SCHEME_ZSTD)
+    if (l2out && level != 2) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2: reduction level 2");
+    if (l2out && (bit_depth < 8 || bit_depth > 16))
+        return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames_l2: bit_depth 8..16 (narrower fields: the stream's length does not give their count)");
+    if (op_mode != 0 && scheme != RC_SCHEME_LZ4 && scheme != RC_SCHEME_ZSTD && scheme != RC_SCHEME_BLOSC_LZ4)
         return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: scheme has no batched device decoder");
-    const uint32_t codec = op_mode == 0 ? EMIT_RAW : (scheme == RC_SCHEME_LZ4 ? EMIT_LZ4 : EMIT_ZSTD);
+    const uint32_t codec = op_mode == 0 ? EMIT_RAW : scheme;   // (EMIT_LZ4 / EMIT_ZSTD / EMIT_BLOSC are the scheme codes)
+    const bool vstream = level != 3;              // the frames carry a value stream (level 1: residuals, level 2: statistics) ...
+    const bool values = level == 1 || l2out;      // ... which this call decodes
+    const uint32_t klevel = level == 1 ? 1u : l2out ? 2u : 3u;   // what the expand kernels see: 2 = value 1, COO without the value array
     const uint64_t N = (uint64_t)nx * ny, nb = (N + 7) / 8, nb8 = (nb + 7) / 8;
     static const bool timing = getenv("RC_READ_TIMING") != nullptr;   // development: phase times on stderr
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -76,12 +134,25 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     uint64_t pv_stride = 16, total_in = 0;
     std::vector<uint64_t> foff(n);
     for (uint32_t f = 0; f < n; ++f) {
-        const uint32_t npk = level == 1 ? sizes[3 * f + 2] : 0;
+        const uint32_t npk = values ? sizes[3 * f + 2] : 0;
         pv_stride = std::max<uint64_t>(pv_stride, ((uint64_t)npk + 15) & ~15ull);
         foff[f] = total_in;
-        total_in += (uint64_t)sizes[3 * f] + (level == 1 ? sizes[3 * f + 1] : 0);
+        total_in += (uint64_t)sizes[3 * f] + (vstream ? sizes[3 * f + 1] : 0);
     }
     pv_stride += 16;
+    // level-2 statistics: frame f holds floor(8 * sizes[f][2] / bit_depth) of them (exact for fields of a byte or more)
+    uint64_t stats_total = 0;
+    uint32_t stats_max = 0;
+    std::vector<uint64_t> st_off(l2out ? n : 0);
+    for (uint32_t f = 0; f < n && l2out; ++f) {
+        const uint32_t c = (uint32_t)(8ull * sizes[3 * f + 2] / bit_depth);
+        st_off[f] = stats_total;
+        stats_total += c;
+        stats_max = std::max(stats_max, c);
+    }
+    const bool stats_short = stats_total > stats_cap;     // the synchronous call still counts (nnz_prefix stays valid), and writes nothing
+    if (stats_short && submit_only) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2_submit: stats holds fewer entries than the frames have statistics");
+    if (stats_short) { triplets = nullptr; cap = 0; }
     UtilScope util_scope;
     int r = util_scope.enter();
     if (r != RC_OK) return r;
@@ -99,13 +170,13 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     uint64_t *h_res = u.h_res.as<uint64_t>();
     hipStream_t s = u.stream;
     const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
-    const uint64_t out_bytes = (uint64_t)n * (bm_stride + (level == 1 ? pv_stride : 0)) + 64;
-    // head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n][pv_bytes n] [base2 2n][pv_base n][src_base n], the
+    const uint64_t out_bytes = (uint64_t)n * (bm_stride + (values ? pv_stride : 0)) + 64;
+    // head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n][pv_bytes n] [base2 2n][pv_base n][src_base n][st_base n], the
     // same layout in page-locked host memory and on the device: one copy
     const uint64_t ntab = codec == EMIT_ZSTD ? 2 * (uint64_t)n : 0;
     const uint64_t o_first = ntab * sizeof(ZdTables);
     const uint64_t o_base2 = (o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList) + (uint64_t)n * 4 + 15) & ~15ull;
-    const uint64_t sz_head = o_base2 + (uint64_t)n * 4 * 8;
+    const uint64_t sz_head = o_base2 + (uint64_t)n * 5 * 8;
     if ((r = u.d_data.ensure(U.dmem, total_in + 64)) != RC_OK || (r = u.d_streams.ensure(U.dmem, out_bytes)) != RC_OK ||
         (r = u.d_head.ensure(U.dmem, sz_head)) != RC_OK ||
         (r = u.d_counters.ensure(U.dmem, (uint64_t)n * nblk * 8 + (uint64_t)(2 * n + 2) * 8 + 64)) != RC_OK ||
@@ -148,7 +219,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     ZdFrameList *bm_list = reinterpret_cast<ZdFrameList *>(u.rd_head.p + o_first), *pv_list = bm_list + n, *raw_list = pv_list + n;
     ZdFrameList *cbm_list = raw_list + RC_READ_THREADS;
     uint32_t *pv_bytes = reinterpret_cast<uint32_t *>(cbm_list + n);
-    uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head.p + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n;
+    uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head.p + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n, *st_base = src_base + n;
     // c0, c_n: the frame's range in its thread's compact offset list (c_n blocks = c_n + 1 offsets); c_skips: tree_skip | seq_skip << 8
     struct FrameIndex { uint32_t bm0 = 0, bm_n = 0, pv0 = 0, pv_n = 0, thread = 0, c0 = 0, c_n = 0, c_skips = 0; int status = ZD_OK; const char *what = nullptr; };
     std::vector<FrameIndex> fi(n);
@@ -160,17 +231,18 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     // wake-up, not the walk - 30 us per frame - is what a static split waited for)
     std::atomic<uint32_t> next_frame{0};
     uint64_t max_npk = 0;
-    if (level == 1) for (uint32_t f = 0; f < n; ++f) max_npk = std::max<uint64_t>(max_npk, sizes[3 * f + 2]);
+    if (values) for (uint32_t f = 0; f < n; ++f) max_npk = std::max<uint64_t>(max_npk, sizes[3 * f + 2]);
     auto index_range = [&](uint32_t t) {
         if (t) (void)hipSetDevice(dev_now);   // (a worker thread: page-locked memory it allocates belongs to this device's context)
         auto &BM = u.rd_bm[t]; auto &PV = u.rd_pv[t]; auto &RAW = u.rd_raw[t]; auto &all = u.rd_tmp[t]; auto &OFF = u.rd_off[t];
         BM.clear(); PV.clear(); RAW.clear(); OFF.clear();
-        if (codec) {
+        if (codec == EMIT_BLOSC) BM.reserve(std::min<uint64_t>(n, 3ull * ((n + nthr - 1) / nthr)) * ((nb + TILE_BM - 1) / TILE_BM));   // (one entry per block)
+        else if (codec) {
             // what this thread is likely to collect (frames are claimed one at a time: up to three times its even share), reserved
             // in one allocation each; anything beyond still grows by doubling
             const uint64_t share = std::min<uint64_t>(n, 3ull * ((n + nthr - 1) / nthr));
             OFF.reserve(share * ((nb + TILE_BM - 1) / TILE_BM + 1));
-            if (level == 1 && codec == EMIT_ZSTD) PV.reserve(share * (max_npk / 1000 + 2));   // (value-stream chunks: PIX_CHUNK = 1008 bytes each)
+            if (values && codec == EMIT_ZSTD) PV.reserve(share * (max_npk / 1000 + 2));   // (value-stream chunks: PIX_CHUNK = 1008 bytes each)
         }
         // A binary-map stream whose blocks all regenerate TILE_BM bytes (the last one the rest), lie back to back and keep to one
         // set of sequence tables - what this library's encoders write - leaves one dword per block (k_bitmap_decode_c); any other
@@ -197,13 +269,13 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             if (f >= n) break;
             FrameIndex &F = fi[f];
             F.thread = t;
-            const uint64_t cb = sizes[3 * f], cp = level == 1 ? sizes[3 * f + 1] : 0, npk = level == 1 ? sizes[3 * f + 2] : 0;
+            const uint64_t cb = sizes[3 * f], cp = vstream ? sizes[3 * f + 1] : 0, npk = values ? sizes[3 * f + 2] : 0;
             const uint64_t o = foff[f];
             uint64_t got = 0;
             int rr = ZD_OK;
             F.bm0 = (uint32_t)BM.size(); F.pv0 = (uint32_t)PV.size();
             if (codec == EMIT_RAW) {
-                if (cb != nb || cp != npk) { F.status = ZD_CORRUPT; F.what = "rc_expand_frames: mode-0 sizes disagree with the frame shape"; continue; }
+                if (cb != nb || cp != (vstream ? sizes[3 * f + 2] : 0u)) { F.status = ZD_CORRUPT; F.what = "rc_expand_frames: mode-0 sizes disagree with the frame shape"; continue; }
                 ZdBlock b;
                 memset(&b, 0, sizeof b);
                 b.frame = f; b.src = o; b.csize = b.regen = (uint32_t)nb; b.dst = 0;
@@ -214,11 +286,15 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
                 rr = lz4_index_frame(walk, o, cb, f, TILE_BM, nb, all, all, &got);
                 if (rr == ZD_OK && got != nb) rr = ZD_CORRUPT;
                 if (rr == ZD_OK) route_bitmap(F, o, cb, 4, true);
-                if (rr == ZD_OK && level == 1) {
+                if (rr == ZD_OK && values) {
                     all.clear();   // (a value stream holds stored chunks only: a compressed block there is outside the subset)
                     rr = lz4_index_frame(walk, o + cb, cp, n + f, 0, npk, all, RAW, &got);
                     if (rr == ZD_OK && got != npk) rr = ZD_CORRUPT;
                 }
+            } else if (codec == EMIT_BLOSC) {
+                // (every block of the map to the frame's list - stored ones too: they are shuffled like the others; a memcpyed chunk to the copy list)
+                rr = blosc_index_stream(walk, o, cb, f, nb, true, BM, RAW);
+                if (rr == ZD_OK && values) rr = blosc_index_stream(walk, o + cb, cp, n + f, npk, false, BM, RAW);
             } else {
                 // (Compressed blocks to the stream's list, stored / RLE ones to the copy list, as the walk finds them)
                 struct Route {
@@ -239,7 +315,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
                 rr = zd_index_frame(walk, o, cb, f, TILE_BM, nb, all, bm_tab[f], &got);
                 if (rr == ZD_OK && got != nb) rr = ZD_CORRUPT;
                 if (rr == ZD_OK) route_bitmap(F, o, cb, 3, !(bm_tab[f].has & 4u));
-                if (rr == ZD_OK && level == 1) {
+                if (rr == ZD_OK && values) {
                     rr = zd_index_frame(walk, o + cb, cp, n + f, 0, npk, rp, pv_tab[f], &got);
                     if (rr == ZD_OK && got != npk) rr = ZD_CORRUPT;
                     if (rr == ZD_OK && rp.too_long) rr = ZD_FOREIGN;
@@ -270,7 +346,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         cbm_list[f].p = reinterpret_cast<const ZdBlock *>(u.rd_off[t].data() + F.c0); cbm_list[f].n = F.c_n; cbm_list[f].pad = F.c_skips;
         src_base[f] = foff[f];
         cbm_max = std::max(cbm_max, F.c_n);
-        pv_bytes[f] = level == 1 ? sizes[3 * f + 2] : 0;
+        pv_bytes[f] = values ? sizes[3 * f + 2] : 0;
+        st_base[f] = l2out ? st_off[f] : 0;
         base2[f] = (uint64_t)f * bm_stride;                                        // stored blocks: frames 0..n-1 = bitmaps,
         base2[n + f] = pv_base[f] = (uint64_t)n * bm_stride + (uint64_t)f * pv_stride;   // n..2n-1 = value streams (behind the bitmaps)
         bm_max = std::max(bm_max, F.bm_n);
@@ -284,7 +361,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const ZdFrameList *d_bm_list = reinterpret_cast<const ZdFrameList *>(u.d_head.p + o_first), *d_pv_list = d_bm_list + n, *d_raw_list = d_pv_list + n;
     const ZdFrameList *d_cbm_list = d_raw_list + RC_READ_THREADS;
     uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.d_head.p + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
-    uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.d_head.p + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n;
+    uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.d_head.p + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n, *d_st_base = d_src_base + n;
     HIP_TRY(hipMemcpyAsync(u.d_head.p, u.rd_head.p, sz_head, hipMemcpyHostToDevice, s));
     const double t_3 = now();
     // the value streams' chunks (few, long serial chains) decode next to the binary maps' blocks (many, short), on a second stream
@@ -297,10 +374,31 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         HIP_TRY(hipEventRecord(u.ev_b, u.stream2));
     }
     if (cbm_max) launch_bitmap_decode_compact(codec, d_data, d_cbm_list, d_src_base, n, cbm_max, d_bm_tab, U.zd_predef, d_out, d_base2, nb, d_err, s);
-    if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
+    if (n_bm && codec == EMIT_BLOSC) launch_blosc_decode_blocks(d_data, d_bm_list, n, bm_max, d_out, d_base2, d_err, s);
+    else if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
     launch_block_copy(d_data, d_raw_list, nthr, (uint32_t)n_raw, raw_max_regen, d_out, d_base2, s);
     if (n_pv && !serial) HIP_TRY(hipStreamWaitEvent(s, u.ev_b, 0));
     const uint8_t *d_bm = d_out, *d_pv = d_out + (uint64_t)n * bm_stride;
+    // level-2 statistics: unpacked where the caller wants them when the device can write there, otherwise staged - a submitted batch's
+    // page-locked destination gets ONE asynchronous copy of all of them (their number is known here), the synchronous call copies at its end
+    uint16_t *stats_dev = stats;
+    bool stats_staged = false;
+    if (l2out && !stats_short && stats_total) {
+        if (!is_device_ptr(stats)) {
+            if (submit_only) {
+                hipPointerAttribute_t a;
+                if (hipPointerGetAttributes(&a, stats) != hipSuccess || a.type != hipMemoryTypeHost) {
+                    (void)hipGetLastError();
+                    return bail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: stats must be device or page-locked host memory");
+                }
+            }
+            if ((r = u.d_stats.ensure(U.dmem, stats_total * 2 + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+            stats_dev = u.d_stats.as<uint16_t>();
+            stats_staged = true;
+        }
+        launch_stats_unpack(d_pv, pv_stride, d_pv_bytes, d_st_base, n, stats_max, bit_depth, stats_dev, d_err, s);
+        if (stats_staged && submit_only) HIP_TRY(hipMemcpyAsync(stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
+    }
     // Triplets wanted in DEVICE memory: the emit kernel is queued right behind the count - no host round trip in between; the kernel that
     // finishes the count (k_expand_bases) checks what the host otherwise would (total <= cap, value streams long enough) and the emit
     // kernel writes nothing once any check or decoder has raised *d_err.  Host memory: the output is staged, so its size must be known
@@ -321,8 +419,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     }
     if (submit_only && !dev_out) return bail(RC_ERR_BAD_ARG, "rc_expand_frames_submit: triplets must be device or page-locked host memory");
     if (dev_out) {
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, level, cap, d_err);
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, cap, triplets, s, d_err, coo);
+        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, cap, d_err);
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, triplets, s, d_err, coo);
     } else
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s);
     HIP_TRY(hipGetLastError());
@@ -342,6 +440,11 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const double t_4 = now();
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     const uint64_t total = nnz_prefix[n];
+    if (stats_short) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2: stats holds fewer entries than the frames have statistics");
+    if (stats_staged) {
+        HIP_TRY(hipMemcpyAsync(stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
     if (!triplets) return RC_OK;
     if (total > cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
     if (level == 1)
@@ -358,18 +461,18 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (coo) {
         // the three arrays keep the caller's stride (cap) on the device as in the caller's buffer: three copies of `total` entries
         if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) return r;
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, cap, u.d_triplets.p, s, nullptr, true);
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, u.d_triplets.p, s, nullptr, true);
         HIP_TRY(hipGetLastError());
         uint8_t *h = reinterpret_cast<uint8_t *>(triplets);
         HIP_TRY(hipMemcpyAsync(h, u.d_triplets.p, total * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h + cap * 4, u.d_triplets.p + cap * 4, total * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * 2, hipMemcpyDeviceToHost, s));
+        if (!l2out) HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * 2, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return RC_OK;
     }
     if ((r = u.d_triplets.ensure(U.dmem, total * 24)) != RC_OK) return r;
     uint64_t *d_trip = u.d_triplets.as<uint64_t>();
-    launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, level, total, d_trip, s);
+    launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, total, d_trip, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(triplets, d_trip, total * 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -407,6 +510,23 @@ RC_EXPORT int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t n
     if (!coo_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo_submit: the output must be device or page-locked host memory");
     if (level == 1 && bit_depth > 16) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)");
     return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, true);
+}
+
+RC_EXPORT int rc_expand_frames_l2(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                  const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *rc, uint64_t cap, uint16_t *stats, uint64_t stats_cap)
+{
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(rc), cap, true, true,
+                      stats, stats_cap);
+}
+
+RC_EXPORT int rc_expand_frames_l2_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme,
+                                         const uint8_t *data, const uint32_t *sizes, uint32_t n, void *rc_dev, uint64_t cap, uint16_t *stats_dev,
+                                         uint64_t stats_cap)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: slot 0 or 1");
+    if (!rc_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: the output must be device or page-locked host memory");
+    return expand_run(slot, true, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(rc_dev), cap, true, true, stats_dev,
+                      stats_cap);
 }
 
 RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)

@@ -248,7 +248,7 @@ class BatchedAccess:
         h = self._header
         return int(h['reduction_level']) == 1 and int(h['target_bit_depth']) > 16
 
-    def get_frames_triplets(self, z0, n, out=None, coo=False):
+    def get_frames_triplets(self, z0, n, out=None, coo=False, device_blosc=False):
         """Frames z0 .. z0+n-1 of a merged file - or records z0 .. z0+n-1 of a part file, whose frame ids are part_frame_ids[z] - in ONE
         device call (rc_expand_frames): both streams of every frame are
         decompressed and expanded on the GPU without a host round trip in between.  Returns (nnz_prefix uint64[n+1],
@@ -259,17 +259,20 @@ class BatchedAccess:
         triplets are then written into that page-locked buffer (grown when too small) and the returned array is a view of it,
         valid until the next call with the same holder.
         coo=True: instead of the triplet rows, (rows int32[total], columns int32[total], values uint16[total]) - the arrays of the COO
-        matrices the frame-at-a-time calls return, 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo)."""
+        matrices the frame-at-a-time calls return, 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo).
+        device_blosc=True: a blosc-LZ4 file (compression_scheme 8) at level 1 or 3 goes through the device call as well (the batched
+        blosc decoder of rc_expand_frames).  A switch, and off by default, because the path such files take through this call is part of
+        its tested behaviour: they read frame by frame, and callers - the read-ahead among them - see 'per-frame' in last_batch_path."""
         h = self._header
         if coo and self._wide_values():
-            prefix, trip = self.get_frames_triplets(z0, n, out=out, coo=False)
+            prefix, trip = self.get_frames_triplets(z0, n, out=out, coo=False, device_blosc=device_blosc)
             return prefix, _split_wide(trip)
         dst = _BatchOut(coo, out)
         nz = self._batch_frames()
         if z0 < 0 or n <= 0 or z0 + n > nz:
             raise ValueError('Requested frame index is greater than number of frames in dataset')
         level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        fast = level in (1, 3) and (mode == 0 or scheme in (1, 2))
+        fast = level in (1, 3) and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc))
         host_only = level in (1, 3) and mode == 1 and scheme in (0, 4, 5)   # zlib / bz2 / lzma: stock decoder on the thread pool, ONE device expand
         if fast or host_only:
             sizes = np.zeros((n, 3), np.uint32)
@@ -312,7 +315,7 @@ class BatchedAccess:
             # the file is really damaged.
             if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
                 _lib.check(st, 'rc_expand_frames')
-            if mode == 1:
+            if mode == 1 and scheme != 8:
                 res = self._foreign_batch_triplets(z0, n, blob, sizes, dst)
                 if res is not None:
                     self._note_batch_end(z0 + n)
@@ -534,19 +537,19 @@ class BatchedAccess:
                 except Exception:         # (a generator finalised while the interpreter shuts down)
                     pass
 
-    def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False):
-        """The caller's own streaming iterator (documented at _iter_frames_impl).  The read-ahead under get_frame / get_next_frame keeps
+    def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False, device_blosc=False):
+        """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc: as in get_frames_triplets).  The read-ahead under get_frame / get_next_frame keeps
         an iterator of its own alive on the same page-locked buffers, with one batch queued on the device: it is ended first (its queued
         batch waited for, the window it serves forgotten), and it stays off while this generator lives."""
         self._ra = None
         self._close_ra_iter()
         self._user_iters += 1
         try:
-            yield from self._iter_frames_impl(z0, n, batch, coo)
+            yield from self._iter_frames_impl(z0, n, batch, coo, device_blosc)
         finally:
             self._user_iters -= 1
 
-    def _iter_frames_impl(self, z0=0, n=None, batch=64, coo=False):
+    def _iter_frames_impl(self, z0=0, n=None, batch=64, coo=False, device_blosc=False):
         """Streams frames z0 .. z0+n-1 of a merged file (records z0 .. of a part file: the reference's own read test sums a part file's
         frames one get_next_frame at a time, tests/recode_v1_read_test.py:9-21) through the batched device reader, two batches in flight
         (rc_expand_frames_submit / _wait): while the device decodes one batch, the next one is read from the file, its block headers
@@ -557,7 +560,7 @@ class BatchedAccess:
         triplet rows - 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo_submit)."""
         h = self._header
         if coo and self._wide_values():   # values beyond uint16: the device's COO layout does not hold them - triplets, split on the host
-            for a, prefix, trip in self._iter_frames_impl(z0, n, batch, coo=False):
+            for a, prefix, trip in self._iter_frames_impl(z0, n, batch, coo=False, device_blosc=device_blosc):
                 yield a, prefix, _split_wide(trip)
             return
         nz = self._batch_frames()
@@ -570,10 +573,10 @@ class BatchedAccess:
         if level in (1, 3) and mode == 1 and (scheme in (0, 4, 5) or (scheme in (1, 2) and self._foreign_file)):
             yield from self._iter_host_decoded(z0, n, batch, coo)  # stock decoders on the pool, one batch ahead of the device
             return
-        if not (level == 1 and (mode == 0 or scheme in (1, 2))):
+        if not (level == 1 and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc))):
             for a in starts:
                 k = min(batch, z0 + n - a)
-                yield (a,) + self.get_frames_triplets(a, k, coo=coo)
+                yield (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)
             return
         L = _lib.lib()
         geom = (int(h['nx']), int(h['ny']), d, level, mode, scheme)
@@ -617,11 +620,11 @@ class BatchedAccess:
         def finish(job):
             a, k, slot, cap = job
             if cap is None:
-                return (a,) + self.get_frames_triplets(a, k, coo=coo)       # (sets last_batch_path itself)
+                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)       # (sets last_batch_path itself)
             prefix = np.zeros(k + 1, np.uint64)
             st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
             if st == _lib.RC_ERR_CORRUPT:                     # the stock decoder is the judge
-                return (a,) + self.get_frames_triplets(a, k, coo=coo)
+                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)
             _lib.check(st, 'rc_expand_frames_wait')
             total = int(prefix[k])
             trip = _BatchOut.views(bufs[2 + slot].array, cap, total, coo)
@@ -645,6 +648,188 @@ class BatchedAccess:
                 yield res
         finally:
             # a consumer that stops early leaves a batch queued: wait for it before its buffers go away
+            if queued is not None and queued[3] is not None:
+                try:
+                    L.rc_expand_frames_wait(queued[2], _lib.ptr(np.zeros(queued[1] + 1, np.uint64)))
+                except Exception:         # (a generator finalised while the interpreter shuts down)
+                    pass
+
+    # ---- level 2 in batches: set pixels and summary statistics (rc_expand_frames_l2) ------------------------------------------
+    def _l2_sizes(self, a, k):
+        """(sizes uint32[k][3], bytes of the k frames' data, statistics prefix int64[k+1]) of frames a .. a+k-1 of a level-2 file"""
+        d = int(self._header['target_bit_depth'])
+        sizes = np.zeros((k, 3), np.uint32)
+        for j in range(k):
+            md = self._frame_metadata[a + j]
+            sizes[j, 0], sizes[j, 1] = self._stream_sizes(md)
+            sizes[j, 2] = int(md['bytes_in_packed_summary_stats'])
+        sp = np.zeros(k + 1, np.int64)
+        np.cumsum(sizes[:, 2].astype(np.int64) * 8 // d, out=sp[1:])
+        return sizes, int(self._seek_table[a:a + k, 0].sum()), sp
+
+    def _l2_on_device(self):
+        h = self._header
+        mode, scheme = int(h['rc_operation_mode']), int(h['compression_scheme'])
+        return 8 <= int(h['target_bit_depth']) <= 16 and (mode == 0 or scheme in (1, 2, 8)) and not (mode == 1 and self._foreign_file)
+
+    def _l2_per_frame(self, z0, n):
+        """get_frames_l2's result from the frame-at-a-time path (_get_frame_sparse): fields narrower than a byte, host-only schemes,
+        foreign or damaged streams - the stock path is the judge"""
+        self.last_batch_path = 'per-frame'
+        rows, cols, stats = [], [], []
+        prefix, sp = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.int64)
+        keep = self._fp.tell()
+        for i in range(n):
+            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0)
+            m, st = self._get_frame_sparse(self._frame_metadata[z0 + i])
+            if m is not None and m.nnz:
+                rows.append(m.row.astype(np.int32))
+                cols.append(m.col.astype(np.int32))
+            if st is not None:
+                stats.append(np.asarray(st, self._numpy_dtype))
+            prefix[i + 1] = prefix[i] + (m.nnz if m is not None else 0)
+            sp[i + 1] = sp[i] + (len(st) if st is not None else 0)
+        if self._is_intermediate:
+            self._fp.seek(keep, 0)
+        else:
+            self._note_batch_end(z0 + n)
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+        return prefix, cat(rows, np.int32), cat(cols, np.int32), sp, cat(stats, self._numpy_dtype)
+
+    def get_frames_l2(self, z0, n):
+        """Frames z0 .. z0+n-1 of a LEVEL-2 file (records of a part file, indexed like get_frames_triplets') in one device call
+        (rc_expand_frames_l2): both streams of every frame decoded on the GPU, the binary maps expanded and the statistics unpacked there.
+        Returns (nnz_prefix uint64[n+1], rows int32[total], columns int32[total], stats_prefix int64[n+1], stats): frame i's set pixels
+        are rows / columns[nnz_prefix[i]:nnz_prefix[i+1]] in row-major order (every value is 1), its summary statistics - one per
+        connected component, in label order, in the file's dtype as get_frame returns them - stats[stats_prefix[i]:stats_prefix[i+1]].
+        Falls back to the frame-at-a-time path (last_batch_path says which) for fields narrower than 8 bits, host-only schemes and
+        streams the device decoders refuse."""
+        h = self._header
+        if int(h['reduction_level']) != 2:
+            raise ValueError('get_frames_l2 reads reduction level 2 files')
+        nz = self._batch_frames()
+        if z0 < 0 or n <= 0 or z0 + n > nz:
+            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        if not self._l2_on_device():
+            return self._l2_per_frame(z0, n)
+        sizes, total, sp = self._l2_sizes(z0, n)
+        if self._pin_blob is None or self._pin_blob.nbytes < total:
+            if self._pin_blob is not None:
+                self._pin_blob.close()
+            self._pin_blob = _lib.PinnedBuffer(max(int(total * 1.25), 1 << 20))
+        blob = self._pin_blob.array[:total]
+        self._read_batch_into(blob, z0, n)
+        L = _lib.lib()
+        geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']))
+        codec = (int(h['rc_operation_mode']), int(h['compression_scheme']))
+        src = (_lib.ptr(blob), _lib.ptr(sizes), n)
+        prefix = np.zeros(n + 1, np.uint64)
+        st = L.rc_expand_frames(*geom, 2, *codec, *src, _lib.ptr(prefix), None, 0)          # the counting call sizes rows / columns
+        if st == _lib.RC_OK:
+            cap, ns = max(int(prefix[n]), 1), int(sp[n])
+            rc, stats = np.empty(2 * cap, np.int32), np.empty(max(ns, 1), np.uint16)
+            st = L.rc_expand_frames_l2(*geom, *codec, *src, _lib.ptr(prefix), _lib.ptr(rc), cap, _lib.ptr(stats), ns)
+        if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+            return self._l2_per_frame(z0, n)
+        _lib.check(st, 'rc_expand_frames_l2')
+        self._note_batch_end(z0 + n)
+        self.last_batch_path = 'device'
+        tot = int(prefix[n])
+        return prefix, rc[:tot], rc[cap:cap + tot], sp, stats[:ns].astype(self._numpy_dtype, copy=False)
+
+    def iter_frames_l2(self, z0=0, n=None, batch=64):
+        """Streams a level-2 file through rc_expand_frames_l2_submit / rc_expand_frames_wait, two batches in flight like
+        iter_frames_triplets: yields (first frame index, nnz_prefix, rows, columns, stats_prefix, stats) per batch of up to `batch` frames
+        (get_frames_l2's items).  rows / columns / stats are copies of their own.  A level-2 batch's set pixels cannot be bounded from
+        the metadata, so the first batch is counted on the device and every later one is given the room the densest batch so far
+        needed per frame plus a quarter; a batch that still does not fit - or that the device path does not take - goes through
+        get_frames_l2."""
+        h = self._header
+        if int(h['reduction_level']) != 2:
+            raise ValueError('iter_frames_l2 reads reduction level 2 files')
+        nz = self._batch_frames()
+        n = nz - z0 if n is None else n
+        if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
+            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        starts = list(range(z0, z0 + n, batch))
+        if not self._l2_on_device():
+            for a in starts:
+                yield (a,) + self.get_frames_l2(a, min(batch, z0 + n - a))
+            return
+        self._ra = None
+        self._close_ra_iter()
+        L = _lib.lib()
+        geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['rc_operation_mode']), int(h['compression_scheme']))
+        if self._stream_bufs is None:
+            self._stream_bufs = [None, None, None, None]
+        if self._l2_bufs is None:
+            self._l2_bufs = [None, None]                       # page-locked statistics of the two slots
+        bufs, sbufs = self._stream_bufs, self._l2_bufs
+        per_frame = [None]                                     # set pixels per frame of the densest batch so far
+
+        def pinned(buf, nbytes):
+            if buf is None or buf.nbytes < nbytes:
+                if buf is not None:
+                    buf.close()
+                buf = _lib.PinnedBuffer(max(int(nbytes * 1.25), 1 << 20))
+            return buf
+
+        def submit(i):
+            a = starts[i]
+            k = min(batch, z0 + n - a)
+            slot = i & 1
+            sizes, total, sp = self._l2_sizes(a, k)
+            bufs[slot] = pinned(bufs[slot], total + 64)
+            blob = bufs[slot].array[:total]
+            self._read_batch_into(blob, a, k)
+            if per_frame[0] is None:
+                prefix = np.zeros(k + 1, np.uint64)
+                st = L.rc_expand_frames(*geom[:3], 2, *geom[3:], _lib.ptr(blob), _lib.ptr(sizes), k, _lib.ptr(prefix), None, 0)
+                if st != _lib.RC_OK:
+                    return (a, k, slot, None, sp)
+                cap = max(int(prefix[k]), 1)
+            else:
+                cap = int(per_frame[0] * k * 1.25) + 1024
+            ns = int(sp[k])
+            bufs[2 + slot] = pinned(bufs[2 + slot], 8 * cap)
+            sbufs[slot] = pinned(sbufs[slot], 2 * max(ns, 1))
+            st = L.rc_expand_frames_l2_submit(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap, sbufs[slot]._p, ns)
+            if st != _lib.RC_OK:
+                # outside the device subset, or ANOTHER iterator holds the slot: get_frames_l2 has resources of its own and knows the fallback
+                if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT) and not (st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error()):
+                    _lib.check(st, 'rc_expand_frames_l2_submit')
+                return (a, k, slot, None, sp)
+            return (a, k, slot, cap, sp)
+
+        def finish(job):
+            a, k, slot, cap, sp = job
+            if cap is None:
+                return (a,) + self.get_frames_l2(a, k)
+            prefix = np.zeros(k + 1, np.uint64)
+            st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
+            if st == _lib.RC_ERR_OUT_TOO_SMALL:
+                per_frame[0] = max(per_frame[0] or 0, int(prefix[k]) / k)
+            if st in (_lib.RC_ERR_CORRUPT, _lib.RC_ERR_OUT_TOO_SMALL):
+                return (a,) + self.get_frames_l2(a, k)
+            _lib.check(st, 'rc_expand_frames_wait')
+            tot, ns = int(prefix[k]), int(sp[k])
+            per_frame[0] = max(per_frame[0] or 0, tot / k)
+            rc = bufs[2 + slot].array[:8 * cap].view(np.int32)
+            self.last_batch_path = 'device'
+            return (a, prefix, rc[:tot].copy(), rc[cap:cap + tot].copy(), sp,
+                    sbufs[slot].array[:2 * ns].view(np.uint16).astype(self._numpy_dtype))
+        queued = None
+        self._user_iters += 1
+        try:
+            queued = submit(0) if starts else None
+            for i in range(len(starts)):
+                job = queued
+                queued = submit(i + 1) if i + 1 < len(starts) else None
+                res = finish(job)
+                self._note_batch_end(job[0] + job[1])
+                yield res
+        finally:
+            self._user_iters -= 1
             if queued is not None and queued[3] is not None:
                 try:
                     L.rc_expand_frames_wait(queued[2], _lib.ptr(np.zeros(queued[1] + 1, np.uint64)))

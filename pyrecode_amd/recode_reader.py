@@ -44,6 +44,7 @@ class ReCoDeReader(BatchedAccess):
         # batched access (rc_expand_frames & co.): buffers, pools and bookkeeping, created on first use and released by close()
         self._pin_blob = None            # page-locked image of a batch's file bytes (get_frames_triplets)
         self._stream_bufs = None         # [blob 0, blob 1, triplets 0, triplets 1] of the streaming iterator
+        self._l2_bufs = None             # page-locked statistics of iter_frames_l2's two slots
         self._read_pool = None           # a few threads for page-cache reads
         self._decode_pool = None         # stock decoders of the Python level (bz2, lzma; zstd / LZ4 without the shared libraries)
         self._decode_coord = None        # the thread that decodes one batch ahead (_iter_host_decoded)
@@ -165,10 +166,10 @@ class ReCoDeReader(BatchedAccess):
         if self._pin_blob is not None:
             self._pin_blob.close()
             self._pin_blob = None
-        for b in self._stream_bufs or []:
+        for b in (self._stream_bufs or []) + (self._l2_bufs or []):
             if b is not None:
                 b.close()
-        self._stream_bufs = None
+        self._stream_bufs = self._l2_bufs = None
         if self._read_pool is not None:
             self._read_pool.shutdown(wait=True)
             self._read_pool = None
