@@ -304,6 +304,16 @@ int rc_expand_frames_coo(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t 
                          const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap);
 int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
                                 uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap);
+/* The COO pair for files whose values do not fit 16 bits (uint32 sources, 17..32-bit fields): the reference's reader gives the matrix the
+ * data type target_bit_depth maps to (recode_reader.py:464-471 with misc.py:41-52), uint32 for such files, and so does
+ * `coo` = int32 rows[cap] | int32 columns[cap] | uint32 values[cap] (12 * cap bytes, 12 instead of 24 per set pixel over the link).
+ * bit_depth 1..32 at reduction level 1 (narrower files come out as the _coo values widened; above 32: RC_ERR_BAD_ARG); levels 3 and 2
+ * as for rc_expand_frames_coo, value 1 in the wider array.  Everything else - arguments, host / device / page-locked outputs, status
+ * codes, rc_expand_frames_wait for the _submit form - as for the _coo pair. */
+int rc_expand_frames_coo32(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                           const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap);
+int rc_expand_frames_coo32_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
+                                  uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap);
 /* A batch of reduction-level-2 frames in full: the set pixels AND every frame's summary statistics.  Replaces, for n frames at once, the
  * level-2 branch of ReCoDeReader._get_frame_sparse (pyrecode/recode_reader.py:413-440 for the pixels, :473-481 for the statistics, whose
  * unpacker is c_extensions/reader.h:74-99 - intended semantics) and the de_compress calls in front of it (:393-411).

@@ -11,9 +11,10 @@ void launch_expand_emit(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, ui
 void launch_expand_batch_count(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t n, uint32_t *blk_cnt, uint32_t *blk_off,
                                uint64_t *frame_nnz, uint64_t *frame_base, hipStream_t s, const uint32_t *pv_bytes = nullptr, uint32_t d = 0,
                                uint32_t level = 0, uint64_t cap = 0, int *err = nullptr);
+// coo_value_bytes: 0 = uint64 (row, col, value) rows; 2 / 4 = int32 rows[cap] | int32 columns[cap] | uint16 / uint32 values[cap]
 void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                               const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d,
-                              uint32_t level, uint64_t cap, void *out, hipStream_t s, const int *err = nullptr, bool coo = false);
+                              uint32_t level, uint64_t cap, void *out, hipStream_t s, const int *err = nullptr, uint32_t coo_value_bytes = 0);
 // rc_zstd_dec.hip: block decoders of the batched reader
 void launch_block_decode(int codec, int row, const uint8_t *data, const void *frame_lists, uint32_t nframes, uint32_t max_blocks_per_frame,
                          const void *tables, const void *predef, uint8_t *out, const uint64_t *out_base, int *err, hipStream_t s,

@@ -164,24 +164,26 @@ __global__ __launch_bounds__(WG) void k_expand_bases(const uint64_t *__restrict_
 // 2^32 pixels: nx, ny <= 65 535), the pixels behind it step the column.
 constexpr uint32_t EMIT_STAGE = 1024;   // triplets
 // COO = false: out = uint64_t[cap][3], the reference's (row, col, value) rows (pyrecode.cpp:95-119).
-// COO = true: out = int32 rows[cap] | int32 columns[cap] | uint16 values[cap] - the three arrays of the scipy COO matrix the reference's
-// reader wraps the rows into (recode_reader.py:466-469), 10 instead of 24 bytes per set pixel on the link and no split on the host.
+// COO = true: out = int32 rows[cap] | int32 columns[cap] | VT values[cap] - the three arrays of the scipy COO matrix the reference's
+// reader wraps the rows into (recode_reader.py:466-469), 10 (VT = uint16_t) or 12 (uint32_t: files of 17..32-bit values, whose matrices
+// carry uint32 data, recode_reader.py:464-471) instead of 24 bytes per set pixel on the link and no split on the host.
 // COO with level 2 (rc_expand_frames_l2): rows and columns only - every value is 1 and the caller's buffer ends behind the columns.
-template <bool COO>
+template <bool COO, class VT = uint16_t>
 __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict__ bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx,
                                                         uint32_t nblk, const uint32_t *__restrict__ blk_off, const uint64_t *__restrict__ frame_base,
                                                         const uint8_t *__restrict__ pv, uint64_t pv_stride, const uint32_t *__restrict__ pv_bytes,
                                                         uint32_t d, uint32_t level, uint64_t cap, void *__restrict__ out_any,
                                                         const int *__restrict__ err)
 {
+    constexpr bool WIDE = COO && sizeof(VT) == 4;
     __shared__ uint32_t sm[WAVES + 1];
     __shared__ uint64_t s_trip[COO ? 1 : 3 * EMIT_STAGE];
     __shared__ uint32_t s_row[COO ? EMIT_STAGE : 1], s_col[COO ? EMIT_STAGE : 1];
-    __shared__ uint16_t s_val[COO ? EMIT_STAGE : 1];
+    __shared__ VT s_val[COO ? EMIT_STAGE : 1];
     if (err && *err) return;   // (workgroup-uniform: k_expand_bases, a decoder or nobody has set it before this kernel started)
     uint64_t *out = static_cast<uint64_t *>(out_any);
     int32_t *o_row = static_cast<int32_t *>(out_any), *o_col = o_row + cap;
-    uint16_t *o_val = reinterpret_cast<uint16_t *>(o_col + cap);
+    VT *o_val = reinterpret_cast<VT *>(o_col + cap);
     const uint32_t f = blockIdx.y;
     const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
     uint64_t bits = expand_word(bm + f * bm_stride, nb8, N, i);
@@ -203,14 +205,25 @@ __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict_
             prev = b;
             while (col >= nx) { col -= nx; ++row; }
             const uint64_t rank = wg_rank + r;
-            const uint64_t val = level != 1 ? 1ull : ((d == 16 && 2 * rank + 2 <= pix_bytes) ? (uint64_t)reinterpret_cast<const uint16_t *>(pix)[rank]   // (value streams are 16-byte aligned)
-                                                                                                : read_field(pix, pix_bytes, rank, d));
+            uint64_t val;
+            // Fields of 17..32 bits that lie inside the stream, from dwords (value streams are 16-byte aligned): d = 32 is the dword itself;
+            // a narrower field lies inside the two dwords at its bit position.  Its last bit is below 8 * pix_bytes, so the first dword
+            // starts below pix_bytes and the second one ends before pix_bytes + 8 - inside the frame's slot, which is the longest stream
+            // rounded up to 16 bytes plus 16 more, zeroed behind the stream (rc_reader.hip: pv_stride, out_bytes; as k_stats_unpack).
+            if (WIDE && level == 1 && d == 32 && 4 * rank + 4 <= pix_bytes) val = reinterpret_cast<const uint32_t *>(pix)[rank];
+            else if (WIDE && level == 1 && d > 16 && d < 32 && rank * d + d <= 8 * pix_bytes) {
+                const uint64_t bit = rank * d;
+                const uint32_t *p = reinterpret_cast<const uint32_t *>(pix) + (bit >> 5);
+                val = (((uint64_t)p[0] | ((uint64_t)p[1] << 32)) >> (bit & 31u)) & ((1u << d) - 1u);
+            } else
+                val = level != 1 ? 1ull : ((d == 16 && 2 * rank + 2 <= pix_bytes) ? (uint64_t)reinterpret_cast<const uint16_t *>(pix)[rank]   // (value streams are 16-byte aligned)
+                                                                                    : read_field(pix, pix_bytes, rank, d));
             if (staged) {
-                if (COO) { s_row[r] = row; s_col[r] = col; s_val[r] = (uint16_t)val; }
+                if (COO) { s_row[r] = row; s_col[r] = col; s_val[r] = (VT)val; }
                 else { s_trip[3 * r] = row; s_trip[3 * r + 1] = col; s_trip[3 * r + 2] = val; }
             } else {
                 if (base + rank >= cap) break;
-                if (COO) { o_row[base + rank] = (int32_t)row; o_col[base + rank] = (int32_t)col; if (level != 2) o_val[base + rank] = (uint16_t)val; }
+                if (COO) { o_row[base + rank] = (int32_t)row; o_col[base + rank] = (int32_t)col; if (level != 2) o_val[base + rank] = (VT)val; }
                 else {
                     uint64_t *o = out + 3 * (base + rank);
                     o[0] = row; o[1] = col; o[2] = val;
@@ -237,12 +250,16 @@ void launch_expand_batch_count(const uint8_t *bm, uint64_t bm_stride, uint64_t n
     hipLaunchKernelGGL(k_expand_scan_b, dim3(n), dim3(WG), 0, s, blk_cnt, blk_off, nblk, frame_nnz);
     hipLaunchKernelGGL(k_expand_bases, dim3(1), dim3(WG), 0, s, frame_nnz, frame_base, n, pv_bytes, d, level, cap, err);
 }
+// coo_value_bytes: 0 = triplet rows, 2 / 4 = the COO arrays with uint16 / uint32 values
 void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                               const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d,
-                              uint32_t level, uint64_t cap, void *out, hipStream_t s, const int *err, bool coo)
+                              uint32_t level, uint64_t cap, void *out, hipStream_t s, const int *err, uint32_t coo_value_bytes)
 {
     const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
-    if (coo)
+    if (coo_value_bytes == 4)
+        hipLaunchKernelGGL((k_expand_emit_b<true, uint32_t>), dim3(nblk, n), dim3(WG), 0, s, bm, bm_stride, nb8, N, nx, nblk, blk_off, frame_base, pv,
+                           pv_stride, pv_bytes, d, level, cap, out, err);
+    else if (coo_value_bytes)
         hipLaunchKernelGGL(k_expand_emit_b<true>, dim3(nblk, n), dim3(WG), 0, s, bm, bm_stride, nb8, N, nx, nblk, blk_off, frame_base, pv, pv_stride,
                            pv_bytes, d, level, cap, out, err);
     else

@@ -101,16 +101,17 @@ int blosc_index_stream(const uint8_t *base, uint64_t off, uint64_t n, uint32_t f
 }  // namespace
 
 // slot, submit_only: rc_expand_frames = (RC_READ_SLOTS - its own resources -, false); rc_expand_frames_submit = (slot, true): returns once everything is queued.
-// coo: the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] | uint16 values[cap]
-// (k_expand_emit_b<true>): 10 bytes per set pixel and capacity instead of 24.
+// coo (bytes of a value, 0 = not): the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] |
+// uint16 (2, rc_expand_frames_coo) or uint32 (4, rc_expand_frames_coo32) values[cap] (k_expand_emit_b<true, ...>): 10 or 12 bytes per set
+// pixel and capacity instead of 24.
 // l2out (rc_expand_frames_l2, level 2 only): rows and columns alone (coo without the value array: 8 bytes per set pixel), and every frame's
 // statistics - the fields of its value stream - as uint16 into stats[stats_cap].  Without it a level-2 frame's statistics stream is
 // stepped over and the frame expands like a level-3 one.
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
-                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, bool coo = false,
+                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
                       bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0)
 {
-    const uint64_t esz = l2out ? 8 : coo ? 10 : 24;      // bytes per entry of the output
+    const uint64_t esz = l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
     if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
         return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
@@ -461,12 +462,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (coo) {
         // the three arrays keep the caller's stride (cap) on the device as in the caller's buffer: three copies of `total` entries
         if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) return r;
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, u.d_triplets.p, s, nullptr, true);
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, u.d_triplets.p, s, nullptr, coo);
         HIP_TRY(hipGetLastError());
         uint8_t *h = reinterpret_cast<uint8_t *>(triplets);
         HIP_TRY(hipMemcpyAsync(h, u.d_triplets.p, total * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h + cap * 4, u.d_triplets.p + cap * 4, total * 4, hipMemcpyDeviceToHost, s));
-        if (!l2out) HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * 2, hipMemcpyDeviceToHost, s));
+        if (!l2out) HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * coo, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return RC_OK;
     }
@@ -500,7 +501,7 @@ RC_EXPORT int rc_expand_frames_coo(uint32_t nx, uint32_t ny, uint32_t bit_depth,
                                    const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap)
 {
     if (level == 1 && bit_depth > 16) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)");
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(coo), cap, true);
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(coo), cap, 2);
 }
 
 RC_EXPORT int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
@@ -509,13 +510,29 @@ RC_EXPORT int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t n
     if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo_submit: slot 0 or 1");
     if (!coo_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo_submit: the output must be device or page-locked host memory");
     if (level == 1 && bit_depth > 16) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)");
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, true);
+    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, 2);
+}
+
+RC_EXPORT int rc_expand_frames_coo32(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                     const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap)
+{
+    if (level == 1 && bit_depth > 32) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32: values are uint32 (bit_depth <= 32)");
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(coo), cap, 4);
+}
+
+RC_EXPORT int rc_expand_frames_coo32_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
+                                            uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32_submit: slot 0 or 1");
+    if (!coo_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32_submit: the output must be device or page-locked host memory");
+    if (level == 1 && bit_depth > 32) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32: values are uint32 (bit_depth <= 32)");
+    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, 4);
 }
 
 RC_EXPORT int rc_expand_frames_l2(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                   const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *rc, uint64_t cap, uint16_t *stats, uint64_t stats_cap)
 {
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(rc), cap, true, true,
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(rc), cap, 2, true,
                       stats, stats_cap);
 }
 
@@ -525,7 +542,7 @@ RC_EXPORT int rc_expand_frames_l2_submit(uint32_t slot, uint32_t nx, uint32_t ny
 {
     if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: slot 0 or 1");
     if (!rc_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: the output must be device or page-locked host memory");
-    return expand_run(slot, true, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(rc_dev), cap, true, true, stats_dev,
+    return expand_run(slot, true, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(rc_dev), cap, 2, true, stats_dev,
                       stats_cap);
 }
 

@@ -12,21 +12,27 @@ from . import _lib
 from .misc import effective_cpus
 
 
-def _split_wide(trip):
-    """uint64 triplet rows -> the COO layout's three arrays with uint32 values (files whose values do not fit the device's uint16 COO form)."""
-    trip = np.asarray(trip).reshape(-1, 3)
-    return trip[:, 0].astype(np.int32), trip[:, 1].astype(np.int32), trip[:, 2].astype(np.uint32)
-
-
 class _BatchOut:
     """Where a batch's expanded entries go and how they are laid out: the reference's uint64 (row, col, value) rows (24 bytes a set
-    pixel; rc_expand_frames), or the three arrays of the COO matrix its reader wraps them into - int32 rows | int32 columns | uint16
-    values, each `cap` entries long (10 bytes; rc_expand_frames_coo).  holder: None (an array of its own per call) or a one-element
-    list with a _lib.PinnedBuffer / None (page-locked, reused, grown when too small: results are views, valid until its next use)."""
+    pixel; rc_expand_frames), or the three arrays of the COO matrix its reader wraps them into - int32 rows | int32 columns | values,
+    each `cap` entries long.  value_bytes is the width of a value: 2 (uint16, 10 bytes an entry; rc_expand_frames_coo) or 4 (uint32, 12
+    bytes; rc_expand_frames_coo32 - level-1 files of more than 16 bits, see for_file).  holder: None (an array of its own per call) or a
+    one-element list with a _lib.PinnedBuffer / None (page-locked, reused, grown when too small: results are views, valid until its next
+    use)."""
 
-    def __init__(self, coo=False, holder=None):
-        self.coo, self.holder, self.esz = bool(coo), holder, 10 if coo else 24
+    def __init__(self, coo=False, holder=None, value_bytes=2):
+        if value_bytes not in (2, 4):
+            raise ValueError('COO values are uint16 or uint32')
+        self.coo, self.holder, self.value_bytes = bool(coo), holder, int(value_bytes)
+        self.esz = 8 + self.value_bytes if coo else 24
         self.buf, self.cap = None, 0
+
+    @classmethod
+    def for_file(cls, header, coo=False, holder=None):
+        """the layout for a file: its COO values are uint32 when it is a level-1 file whose fields are wider than 16 bits (what the
+        reference's reader returns for it: recode_reader.py:464-471, misc.py:41-52), uint16 otherwise"""
+        wide = int(header['reduction_level']) == 1 and int(header['target_bit_depth']) > 16
+        return cls(coo, holder, 4 if wide else 2)
 
     def room(self, cap):
         nbytes = cap * self.esz
@@ -45,25 +51,27 @@ class _BatchOut:
         return _lib.ptr(self.buf)
 
     def fn(self, L, submit=False):
-        if submit:
-            return L.rc_expand_frames_coo_submit if self.coo else L.rc_expand_frames_submit
-        return L.rc_expand_frames_coo if self.coo else L.rc_expand_frames
+        name = 'rc_expand_frames' + (('_coo32' if self.value_bytes == 4 else '_coo') if self.coo else '') + ('_submit' if submit else '')
+        return getattr(L, name)
 
     def result(self, total):
-        return self.views(self.buf, self.cap, total, self.coo)
+        return self.views(self.buf, self.cap, total, self.coo, self.value_bytes)
 
     @staticmethod
-    def views(buf, cap, total, coo):
+    def views(buf, cap, total, coo, value_bytes=2):
+        """the first `total` entries of a buffer of capacity `cap` in the layout (coo, value_bytes)"""
         if not coo:
             return buf[:total * 24].view(np.uint64).reshape(total, 3)
-        return (buf[:4 * cap].view(np.int32)[:total], buf[4 * cap:8 * cap].view(np.int32)[:total], buf[8 * cap:10 * cap].view(np.uint16)[:total])
+        vt = np.uint32 if value_bytes == 4 else np.uint16
+        return (buf[:4 * cap].view(np.int32)[:total], buf[4 * cap:8 * cap].view(np.int32)[:total],
+                buf[8 * cap:(8 + value_bytes) * cap].view(vt)[:total])
 
     @staticmethod
-    def from_triplets(trip, coo):
+    def from_triplets(trip, coo, value_bytes=2):
         """the frame-at-a-time path's triplets in the layout asked for"""
         if not coo:
             return trip
-        return (trip[:, 0].astype(np.int32), trip[:, 1].astype(np.int32), trip[:, 2].astype(np.uint16))
+        return (trip[:, 0].astype(np.int32), trip[:, 1].astype(np.int32), trip[:, 2].astype(np.uint32 if value_bytes == 4 else np.uint16))
 
 
 class BatchedAccess:
@@ -154,8 +162,8 @@ class BatchedAccess:
         batch through the synchronous call, so any number of readers in a process may do this side by side."""
         if self._ra_off or int(self._header['reduction_level']) not in (1, 3):
             return None
-        if int(self._header['target_bit_depth']) > 16:
-            return None        # (the read-ahead's batches come as the COO arrays with uint16 values: wider values keep the frame-at-a-time path)
+        if int(self._header['reduction_level']) == 1 and int(self._header['target_bit_depth']) > 32:
+            return None        # (the read-ahead's batches come as the COO arrays, whose values are uint32 at most)
         if self._user_iters:
             # a caller's own iter_frames_* on THIS reader is alive: it owns the reader's page-locked batch buffers (the read-ahead's
             # iterator would write the next batch into what that one's arrays view) - these calls go frame by frame meanwhile
@@ -179,10 +187,10 @@ class BatchedAccess:
             if nz - z < 2:
                 return None
             k, d, level = self._RA_FRAMES, int(self._header['target_bit_depth']), int(self._header['reduction_level'])
-            # batches sized by what they expand to (10 bytes per set pixel): the value stream's length says how many there are; a
+            # batches sized by what they expand to (10 or 12 bytes per set pixel): the value stream's length says how many there are; a
             # bitmap-only file does not - one set pixel in ten is assumed
             if level == 1:
-                per = max(int(self._frame_metadata[z]['bytes_in_packed_pixvals']) * 8 // d * 10, 1)
+                per = max(int(self._frame_metadata[z]['bytes_in_packed_pixvals']) * 8 // d * _BatchOut.for_file(self._header, True).esz, 1)
             else:
                 per = max(int(self._header['nx']) * int(self._header['ny']), 1)
             k = min(max(2, min(k, self._RA_BYTES // per)), nz - z)
@@ -224,7 +232,7 @@ class BatchedAccess:
         if hi == lo:
             return None
         self.readahead_frames_served = self.readahead_frames_served + 1
-        # the batch came as the COO arrays themselves (rc_expand_frames_coo): the frame's matrix takes its own copies of its slices
+        # the batch came as the COO arrays themselves (rc_expand_frames_coo / _coo32): the frame's matrix takes its own copies of its slices
         return self._coo_from_arrays(vals[lo:hi].astype(self._numpy_dtype), rows[lo:hi].copy(), cols[lo:hi].copy())
 
     def _close_ra_iter(self):
@@ -241,13 +249,6 @@ class BatchedAccess:
         self._ra_buf = None
 
     # ---- batched access (device-resident decode + expand; no counterpart in the reference, which reads frame by frame) ------
-    def _wide_values(self):
-        """Level-1 files whose values are wider than 16 bits (target_bit_depth > 16: uint32 sources, recode_reader.py:56 / misc.py:41-49):
-        rc_expand_frames_coo carries uint16 values (include/recode_hip.h), so the COO forms of the batched calls take such files through the
-        24-byte triplets and split them on the host - same arrays, values as uint32."""
-        h = self._header
-        return int(h['reduction_level']) == 1 and int(h['target_bit_depth']) > 16
-
     def get_frames_triplets(self, z0, n, out=None, coo=False, device_blosc=False):
         """Frames z0 .. z0+n-1 of a merged file - or records z0 .. z0+n-1 of a part file, whose frame ids are part_frame_ids[z] - in ONE
         device call (rc_expand_frames): both streams of every frame are
@@ -258,16 +259,14 @@ class BatchedAccess:
         out: None (the triplets come in an array of their own), or a one-element list holding a _lib.PinnedBuffer or None - the
         triplets are then written into that page-locked buffer (grown when too small) and the returned array is a view of it,
         valid until the next call with the same holder.
-        coo=True: instead of the triplet rows, (rows int32[total], columns int32[total], values uint16[total]) - the arrays of the COO
-        matrices the frame-at-a-time calls return, 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo).
+        coo=True: instead of the triplet rows, (rows int32[total], columns int32[total], values[total]) - the arrays of the COO
+        matrices the frame-at-a-time calls return, 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo: values
+        uint16), or 12 for a level-1 file of more than 16 bits (rc_expand_frames_coo32: values uint32).
         device_blosc=True: a blosc-LZ4 file (compression_scheme 8) at level 1 or 3 goes through the device call as well (the batched
         blosc decoder of rc_expand_frames).  A switch, and off by default, because the path such files take through this call is part of
         its tested behaviour: they read frame by frame, and callers - the read-ahead among them - see 'per-frame' in last_batch_path."""
         h = self._header
-        if coo and self._wide_values():
-            prefix, trip = self.get_frames_triplets(z0, n, out=out, coo=False, device_blosc=device_blosc)
-            return prefix, _split_wide(trip)
-        dst = _BatchOut(coo, out)
+        dst = _BatchOut.for_file(h, coo, out)
         nz = self._batch_frames()
         if z0 < 0 or n <= 0 or z0 + n > nz:
             raise ValueError('Requested frame index is greater than number of frames in dataset')
@@ -338,7 +337,7 @@ class BatchedAccess:
             self._fp.seek(keep, 0)           # (get_next_frame's cursor)
         else:
             self._note_batch_end(z0 + n)
-        return prefix, _BatchOut.from_triplets(np.concatenate(parts) if parts else np.zeros((0, 3), np.uint64), coo)
+        return prefix, dst.from_triplets(np.concatenate(parts) if parts else np.zeros((0, 3), np.uint64), coo, dst.value_bytes)
 
     def _note_batch_end(self, z):
         if not self._is_intermediate:        # (a part file's sequential cursor is its file position, which the batched readers leave alone)
@@ -496,23 +495,24 @@ class BatchedAccess:
                     prefix = np.zeros(k + 1, np.uint64)
                     args = geom0 + (_lib.ptr(pieces), _lib.ptr(sizes0), k)
                     _lib.check(L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0), 'rc_expand_frames')
-                    dst = _BatchOut(coo).room(max(int(prefix[k]), 1))
+                    dst = _BatchOut.for_file(h, coo).room(max(int(prefix[k]), 1))
                     _lib.check(dst.fn(L)(*args, _lib.ptr(prefix), dst.ptr(), dst.cap), 'rc_expand_frames')
                     self.last_batch_path = 'host-decode + device-expand'
                     res = (a, prefix, dst.result(int(prefix[k])))
                 else:
                     pieces, sizes0 = got
                     cap = max(int((sizes0[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-                    esz = 10 if coo else 24
+                    dst = _BatchOut.for_file(h, coo)
+                    esz = dst.esz
                     if bufs[2 + slot] is None or bufs[2 + slot].nbytes < cap * esz:
                         if bufs[2 + slot] is not None:
                             bufs[2 + slot].close()
                         bufs[2 + slot] = _lib.PinnedBuffer(max(int(cap * esz * 1.25), 1 << 20))
                     prefix = np.zeros(k + 1, np.uint64)
-                    st = _BatchOut(coo).fn(L, submit=True)(slot, *geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, bufs[2 + slot]._p, cap)
+                    st = dst.fn(L, submit=True)(slot, *geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, bufs[2 + slot]._p, cap)
                     if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
                         # another iterator of this process holds the slot: the synchronous call has resources of its own
-                        _lib.check(_BatchOut(coo).fn(L)(*geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, _lib.ptr(prefix), bufs[2 + slot]._p, cap),
+                        _lib.check(dst.fn(L)(*geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, _lib.ptr(prefix), bufs[2 + slot]._p, cap),
                                    'rc_expand_frames')
                     else:
                         _lib.check(st, 'rc_expand_frames_submit')
@@ -522,7 +522,7 @@ class BatchedAccess:
                         _lib.check(st, 'rc_expand_frames_wait')
                     total = int(prefix[k])
                     self.last_batch_path = 'host-decode + device-expand'
-                    res = (a, prefix, _BatchOut.views(bufs[2 + slot].array, cap, total, coo))
+                    res = (a, prefix, dst.views(bufs[2 + slot].array, cap, total, coo, dst.value_bytes))
                 self._note_batch_end(a + k)
                 yield res
         finally:
@@ -556,13 +556,10 @@ class BatchedAccess:
         are walked and its bytes copied in.  Yields (first frame index, nnz_prefix uint64[k+1], triplets uint64[total, 3]) per batch
         of k <= `batch` frames; `triplets` is a VIEW of page-locked memory the device wrote directly - valid until the generator is
         advanced (copy it to keep it).  Files the device path does not take (level 2, host-only schemes, foreign streams) go through
-        get_frames_triplets batch by batch.  coo=True: the third item is (rows int32, columns int32, values uint16) instead of the
-        triplet rows - 10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo_submit)."""
+        get_frames_triplets batch by batch.  coo=True: the third item is (rows int32, columns int32, values) instead of the triplet rows -
+        10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo_submit: values uint16), 12 for a level-1 file of more than
+        16 bits (rc_expand_frames_coo32_submit: values uint32)."""
         h = self._header
-        if coo and self._wide_values():   # values beyond uint16: the device's COO layout does not hold them - triplets, split on the host
-            for a, prefix, trip in self._iter_frames_impl(z0, n, batch, coo=False, device_blosc=device_blosc):
-                yield a, prefix, _split_wide(trip)
-            return
         nz = self._batch_frames()
         n = nz - z0 if n is None else n
         if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
@@ -580,6 +577,7 @@ class BatchedAccess:
             return
         L = _lib.lib()
         geom = (int(h['nx']), int(h['ny']), d, level, mode, scheme)
+        dst = _BatchOut.for_file(h, coo)
         if self._stream_bufs is None:
             self._stream_bufs = [None, None, None, None]       # page-locked: two input blobs, two outputs; kept until close()
         bufs = self._stream_bufs
@@ -606,8 +604,8 @@ class BatchedAccess:
             blob = bufs[slot].array[:total]
             self._read_batch_into(blob, a, k)
             cap = max(int((sizes[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-            bufs[2 + slot] = pinned(bufs[2 + slot], cap * (10 if coo else 24))
-            st = _BatchOut(coo).fn(L, submit=True)(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap)
+            bufs[2 + slot] = pinned(bufs[2 + slot], cap * dst.esz)
+            st = dst.fn(L, submit=True)(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap)
             if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
                 return (a, k, slot, None)
             if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
@@ -627,7 +625,7 @@ class BatchedAccess:
                 return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)
             _lib.check(st, 'rc_expand_frames_wait')
             total = int(prefix[k])
-            trip = _BatchOut.views(bufs[2 + slot].array, cap, total, coo)
+            trip = dst.views(bufs[2 + slot].array, cap, total, coo, dst.value_bytes)
             self.last_batch_path = 'device'
             return a, prefix, trip
         queued = None        # a batch submitted and not yet waited for
@@ -837,16 +835,19 @@ class BatchedAccess:
                     pass
 
     def get_frames_coo(self, z0, n, out=None):
-        """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16))"""
+        """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
+        more than 16 bits))"""
         return self.get_frames_triplets(z0, n, out=out, coo=True)
 
     def iter_frames_coo(self, z0=0, n=None, batch=64):
-        """iter_frames_triplets in the COO layout: yields (first frame, nnz_prefix, (rows int32, columns int32, values uint16))"""
+        """iter_frames_triplets in the COO layout: yields (first frame, nnz_prefix, (rows int32, columns int32, values uint16 - uint32
+        for a level-1 file of more than 16 bits))"""
         return self.iter_frames_triplets(z0, n, batch, coo=True)
 
     def get_frames(self, z0, n):
         """{frame index: {'metadata', 'data': COO}} for n consecutive frames, decoded in one device call."""
-        coo_ok = int(self._header['reduction_level']) in (1, 3) and int(self._header['target_bit_depth']) <= 16
+        level, d = int(self._header['reduction_level']), int(self._header['target_bit_depth'])
+        coo_ok = level == 3 or (level == 1 and d <= 32)          # (the COO arrays' values are uint32 at most)
         prefix, got = self.get_frames_triplets(z0, n, coo=coo_ok)
         out = {}
         for i in range(n):

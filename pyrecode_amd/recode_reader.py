@@ -354,8 +354,8 @@ class ReCoDeReader(BatchedAccess):
             cap = int(prefix[1])
         if cap == 0:
             return NotImplemented      # (an empty frame: the plain path knows the reference's conventions for it)
-        coo = d <= 16                  # the matrix's own arrays straight from the device (rc_expand_frames_coo), else triplet rows
-        dst = _BatchOut(coo).room(cap)
+        coo = level != 1 or d <= 32    # the matrix's own arrays straight from the device (rc_expand_frames_coo / _coo32), else triplet rows
+        dst = _BatchOut.for_file(h, coo).room(cap)
         st = dst.fn(L)(*args, _lib.ptr(prefix), dst.ptr(), cap)
         if st != _lib.RC_OK:
             if st == _lib.RC_ERR_UNSUPPORTED and int(h['rc_operation_mode']) == 1:
