@@ -52,7 +52,13 @@ typedef enum rc_status {
  * field 0, recode_compressors.py:42-43,84-85) whose two streams are zlib streams (RFC 1950) made by the device's own DEFLATE
  * encoder - a byte-aligned fixed-Huffman block per 512-byte tile of the binary map, stored blocks for the packed values, Adler-32
  * trailers - which `zlib.decompress` (the reference's reader, recode_compressors.py:43) expands to the exact bytes; like every other
- * device codec it promises a VALID stream, not stock zlib's bytes (RC_SCHEME_ZLIB through the host layer keeps those). */
+ * device codec it promises a VALID stream, not stock zlib's bytes (RC_SCHEME_ZLIB through the host layer keeps those).
+ * compression_level: 0 / 1 as above.  From 2 on (reduction level 1) the packed values are Huffman-coded: every 32 KiB chunk that pays
+ * becomes a literals-only dynamic-Huffman block (RFC 1951 BTYPE 10) under ONE table per ctx, fitted to (up to two frames of) the ctx's
+ * first batch - rc_ctx_refit_model fits it again -, every other chunk stays the stored block it was, so a record never grows; a ctx
+ * whose sample the byte-wise code cannot shrink by 3 % (bit-packed depths such as 12) keeps the stored form.  The workspace of such a ctx
+ * holds the flat value stream and the chunk images besides (about two raw frames per frame of a batch, per scratch set).  Reduction
+ * levels 2 and 3 write at every level what they write at level 1. */
 enum { RC_SCHEME_ZLIB = 0, RC_SCHEME_ZSTD = 1, RC_SCHEME_LZ4 = 2, RC_SCHEME_BLOSC_LZ4 = 8, RC_SCHEME_ZLIB_DEVICE = 0x100 };
 
 typedef struct rc_ctx rc_ctx;

@@ -181,7 +181,10 @@ class ReduceContext:
     def __init__(self, nx, ny, src_bit_depth, reduction_level=1, op_mode=1, scheme=2, clevel=1, device_id=0, max_batch=16, src_dtype=np.uint16,
                  device_zlib=False):
         """src_dtype: numpy dtype of the frames and the dark frame - uint16, or uint8 (source_bit_depth <= 8: rc_ctx_set_source_bytes)
-        device_zlib: compression_scheme 0 encoded by the device's DEFLATE encoder (valid zlib streams, not stock zlib's bytes)"""
+        device_zlib: compression_scheme 0 encoded by the device's DEFLATE encoder (valid zlib streams, not stock zlib's bytes).  clevel 0 / 1:
+        the binary map is coded, the packed values are stored blocks; clevel >= 2 (reduction level 1): the packed values are Huffman-coded
+        too - a literals-only dynamic block per 32 KiB chunk that pays, under one table fitted to the ctx's first batch (refit_model()
+        fits it again); a record never grows over its clevel-1 form"""
         if device_zlib and scheme == 0 and op_mode == 1:
             scheme = RC_SCHEME_ZLIB_DEVICE
         st = C.c_int(0)

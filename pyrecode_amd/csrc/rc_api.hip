@@ -1,6 +1,7 @@
 // rc_api.hip - the C ABI of librecode_hip.so (include/recode_hip.h): contexts, staging, entry points.
 // No CPU implementation lives here: every compute entry point runs HIP kernels or returns RC_ERR_DEVICE.
 #include "rc_host.h"
+#include "rc_deflate_model.h"
 
 thread_local std::string g_last_error;
 WorkerPool *g_pool = new WorkerPool;
@@ -46,6 +47,10 @@ struct rc_ctx {
     bool modelled = false, model_ready = false;
     rc::ZstdModel *d_model = nullptr, *h_model = nullptr;
     rc::ZstdSample *d_sample = nullptr, *h_sample = nullptr;
+    // device DEFLATE, level 1, compression_level >= 2: the residual stream's Huffman table, fitted like the zstd model (rc_deflate_model.h)
+    bool dz_values = false;
+    rc::DeflateModel *d_dzm = nullptr, *h_dzm = nullptr;
+    uint32_t *d_dzhist = nullptr, *h_dzhist = nullptr;   // the sample's byte histogram
     uint32_t l2_sum = 0;                  // L2_statistics: 0/1 max, 2 sum
     rc::u32x2 *d_l2_node[2] = {};         // level 2: the labelling stage's nodes (rc_l2.hip) - one workspace per chain of second stages
     uint16_t *d_l2_base[2] = {};          // ... and its directory of rank bases
@@ -148,11 +153,14 @@ static int alloc_set(rc_ctx *c, rc::Scratch &sc, DevMem &model_mem)
             HIP_TRY(hipMemset(sc.zl_acc, 0, B * 32));
         }
     }
-    if (c->emit == EMIT_ZSTD && c->clevel != 0 && c->level == 1) {   // modelled zstd: Huffman stage of the residual stream
+    const bool dz_values = c->emit == EMIT_DEFLATE && c->clevel >= 2 && c->level == 1;
+    if ((c->emit == EMIT_ZSTD && c->clevel != 0 && c->level == 1) || dz_values) {   // modelled zstd / device DEFLATE: Huffman stage of the residual stream
+        const uint32_t chunk = dz_values ? PD_CHUNK : PIX_CHUNK, slot = dz_values ? PD_SLOT : PIX_SLOT;
         sc.pixraw_stride = ((sc.N * 2 + 15) & ~15ull) + 32;
-        sc.nchunk_max = (uint32_t)((sc.N * 2 + PIX_CHUNK - 1) / PIX_CHUNK) + 1;
+        sc.nchunk_max = (uint32_t)((sc.N * 2 + chunk - 1) / chunk) + 1;
         RC_ALLOC(model_mem, sc.pixraw, B * sc.pixraw_stride + 64);
-        RC_ALLOC(model_mem, sc.pix_chunks, B * (uint64_t)sc.nchunk_max * PIX_SLOT + 64);
+        RC_ALLOC(model_mem, sc.pix_chunks, B * (uint64_t)sc.nchunk_max * slot + 64);
+        if (dz_values) RC_ALLOC(model_mem, sc.chunk_aux, B * (uint64_t)(sc.nchunk_max + 1) * 8);
         RC_ALLOC(model_mem, sc.chunk_size, B * (uint64_t)sc.nchunk_max * 4);
         RC_ALLOC(model_mem, sc.chunk_off, B * (uint64_t)sc.nchunk_max * 4);
         RC_ALLOC(model_mem, sc.frame_pbytes, B * 4);
@@ -225,6 +233,13 @@ static int ctx_alloc(rc_ctx *c)
             RC_ALLOC(c->hmem, c->h_model, sizeof(ZstdModel));
             RC_ALLOC(c->hmem, c->h_sample, sizeof(ZstdSample));
         }
+    }
+    c->dz_values = c->emit == EMIT_DEFLATE && c->clevel >= 2 && c->level == 1;
+    if (c->dz_values) {
+        RC_ALLOC(m, c->d_dzm, sizeof(DeflateModel));
+        RC_ALLOC(m, c->d_dzhist, 256 * 4);
+        RC_ALLOC(c->hmem, c->h_dzm, sizeof(DeflateModel));
+        RC_ALLOC(c->hmem, c->h_dzhist, 256 * 4);
     }
     RC_ALLOC(m, c->d_rec_off, (B + 1) * 8);
     RC_ALLOC(m, c->d_md, B * 3 * 4);
@@ -475,6 +490,37 @@ static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
     return RC_OK;
 }
 
+// Device DEFLATE, compression_level >= 2: fit the ctx's residual-stream table to (up to two frames of) its first batch.  The sample is reduced
+// into the scratch set the batch is about to use, its residual streams are laid out flat (k_gather's PIX_MODE_FLAT pass), k_pd_hist counts
+// their bytes, the host builds the table and the block header (rc_deflate_model.h).  Synchronous, once per ctx (and per rc_ctx_refit_model).
+static int fit_deflate_model(rc_ctx *c, const void *frames_dev, uint32_t n)
+{
+    using namespace rc;
+    hipStream_t s = c->stream;
+    const Scratch &sc = c->sets[c->cur];
+    const uint32_t ns = n < 2 ? n : 2;
+    for (int k = 0; k < 2; ++k)
+        if (c->post_pending[k]) HIP_TRY(hipStreamWaitEvent(s, c->ev_post[k], 0));
+    HIP_TRY(hipMemsetAsync(c->d_dzhist, 0, 256 * 4, s));
+    launch_reduce(sc, frames_dev, ns, 1u, CODEC_DEFLATE, true, c->depth, s, nullptr, c->src_bytes);
+    launch_scans(sc, ns, true, true, s);
+    RecordParams rp;
+    rp.level = 1u; rp.emit = c->emit; rp.depth = c->depth; rp.first_frame_id = 0; rp.packed_slots = 1u;
+    rp.frame_bytes = c->geo().N * c->src_bytes;
+    rp.pix_mode = PIX_MODE_FLAT;
+    launch_assemble(sc, rp, ns, nullptr, nullptr, c->batch_seq, s);   // (the flat pass touches neither the records nor their offsets)
+    launch_pd_hist(sc, ns, c->depth, c->d_dzhist, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_dzhist, c->d_dzhist, 256 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    dm_build_model(c->h_dzhist, c->h_dzm);   // (usable: the 97 % rule of fit_model - a stream the byte-wise code cannot shrink stays stored)
+    HIP_TRY(hipMemcpyAsync(c->d_dzm, c->h_dzm, sizeof(DeflateModel), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (Scratch &set : c->sets) set.zm_model = c->d_dzm;
+    c->model_ready = true;
+    return RC_OK;
+}
+
 // The block encoder fused into the reduce kernel for a ctx's record form.  uint32 sources (src_bytes 4, rc_reduce32.hip) have the fast zstd
 // encoder only (the modelled one is fitted inside the uint16 kernel).
 static uint32_t fused_codec(uint32_t emit, uint32_t clevel, bool modelled, uint32_t src_bytes)
@@ -496,6 +542,10 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     hipStream_t s = c->stream;
     if (c->modelled && !c->model_ready) {
         int r = fit_model(c, frames_dev, n);
+        if (r != RC_OK) return r;
+    }
+    if (c->dz_values && !c->model_ready) {
+        int r = fit_deflate_model(c, frames_dev, n);
         if (r != RC_OK) return r;
     }
     RecordParams rp;
@@ -570,6 +620,16 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
         launch_pix_scan(sc, n, c->depth, ps);
         rp.pix_mode = PIX_MODE_SKIP;
     }
+    // device DEFLATE, compression_level >= 2, level 1: the same stage in DEFLATE's container (rc_pix_deflate.hip) - flat pass, a dynamic-Huffman
+    // block per 32 KiB chunk that pays, sizes -> layout; a ctx whose table does not pay keeps the stored blocks
+    const bool pix_deflate = c->dz_values && c->h_dzm->usable && sc.pixraw;
+    if (pix_deflate) {
+        rp.pix_mode = PIX_MODE_FLAT;
+        launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
+        launch_pd_encode(sc, n, c->depth, ps);
+        launch_pd_scan(sc, n, c->depth, ps);
+        rp.pix_mode = PIX_MODE_SKIP;
+    }
     if (two && c->post_pending[k ^ 1]) {
         // Two chains run the second stages of batches i and i + 1 at the same time, which is why include/recode_hip.h asks a pipelined caller for
         // two sets of output buffers.  A caller that hands this batch a buffer the previous batch is still writing (rounds 1-4 tolerated that: one
@@ -586,6 +646,7 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
     ++c->batch_seq;
     if (pix_huff) launch_pix_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
+    if (pix_deflate) launch_pd_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
     if (ev) HIP_TRY(hipEventRecord(ev[4], ps));
     if (two && c->post_pending[k ^ 1]) HIP_TRY(hipStreamWaitEvent(ps, c->ev_post[k ^ 1], 0));   // batches still COMPLETE in order
     HIP_TRY(hipEventRecord(c->ev_post[k], ps));

@@ -66,6 +66,9 @@ struct Scratch {
     u32x2 *l2_node = nullptr;          // [B][ntiles * TILE_PX] {parent id, accumulator} per set pixel, id = tile * TILE_PX + rank in the tile
     uint64_t l2_ids_per_frame = 0;
     uint16_t *l2_base = nullptr;       // [B][ntiles * 64] set pixels of a word's tile in front of the word (k_l2_dir)
+    // device DEFLATE, compression_level >= 2 (rc_pix_deflate.hip): the Huffman stage of the residual stream shares pixraw, pix_chunks
+    // ([B][nchunk_max][PD_SLOT]), chunk_size, chunk_off, frame_pbytes and zm_model (a DeflateModel) with the modelled zstd encoder's
+    uint32_t *chunk_aux = nullptr;     // [B][nchunk_max + 1][2]  the chunks' Adler-32 partials {A, W}; last entry: the stream's Adler-32
 };
 
 // RecordParams::emit / rc_ctx::emit: the form of a record's two streams (rc_record.h).  Also the batched decoder's selector (rc_reader.hip,
@@ -132,6 +135,13 @@ void launch_pix_huff(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t 
 void launch_pix_scan(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);   // (rc_reduce.hip)
 void launch_pix_gather(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t level1_hdr, uint8_t *out, const uint64_t *rec_off,
                        hipStream_t s);
+// rc_pix_deflate.hip: the packed residual stream of every frame (Scratch::pixraw) -> dynamic-Huffman DEFLATE blocks -> the records
+constexpr uint32_t PD_CHUNK = 1u << 15, PD_SLOT = PD_CHUNK + 32;   // the stored blocks' grid (rc_record.h::frame_fmt); a coded image is < PD_CHUNK + 5 bytes
+void launch_pd_hist(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t *hist_dev, hipStream_t s);
+void launch_pd_encode(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
+void launch_pd_scan(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
+void launch_pd_gather(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t level1_hdr, uint8_t *out, const uint64_t *rec_off,
+                      hipStream_t s);
 // rc_lz4.hip
 struct Lz4Block { uint64_t src_off; uint32_t size; uint32_t raw; };
 void launch_lz4_encode_buffer(const Scratch &sc, hipStream_t s, bool events = false);  // sc.bitmap = the buffer, sc.nb = its length

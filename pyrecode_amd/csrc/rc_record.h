@@ -15,7 +15,9 @@ namespace rc {
 //                                     "memcpyed" flag + the bytes (what c-blosc itself emits for incompressible input)
 //   zlib stream (RFC 1950 / 1951):    2-byte header, deflate blocks (the map: a byte-aligned block pair per tile, rc_deflate_block.h; the
 //                                     residuals: stored blocks of 32 KiB with 5-byte headers, BFINAL on the last, >= 1 block), Adler-32
-//                                     of the uncompressed bytes, big-endian (summed up inside k_gather, written by k_zlib_finish behind it)
+//                                     of the uncompressed bytes, big-endian (summed up inside k_gather, written by k_zlib_finish behind it);
+//                                     compression_level >= 2: a residual chunk that pays is a dynamic-Huffman block instead and the stream is
+//                                     laid out by rc_pix_deflate.hip (PIX_MODE_SKIP: hdr + frame_pbytes, the trailer included)
 struct FrameFmt { uint32_t hdr, end, chunk_shift, chunk_hdr, min_chunks; };
 __host__ __device__ inline FrameFmt frame_fmt(uint32_t emit)
 {

@@ -44,13 +44,14 @@ struct ZmBits {
 // Code lengths (1..maxbits) for ALL 256 byte values from a histogram: every value must stay encodable whatever later frames
 // contain, so the counts are smoothed (x256 + 1) before the usual pairing; lengths above maxbits are cut and the Kraft sum is
 // then repaired so that it is exactly one again (a zstd tree description only exists for complete codes).
-inline void zm_huf_lengths(const uint32_t *hist, uint8_t *len, int maxbits = ZM_HUF_MAXBITS)
+// (zm_huf_lengths_n: the same for an alphabet of nsym symbols - the device DEFLATE encoder's 257 and 19, rc_deflate_model.h)
+inline void zm_huf_lengths_n(const uint32_t *hist, uint8_t *len, int nsym, int maxbits)
 {
     struct Node { uint64_t w; int l, r; };
     std::vector<Node> nodes;
     std::vector<int> live;
-    for (int s = 0; s < 256; ++s) { nodes.push_back({(uint64_t)hist[s] * 256u + 1u, -1, -1}); live.push_back(s); }
-    while (live.size() > 1) {   // 256 symbols: the quadratic pairing is cheap enough
+    for (int s = 0; s < nsym; ++s) { nodes.push_back({(uint64_t)hist[s] * 256u + 1u, -1, -1}); live.push_back(s); }
+    while (live.size() > 1) {   // <= 257 symbols: the quadratic pairing is cheap enough
         std::sort(live.begin(), live.end(), [&](int a, int b) { return nodes[a].w != nodes[b].w ? nodes[a].w > nodes[b].w : a > b; });
         const int a = live.back(); live.pop_back();
         const int b = live.back(); live.pop_back();
@@ -58,15 +59,15 @@ inline void zm_huf_lengths(const uint32_t *hist, uint8_t *len, int maxbits = ZM_
         live.push_back((int)nodes.size() - 1);
     }
     std::vector<int> depth(nodes.size(), 0);
-    for (int i = (int)nodes.size() - 1; i >= 256; --i) { depth[nodes[i].l] = depth[i] + 1; depth[nodes[i].r] = depth[i] + 1; }
+    for (int i = (int)nodes.size() - 1; i >= nsym; --i) { depth[nodes[i].l] = depth[i] + 1; depth[nodes[i].r] = depth[i] + 1; }
     int64_t kraft = 0;  // in units of 2^-maxbits
-    for (int s = 0; s < 256; ++s) {
+    for (int s = 0; s < nsym; ++s) {
         len[s] = (uint8_t)std::min(std::max(depth[s], 1), maxbits);
         kraft += (int64_t)1 << (maxbits - len[s]);
     }
     const int64_t one = (int64_t)1 << maxbits;
-    std::vector<int> order(256);
-    for (int s = 0; s < 256; ++s) order[s] = s;
+    std::vector<int> order(nsym);
+    for (int s = 0; s < nsym; ++s) order[s] = s;
     std::sort(order.begin(), order.end(), [&](int a, int b) { return hist[a] != hist[b] ? hist[a] < hist[b] : a > b; });  // rarest first
     while (kraft > one) {       // over-subscribed after the cut: lengthen the rarest symbols that still can be
         bool moved = false;
@@ -76,7 +77,7 @@ inline void zm_huf_lengths(const uint32_t *hist, uint8_t *len, int maxbits = ZM_
     }
     while (kraft < one) {       // slack: shorten the most frequent symbol whose step fits (a maxbits symbol always does)
         bool moved = false;
-        for (int i = 255; i >= 0; --i) {
+        for (int i = nsym - 1; i >= 0; --i) {
             const int s = order[i];
             const int64_t gain = (int64_t)1 << (maxbits - len[s]);
             if (len[s] > 1 && gain <= one - kraft) { --len[s]; kraft += gain; moved = true; break; }
@@ -84,6 +85,7 @@ inline void zm_huf_lengths(const uint32_t *hist, uint8_t *len, int maxbits = ZM_
         if (!moved) break;
     }
 }
+inline void zm_huf_lengths(const uint32_t *hist, uint8_t *len, int maxbits = ZM_HUF_MAXBITS) { zm_huf_lengths_n(hist, len, 256, maxbits); }
 
 // Code values the decoder's table construction implies (RFC 8878 4.2.1: symbols in order of increasing weight, then
 // increasing value, fill the decoding table from index 0): longest codes get the numerically smallest values.

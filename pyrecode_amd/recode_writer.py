@@ -54,7 +54,9 @@ class ReCoDeWriter:
         device_zlib compression_scheme 0 only: True = both streams of a record are made by the device's DEFLATE encoder (valid zlib
                     streams that the reference's reader - zlib.decompress, recode_compressors.py:43 - expands to the same bytes; the file
                     header still says scheme 0), False = the reference's own `zlib.compress` call on the host (byte-identical files, two
-                    orders of magnitude slower).  Default: the environment's RC_DEVICE_ZLIB (1 / 0), else False.
+                    orders of magnitude slower).  Default: the environment's RC_DEVICE_ZLIB (1 / 0), else False.  With True,
+                    compression_level >= 2 also Huffman-codes the packed values (level 0 / 1: stored blocks), which brings the record
+                    to about stock zlib-1's size at depth 16.
         use_c is accepted for compatibility; the native path is always the HIP library."""
         self._init_params = InitParams(mode, output_directory, image_filename=image_filename,
                                        calibration_filename=dark_filename, params_filename=params_filename,
