@@ -23,7 +23,7 @@ struct rc_ctx {
     const rc::Scratch &geo() const { return sets[0]; }       // N, ntiles, nb, nb_stride, thr
     const rc::Scratch &recent() const { return sets[last]; } // the most recent batch's status word and binary maps
     // Every device and page-locked allocation of the ctx - scratch sets, pipe slots, staging - is on one of these lists (rc_host.h);
-    // model_mem: the modelled zstd encoder's residual-stream scratch of each set, which rc_ctx_set_source_bytes(ctx, 4) gives back.
+    // model_mem: the value stage's scratch of each set, which rc_ctx_set_source_bytes(ctx, 4) gives back.
     DevMem dmem, model_mem[2];
     PinMem hmem;
     hipStream_t pstream = nullptr;        // carries everything behind the reduce kernel
@@ -43,14 +43,16 @@ struct rc_ctx {
     uint64_t *d_rec_off = nullptr;
     uint32_t *d_md = nullptr;
     void *d_ztab = nullptr;               // zstd FSE tables (EMIT_ZSTD)
-    // modelled zstd (compression_level >= 1): tables fitted to a sample of the ctx's first batch (rc_zstd_model.h)
+    // the value stage (rc_launch.h): its format, set by rc_ctx_create (uint32 sources: none); values_on: the fitted table pays (else the stream stays stored)
+    rc::ValueStage values = rc::VALUES_NONE;
+    bool values_on = false;
+    // tables fitted to a sample of the ctx's first batch (fit_value_model): modelled zstd (compression_level >= 1, every reduction level:
+    // rc_zstd_model.h) and the DEFLATE value stage's (rc_deflate_model.h, with the sample's byte histogram)
     bool modelled = false, model_ready = false;
     rc::ZstdModel *d_model = nullptr, *h_model = nullptr;
     rc::ZstdSample *d_sample = nullptr, *h_sample = nullptr;
-    // device DEFLATE, level 1, compression_level >= 2: the residual stream's Huffman table, fitted like the zstd model (rc_deflate_model.h)
-    bool dz_values = false;
     rc::DeflateModel *d_dzm = nullptr, *h_dzm = nullptr;
-    uint32_t *d_dzhist = nullptr, *h_dzhist = nullptr;   // the sample's byte histogram
+    uint32_t *d_dzhist = nullptr, *h_dzhist = nullptr;
     uint32_t l2_sum = 0;                  // L2_statistics: 0/1 max, 2 sum
     rc::u32x2 *d_l2_node[2] = {};         // level 2: the labelling stage's nodes (rc_l2.hip) - one workspace per chain of second stages
     uint16_t *d_l2_base[2] = {};          // ... and its directory of rank bases
@@ -153,14 +155,13 @@ static int alloc_set(rc_ctx *c, rc::Scratch &sc, DevMem &model_mem)
             HIP_TRY(hipMemset(sc.zl_acc, 0, B * 32));
         }
     }
-    const bool dz_values = c->emit == EMIT_DEFLATE && c->clevel >= 2 && c->level == 1;
-    if ((c->emit == EMIT_ZSTD && c->clevel != 0 && c->level == 1) || dz_values) {   // modelled zstd / device DEFLATE: Huffman stage of the residual stream
-        const uint32_t chunk = dz_values ? PD_CHUNK : PIX_CHUNK, slot = dz_values ? PD_SLOT : PIX_SLOT;
+    if (c->values != VALUES_NONE) {   // the value stage's scratch (free_value_stage gives it back)
+        const ValueGeom g = value_geom(c->values);
         sc.pixraw_stride = ((sc.N * 2 + 15) & ~15ull) + 32;
-        sc.nchunk_max = (uint32_t)((sc.N * 2 + chunk - 1) / chunk) + 1;
+        sc.nchunk_max = (uint32_t)((sc.N * 2 + g.chunk - 1) / g.chunk) + 1;
         RC_ALLOC(model_mem, sc.pixraw, B * sc.pixraw_stride + 64);
-        RC_ALLOC(model_mem, sc.pix_chunks, B * (uint64_t)sc.nchunk_max * slot + 64);
-        if (dz_values) RC_ALLOC(model_mem, sc.chunk_aux, B * (uint64_t)(sc.nchunk_max + 1) * 8);
+        RC_ALLOC(model_mem, sc.pix_chunks, B * (uint64_t)sc.nchunk_max * g.slot + 64);
+        if (c->values == VALUES_DEFLATE_HUFF) RC_ALLOC(model_mem, sc.chunk_aux, B * (uint64_t)(sc.nchunk_max + 1) * 8);
         RC_ALLOC(model_mem, sc.chunk_size, B * (uint64_t)sc.nchunk_max * 4);
         RC_ALLOC(model_mem, sc.chunk_off, B * (uint64_t)sc.nchunk_max * 4);
         RC_ALLOC(model_mem, sc.frame_pbytes, B * 4);
@@ -170,6 +171,19 @@ static int alloc_set(rc_ctx *c, rc::Scratch &sc, DevMem &model_mem)
     HIP_TRY(hipMemset(sc.frame_cbytes, 0, B * 4));
     HIP_TRY(hipMemset(sc.status, 0, sizeof(BatchStatus)));
     return RC_OK;
+}
+
+// uint32 sources have no value stage: its scratch (alloc_set sized it for uint16 sources) goes back, every field of it is cleared
+static void free_value_stage(rc_ctx *c)
+{
+    c->values = rc::VALUES_NONE;
+    c->values_on = false;
+    for (int k = 0; k < 2; ++k) {
+        rc::Scratch &set = c->sets[k];
+        c->model_mem[k].release_all();
+        set.pixraw = nullptr; set.pix_chunks = nullptr; set.chunk_aux = nullptr; set.chunk_size = nullptr; set.chunk_off = nullptr;
+        set.frame_pbytes = nullptr; set.pixraw_stride = 0; set.nchunk_max = 0;
+    }
 }
 
 static int ctx_alloc(rc_ctx *c)
@@ -234,8 +248,7 @@ static int ctx_alloc(rc_ctx *c)
             RC_ALLOC(c->hmem, c->h_sample, sizeof(ZstdSample));
         }
     }
-    c->dz_values = c->emit == EMIT_DEFLATE && c->clevel >= 2 && c->level == 1;
-    if (c->dz_values) {
+    if (c->values == VALUES_DEFLATE_HUFF) {
         RC_ALLOC(m, c->d_dzm, sizeof(DeflateModel));
         RC_ALLOC(m, c->d_dzhist, 256 * 4);
         RC_ALLOC(c->hmem, c->h_dzm, sizeof(DeflateModel));
@@ -301,6 +314,7 @@ RC_EXPORT rc_ctx *rc_ctx_create(uint32_t nx, uint32_t ny, uint32_t src_bit_depth
     c->nx = nx; c->ny = ny; c->depth = src_bit_depth; c->level = reduction_level; c->op_mode = op_mode;
     c->scheme = scheme; c->clevel = clevel; c->max_batch = max_batch;
     c->emit = (op_mode == 1 && rc_scheme_on_device(scheme)) ? scheme : rc::EMIT_RAW;
+    c->values = rc::value_stage_of(c->emit, clevel, reduction_level);
     rc::Scratch &sc = c->sets[0];   // (ctx_alloc copies the geometry to the other set)
     sc.N = (uint64_t)nx * ny;
     sc.ntiles = (uint32_t)((sc.N + rc::TILE_PX - 1) / rc::TILE_PX);
@@ -419,6 +433,7 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
         }
         if (c->depth % 8 == 0) c->depth = 32;
         c->modelled = false;
+        free_value_stage(c);
         c->thr32 = thr32;
         for (int k = 0; k < 2; ++k) {
             rc::Scratch *set = &c->sets[k];
@@ -428,10 +443,6 @@ RC_EXPORT int rc_ctx_set_source_bytes(rc_ctx *c, uint32_t bytes_per_pixel)
                 c->dmem.free_one(set->pix_slots);
                 set->pix_slots = slots[k];
             }
-            // the modelled zstd encoder's residual-stream scratch (alloc_set sized it for uint16 sources): not used by this path
-            c->model_mem[k].release_all();
-            set->pixraw = nullptr; set->pix_chunks = nullptr; set->chunk_size = nullptr; set->chunk_off = nullptr; set->frame_pbytes = nullptr;
-            set->pixraw_stride = 0; set->nchunk_max = 0;
         }
     }
     c->src_bytes = bytes_per_pixel;
@@ -449,74 +460,62 @@ RC_EXPORT uint32_t rc_md_fields(const rc_ctx *c)
     return comp ? 1 : 0;
 }
 
-// Modelled zstd: fit the ctx's tables to (up to two frames of) its first batch.  The sample is tokenized by the plain encoder
-// into the scratch set the batch is about to use, k_zstd_sample turns the slots into histograms, the host builds the model
-// (rc_zstd_model.h).  Synchronous, once per ctx; every later frame carries this model's descriptions.
-static int fit_model(rc_ctx *c, const void *frames_dev, uint32_t n)
+// Fit the ctx's tables to (up to two frames of) its first batch: synchronous, once per ctx and per rc_ctx_refit_model; every later frame is
+// written under them.  The sample is reduced into the scratch set the batch is about to use and counted on the device, the host builds the model.
+// Modelled zstd (every reduction level; the value stage's code at level 1 only): the plain encoder tokenizes the sample, k_zstd_sample turns the
+// slots into histograms.  DEFLATE value stage: the sample's residual streams are laid out flat (PIX_MODE_FLAT), k_pd_hist counts their bytes.
+static int fit_value_model(rc_ctx *c, const void *frames_dev, uint32_t n)
 {
     using namespace rc;
+    const bool dz = c->values == VALUES_DEFLATE_HUFF;
     hipStream_t s = c->stream;
     const Scratch &sc = c->sets[c->cur];
     const uint32_t ns = n < 2 ? n : 2;
+    void *d_sample = dz ? (void *)c->d_dzhist : c->d_sample, *h_sample = dz ? (void *)c->h_dzhist : c->h_sample;
+    void *d_model = dz ? (void *)c->d_dzm : c->d_model, *h_model = dz ? (void *)c->h_dzm : c->h_model;
+    const size_t sample_bytes = dz ? 256 * 4 : sizeof(ZstdSample), model_bytes = dz ? sizeof(DeflateModel) : sizeof(ZstdModel);
     for (int k = 0; k < 2; ++k)
         if (c->post_pending[k]) HIP_TRY(hipStreamWaitEvent(s, c->ev_post[k], 0));
-    HIP_TRY(hipMemsetAsync(c->d_sample, 0, sizeof(ZstdSample), s));
-    launch_reduce(sc, frames_dev, ns, c->level == 3 ? 3u : 1u, CODEC_ZSTD_FAST, true, c->depth, s, nullptr, c->src_bytes);   // (with the raw maps: the sample counts all their bytes)
-    launch_zstd_sample(sc, ns, c->level == 1, c->depth, c->d_sample, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_sample, c->d_sample, sizeof(ZstdSample), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // compression_level -> how much size the faster block form of the binary maps may cost (rc_zstd_model.h): the reference hands the
-    // level to libzstd (recode_writer.py:175-178), where 1 is the fast end too.  Level 1: up to 5 % of the binary-map stream, level 2: 2 %,
-    // from 3 on the smaller form always.
-    zstd_model_from_sample(c->h_sample, c->h_model, c->clevel == 1 ? 50u : (c->clevel == 2 ? 20u : 0u));
-    if (c->level != 1) c->h_model->valid &= ~ZM_PIX_CODE;   // level 2 statistics / level 3: no residual-stream code
-    {   // a residual stream the byte-wise code cannot shrink (bit-packed depths) is stored instead, in 128 KiB Raw blocks
-        uint64_t bits = 0, total = 0;
-        for (int v = 0; v < 256; ++v) { bits += (uint64_t)c->h_sample->pix[v] * (c->h_model->pix_code[v] >> 12); total += c->h_sample->pix[v]; }
-        if (total == 0 || bits > total * 8 * 97 / 100) c->h_model->valid &= ~ZM_PIX_CODE;
+    HIP_TRY(hipMemsetAsync(d_sample, 0, sample_bytes, s));
+    if (dz) {
+        launch_reduce(sc, frames_dev, ns, 1u, CODEC_DEFLATE, true, c->depth, s, nullptr, c->src_bytes);
+        launch_scans(sc, ns, true, true, s);
+        RecordParams rp;
+        rp.level = 1u; rp.emit = c->emit; rp.depth = c->depth; rp.first_frame_id = 0; rp.packed_slots = 1u;
+        rp.frame_bytes = c->geo().N * c->src_bytes;
+        rp.pix_mode = PIX_MODE_FLAT;
+        launch_assemble(sc, rp, ns, nullptr, nullptr, c->batch_seq, s);   // (the flat pass touches neither the records nor their offsets)
+        launch_pd_hist(sc, ns, c->depth, c->d_dzhist, s);
+    } else {
+        launch_reduce(sc, frames_dev, ns, c->level == 3 ? 3u : 1u, CODEC_ZSTD_FAST, true, c->depth, s, nullptr, c->src_bytes);   // (with the raw maps: the sample counts all their bytes)
+        launch_zstd_sample(sc, ns, c->level == 1, c->depth, c->d_sample, s);
     }
-    HIP_TRY(hipMemcpyAsync(c->d_model, c->h_model, sizeof(ZstdModel), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_sample, d_sample, sample_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const ZstdModel &M = *c->h_model;
+    if (dz) {
+        dm_build_model(c->h_dzhist, c->h_dzm);
+        c->values_on = c->h_dzm->usable != 0;
+    } else {
+        // compression_level -> how much size the faster block form of the binary maps may cost (rc_zstd_model.h): the reference hands the
+        // level to libzstd (recode_writer.py:175-178), where 1 is the fast end too.  Level 1: up to 5 % of the binary-map stream, level 2: 2 %,
+        // from 3 on the smaller form always.
+        zstd_model_from_sample(c->h_sample, c->h_model, c->clevel == 1 ? 50u : (c->clevel == 2 ? 20u : 0u));
+        // (no value stage: reduction levels 2 and 3; a code that does not pay: the stream is stored, in 128 KiB Raw blocks)
+        if (c->values == VALUES_NONE || !zm_code_pays(c->h_sample->pix, c->h_model->pix_code)) c->h_model->valid &= ~ZM_PIX_CODE;
+        c->values_on = (c->h_model->valid & ZM_PIX_CODE) != 0;
+    }
+    HIP_TRY(hipMemcpyAsync(d_model, h_model, model_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     for (Scratch &set : c->sets) {
+        if (dz) { set.dz_model = c->d_dzm; continue; }
+        const ZstdModel &M = *c->h_model;
         set.zm_model = c->d_model;
         set.zm_lit_code = c->d_model->lit_code;
         set.zm_valid = M.valid;
         set.zm_budget = zm_block_budget(M, BLK_SLOT);
         set.zm_seq_bits = (M.valid & ZM_SEQ_TABLES) ? M.seq.ll_log + M.seq.ml_log : 12u;
     }
-    c->model_ready = true;
-    return RC_OK;
-}
-
-// Device DEFLATE, compression_level >= 2: fit the ctx's residual-stream table to (up to two frames of) its first batch.  The sample is reduced
-// into the scratch set the batch is about to use, its residual streams are laid out flat (k_gather's PIX_MODE_FLAT pass), k_pd_hist counts
-// their bytes, the host builds the table and the block header (rc_deflate_model.h).  Synchronous, once per ctx (and per rc_ctx_refit_model).
-static int fit_deflate_model(rc_ctx *c, const void *frames_dev, uint32_t n)
-{
-    using namespace rc;
-    hipStream_t s = c->stream;
-    const Scratch &sc = c->sets[c->cur];
-    const uint32_t ns = n < 2 ? n : 2;
-    for (int k = 0; k < 2; ++k)
-        if (c->post_pending[k]) HIP_TRY(hipStreamWaitEvent(s, c->ev_post[k], 0));
-    HIP_TRY(hipMemsetAsync(c->d_dzhist, 0, 256 * 4, s));
-    launch_reduce(sc, frames_dev, ns, 1u, CODEC_DEFLATE, true, c->depth, s, nullptr, c->src_bytes);
-    launch_scans(sc, ns, true, true, s);
-    RecordParams rp;
-    rp.level = 1u; rp.emit = c->emit; rp.depth = c->depth; rp.first_frame_id = 0; rp.packed_slots = 1u;
-    rp.frame_bytes = c->geo().N * c->src_bytes;
-    rp.pix_mode = PIX_MODE_FLAT;
-    launch_assemble(sc, rp, ns, nullptr, nullptr, c->batch_seq, s);   // (the flat pass touches neither the records nor their offsets)
-    launch_pd_hist(sc, ns, c->depth, c->d_dzhist, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_dzhist, c->d_dzhist, 256 * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    dm_build_model(c->h_dzhist, c->h_dzm);   // (usable: the 97 % rule of fit_model - a stream the byte-wise code cannot shrink stays stored)
-    HIP_TRY(hipMemcpyAsync(c->d_dzm, c->h_dzm, sizeof(DeflateModel), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (Scratch &set : c->sets) set.zm_model = c->d_dzm;
     c->model_ready = true;
     return RC_OK;
 }
@@ -540,12 +539,8 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
 {
     using namespace rc;
     hipStream_t s = c->stream;
-    if (c->modelled && !c->model_ready) {
-        int r = fit_model(c, frames_dev, n);
-        if (r != RC_OK) return r;
-    }
-    if (c->dz_values && !c->model_ready) {
-        int r = fit_deflate_model(c, frames_dev, n);
+    if ((c->modelled || c->values == VALUES_DEFLATE_HUFF) && !c->model_ready) {
+        int r = fit_value_model(c, frames_dev, n);
         if (r != RC_OK) return r;
     }
     RecordParams rp;
@@ -610,24 +605,13 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     if (all_ev) HIP_TRY(hipEventRecord(ev[2], ps));
     launch_scans(sc, n, c->level != 3, c->emit != EMIT_RAW, ps);
     if (all_ev) HIP_TRY(hipEventRecord(ev[3], ps));
-    // modelled zstd, level 1: the residual stream is laid out flat, Huffman-coded in chunks, and placed behind the bitmap stream
-    // (rc_pix_huff.hip); its encoded size is part of the record layout
-    const bool pix_huff = c->modelled && c->level == 1 && (c->h_model->valid & ZM_PIX_CODE) && sc.pixraw;
-    if (pix_huff) {
+    // the value stage (rc_launch.h), where the ctx's table pays: the residual stream is laid out flat, Huffman-coded in chunks and placed
+    // behind the binary-map stream; its encoded size is part of the record layout
+    if (c->values_on) {
         rp.pix_mode = PIX_MODE_FLAT;
         launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
-        launch_pix_huff(sc, n, c->depth, ps);
-        launch_pix_scan(sc, n, c->depth, ps);
-        rp.pix_mode = PIX_MODE_SKIP;
-    }
-    // device DEFLATE, compression_level >= 2, level 1: the same stage in DEFLATE's container (rc_pix_deflate.hip) - flat pass, a dynamic-Huffman
-    // block per 32 KiB chunk that pays, sizes -> layout; a ctx whose table does not pay keeps the stored blocks
-    const bool pix_deflate = c->dz_values && c->h_dzm->usable && sc.pixraw;
-    if (pix_deflate) {
-        rp.pix_mode = PIX_MODE_FLAT;
-        launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
-        launch_pd_encode(sc, n, c->depth, ps);
-        launch_pd_scan(sc, n, c->depth, ps);
+        launch_values_encode(c->values, sc, n, c->depth, ps);
+        launch_values_scan(c->values, sc, n, c->depth, ps);
         rp.pix_mode = PIX_MODE_SKIP;
     }
     if (two && c->post_pending[k ^ 1]) {
@@ -645,8 +629,7 @@ static int enqueue_batch(rc_ctx *c, const void *frames_dev, uint32_t n, uint32_t
     launch_layout(sc, rp, n, out_cap, rec_off_dev, md_dev, ps);
     launch_assemble(sc, rp, n, out_dev, rec_off_dev, c->batch_seq, ps);
     ++c->batch_seq;
-    if (pix_huff) launch_pix_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
-    if (pix_deflate) launch_pd_gather(sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
+    if (c->values_on) launch_values_gather(c->values, sc, n, c->depth, 16, out_dev, rec_off_dev, ps);
     if (ev) HIP_TRY(hipEventRecord(ev[4], ps));
     if (two && c->post_pending[k ^ 1]) HIP_TRY(hipStreamWaitEvent(ps, c->ev_post[k ^ 1], 0));   // batches still COMPLETE in order
     HIP_TRY(hipEventRecord(c->ev_post[k], ps));

@@ -59,11 +59,7 @@ inline void dm_build_model(const uint32_t *hist256, DeflateModel *M, uint8_t *le
     uint16_t code[DM_SYMS];
     dm_canonical(len, DM_SYMS, DM_MAXBITS, code);
     for (int s = 0; s < DM_SYMS; ++s) M->code[s] = (uint16_t)(dm_reverse(code[s], len[s]) | ((uint32_t)len[s] << 12));
-    {   // the 97 % rule of the modelled zstd encoder (rc_api.hip::fit_model)
-        uint64_t bits = 0;
-        for (int v = 0; v < 256; ++v) bits += (uint64_t)hist[v] * len[v];
-        M->usable = (total != 0 && bits <= total * 8 * 97 / 100) ? 1u : 0u;
-    }
+    M->usable = zm_code_pays(hist256, M->code) ? 1u : 0u;
     // the lengths as code-length symbols
     struct Sym { uint8_t s, extra; };
     Sym syms[DM_SYMS + 1];

@@ -8,6 +8,9 @@
 
 namespace rc {
 
+struct ZstdModel;      // rc_zstd_block.h
+struct DeflateModel;   // rc_deflate_model.h
+
 // Scratch::comb: where a tile's packed residual stream lives
 constexpr uint32_t COMB_OFF = 0u;          // in pix_slots
 constexpr uint32_t COMB_BEHIND_BLOCK = 1u; // in the block's slot, at the next 16-byte boundary behind the block image (LZ4 / blosc: the image is
@@ -50,25 +53,25 @@ struct Scratch {
     BatchStatus *status = nullptr;     // [1] of this batch
     BatchStatus *first_err = nullptr;  // [1] shared by both scratch sets: first failed batch since the last rc_ctx_sync
                                        //     (code, frame, total = number of the batch among those enqueued since then)
-    // modelled zstd, residual stream (rc_pix_huff.hip): the frame's packed stream flat, its PIX_CHUNK-byte chunks encoded
-    uint8_t *pixraw = nullptr;         // [B][pixraw_stride]
+    // The value stage (ValueStage below): one pipeline, two formats.  Allocated only for a ctx that has the stage.
+    uint8_t *pixraw = nullptr;         // [B][pixraw_stride]           the frame's packed stream laid out flat (k_gather, PIX_MODE_FLAT)
     uint64_t pixraw_stride = 0;
-    uint8_t *pix_chunks = nullptr;     // [B][nchunk_max][PIX_SLOT]
-    uint32_t *chunk_size = nullptr;    // [B][nchunk_max]   encoded bytes (ZW_TREE flag: the chunk's literals are treeless)
-    uint32_t *chunk_off = nullptr;     // [B][nchunk_max]   exclusive prefix inside the frame
-    uint32_t *frame_pbytes = nullptr;  // [B]               sum of chunk_size
-    uint32_t nchunk_max = 0;
+    uint8_t *pix_chunks = nullptr;     // [B][nchunk_max][slot]        the encoded image of every chunk of the flat stream (chunk, slot: value_geom)
+    uint32_t *chunk_size = nullptr;    // [B][nchunk_max]              the chunk's bytes in the record | the format's flag (ZW_TREE: treeless literals, PD_CODED)
+    uint32_t *chunk_off = nullptr;     // [B][nchunk_max]              exclusive prefix of the sizes inside the frame
+    uint32_t *frame_pbytes = nullptr;  // [B]                          the encoded stream behind its frame header (DEFLATE: the Adler-32 included)
+    uint32_t nchunk_max = 0;           // chunks a frame can have
     // modelled zstd (CODEC_ZSTD_MODELLED, rc_zstd_model.h): the ctx's model on the device and what the block encoders need of it
-    const void *zm_model = nullptr;    // ZstdModel
+    const ZstdModel *zm_model = nullptr;
     const void *zm_lit_code = nullptr; // &model->lit_code
     uint32_t zm_valid = 0, zm_budget = 0, zm_seq_bits = 12;
     // level 2 (rc_l2.hip)
     u32x2 *l2_node = nullptr;          // [B][ntiles * TILE_PX] {parent id, accumulator} per set pixel, id = tile * TILE_PX + rank in the tile
     uint64_t l2_ids_per_frame = 0;
     uint16_t *l2_base = nullptr;       // [B][ntiles * 64] set pixels of a word's tile in front of the word (k_l2_dir)
-    // device DEFLATE, compression_level >= 2 (rc_pix_deflate.hip): the Huffman stage of the residual stream shares pixraw, pix_chunks
-    // ([B][nchunk_max][PD_SLOT]), chunk_size, chunk_off, frame_pbytes and zm_model (a DeflateModel) with the modelled zstd encoder's
+    // the value stage in DEFLATE's format (appended: every older field keeps its kernel-argument offset)
     uint32_t *chunk_aux = nullptr;     // [B][nchunk_max + 1][2]  the chunks' Adler-32 partials {A, W}; last entry: the stream's Adler-32
+    const DeflateModel *dz_model = nullptr;   // the ctx's table (rc_deflate_model.h)
 };
 
 // RecordParams::emit / rc_ctx::emit: the form of a record's two streams (rc_record.h).  Also the batched decoder's selector (rc_reader.hip,
@@ -93,7 +96,7 @@ constexpr int CODEC_BLOSC = 8;           // blosc1 block: bit-shuffle (typesize 
 
 // RecordParams::pix_mode: what k_gather / k_layout do with the level-1 residual stream
 constexpr uint32_t PIX_MODE_STORED = 0u; // it goes into the record as it is (stored chunks)
-constexpr uint32_t PIX_MODE_FLAT = 1u;   // ONLY the residual stream, flat, into Scratch::pixraw (input of the Huffman stage, rc_pix_huff.hip)
+constexpr uint32_t PIX_MODE_FLAT = 1u;   // ONLY the residual stream, flat, into Scratch::pixraw (input of the value stage)
 constexpr uint32_t PIX_MODE_SKIP = 2u;   // everything but the residual stream, whose encoded size is Scratch::frame_pbytes
 
 struct RecordParams {
@@ -129,19 +132,27 @@ void launch_assemble(const Scratch &sc, const RecordParams &rp, uint32_t B, uint
 // rc_gather.hip: k_gather, what launch_assemble runs for everything but level-2 value lists
 void launch_gather(const Scratch &sc, const RecordParams &rp, uint32_t B, uint8_t *out, const uint64_t *rec_off, uint32_t hdr_bitmap, uint32_t hdr_pix,
                    uint32_t batch_seq, hipStream_t s);
-// rc_pix_huff.hip: the packed residual stream of every frame (Scratch::pixraw) -> Huffman-coded zstd blocks -> the records
-constexpr uint32_t PIX_CHUNK = 1008, PIX_SLOT = 1024;
-void launch_pix_huff(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
-void launch_pix_scan(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);   // (rc_reduce.hip)
-void launch_pix_gather(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t level1_hdr, uint8_t *out, const uint64_t *rec_off,
-                       hipStream_t s);
-// rc_pix_deflate.hip: the packed residual stream of every frame (Scratch::pixraw) -> dynamic-Huffman DEFLATE blocks -> the records
-constexpr uint32_t PD_CHUNK = 1u << 15, PD_SLOT = PD_CHUNK + 32;   // the stored blocks' grid (rc_record.h::frame_fmt); a coded image is < PD_CHUNK + 5 bytes
-void launch_pd_hist(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t *hist_dev, hipStream_t s);
-void launch_pd_encode(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
-void launch_pd_scan(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
-void launch_pd_gather(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t level1_hdr, uint8_t *out, const uint64_t *rec_off,
-                      hipStream_t s);
+// The value stage: a ctx's Huffman stage for the level-1 residual stream (uint16 / uint8 sources).  k_gather's flat pass into Scratch::pixraw ->
+// encode (a wavefront per chunk) -> scan (sizes -> offsets, per frame) -> gather behind the binary-map stream (rc_values.h, rc_pix_huff.hip,
+// rc_pix_deflate.hip), under a table fitted to a sample of the ctx's first batch (rc_api.hip::fit_value_model).
+enum ValueStage : uint32_t {
+    VALUES_NONE = 0,       // the stream is stored
+    VALUES_ZSTD_HUFF,      // modelled zstd: a block of treeless Huffman-coded literals per 1008 bytes
+    VALUES_DEFLATE_HUFF,   // device DEFLATE, compression_level >= 2: a dynamic-Huffman block per 32 KiB, the grid of the stored blocks (rc_record.h)
+};
+inline ValueStage value_stage_of(uint32_t emit, uint32_t clevel, uint32_t level)
+{
+    if (level == 1 && emit == EMIT_ZSTD && clevel != 0) return VALUES_ZSTD_HUFF;
+    return level == 1 && emit == EMIT_DEFLATE && clevel >= 2 ? VALUES_DEFLATE_HUFF : VALUES_NONE;
+}
+constexpr uint32_t PIX_CHUNK = 1008, PIX_SLOT = 1024, PD_CHUNK = 1u << 15, PD_SLOT = PD_CHUNK + 32;   // (a coded DEFLATE image is < PD_CHUNK + 5 bytes)
+struct ValueGeom { uint32_t chunk, slot; };   // bytes of the flat stream per chunk, bytes between two chunks' images in Scratch::pix_chunks
+inline ValueGeom value_geom(ValueStage kind) { return kind == VALUES_DEFLATE_HUFF ? ValueGeom{PD_CHUNK, PD_SLOT} : ValueGeom{PIX_CHUNK, PIX_SLOT}; }
+void launch_values_encode(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
+void launch_values_scan(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s);
+void launch_values_gather(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, uint32_t level1_hdr, uint8_t *out, const uint64_t *rec_off,
+                          hipStream_t s);
+void launch_pd_hist(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t *hist_dev, hipStream_t s);   // the DEFLATE fit's sample: byte histogram of pixraw
 // rc_lz4.hip
 struct Lz4Block { uint64_t src_off; uint32_t size; uint32_t raw; };
 void launch_lz4_encode_buffer(const Scratch &sc, hipStream_t s, bool events = false);  // sc.bitmap = the buffer, sc.nb = its length
@@ -164,7 +175,6 @@ void launch_zstd_sample(const Scratch &sc, uint32_t B, bool with_pix, uint32_t d
 size_t zstd_model_bytes();
 size_t zstd_sample_bytes();
 void zstd_model_from_sample(const void *sample_host, void *model_host, uint32_t speed_permille = 0);   // (rc_zstd_model.h::zm_build_model)
-struct ZstdModel;
 void launch_zstd_gather(const Scratch &sc, uint8_t *out, hipStream_t s);
 size_t zstd_tables_bytes();
 void zstd_tables_host(void *dst);  // rc_reduce.hip: FLG | BD << 8 | HC << 16

@@ -14,8 +14,9 @@
 //   k_pd_scan     per frame: chunk sizes -> offsets, the stream's length and its Adler-32
 //   k_pd_gather   a wavefront per chunk: the coded image from its slot, or the stored block straight from the flat stream, behind the
 //                 binary-map stream; chunk 0's wavefront also writes the two header bytes and the trailer
-#include "rc_launch.h"
-#include "rc_record.h"
+#include <algorithm>
+
+#include "rc_values.h"
 #include "rc_deflate_block.h"
 #include "rc_deflate_model.h"
 
@@ -26,7 +27,6 @@ constexpr uint32_t PD_WIN = 1024;               // bytes per window: 16 per lane
 constexpr int PD_DW = 392;                      // LDS dwords per wavefront: the open dword + 1024 * 12 bits + slack for the OR of a straddling group
 constexpr uint32_t PD_CODED = 0x80000000u;      // chunk_size: the slot holds a coded image (otherwise the chunk is a stored block of the flat stream)
 
-__device__ __forceinline__ uint32_t pd_chunks(uint32_t npk) { return npk ? (npk + PD_CHUNK - 1) / PD_CHUNK : 1u; }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_last(wave_incl_scan(v)); }
 // the wavefront's LDS window passes from one phase to the next (all lanes' accesses of the phase before are ordered in front)
 __device__ __forceinline__ void pd_sync()
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(WG) void k_pd_encode(Scratch sc, uint32_t B, uint32
     __shared__ uint16_t s_code[DM_SYMS + 3];
     __shared__ uint32_t s_hdr[DM_HDR_WORDS];
     __shared__ __attribute__((aligned(16))) uint32_t s_out[WAVES][PD_DW];
-    const DeflateModel *M = reinterpret_cast<const DeflateModel *>(sc.zm_model);
+    const DeflateModel *M = sc.dz_model;
     if (threadIdx.x < (DM_SYMS + 3) / 2) reinterpret_cast<uint32_t *>(s_code)[threadIdx.x] = reinterpret_cast<const uint32_t *>(M->code)[threadIdx.x];
     if (threadIdx.x < DM_HDR_WORDS) s_hdr[threadIdx.x] = M->hdr[threadIdx.x];
     __syncthreads();
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(WG) void k_pd_encode(Scratch sc, uint32_t B, uint32
     const uint32_t lane = (uint32_t)lane_id();
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = pd_chunks(npk);
+    const uint32_t nch = value_chunks(npk, PD_CHUNK);
     const uint32_t hdr_bits = M->hdr_bits, usable = M->usable;
     const uint32_t eob = s_code[DM_EOB] & 0xFFFu, eob_len = s_code[DM_EOB] >> 12;
     uint32_t *o = s_out[w];
@@ -143,34 +143,16 @@ __global__ __launch_bounds__(WG) void k_pd_encode(Scratch sc, uint32_t B, uint32
         for (uint32_t w0 = 0; w0 < n; w0 += PD_WIN) {
             int vb;
             const u32x4 v = pd_load(src, n, w0 + 16u * lane, vb);
-            // codes of the lane's bytes, in groups of four (<= 48 bits): inside a group the FIRST byte is lowest
             uint64_t g[4];
-            uint32_t gb[4], nb = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint64_t a = 0;
-                uint32_t b = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (4 * k + j < vb) {
-                        const uint32_t cd = s_code[(v[k] >> (8 * j)) & 0xFFu];
-                        a |= (uint64_t)(cd & 0xFFFu) << b;
-                        b += cd >> 12;
-                    }
-                g[k] = a; gb[k] = b; nb += b;
-            }
+            uint32_t gb[4];
+            const uint32_t nb = value_codes<false>(v, vb, s_code, g, gb);
             const uint32_t binc = wave_incl_scan(nb);
             const uint32_t tot = wave_last(binc);
             uint32_t bit = carry + binc - nb;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (gb[k]) {
-                    const uint32_t wd = bit >> 5, s = bit & 31u;
-                    const uint64_t a = g[k] << s;
-                    const uint32_t top = s ? (uint32_t)(g[k] >> (64 - s)) : 0u;
-                    __hip_atomic_fetch_or(&o[wd], (uint32_t)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    if (a >> 32) __hip_atomic_fetch_or(&o[wd + 1], (uint32_t)(a >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    if (top) __hip_atomic_fetch_or(&o[wd + 2], top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    window_or(o, bit, g[k]);
                     bit += gb[k];
                 }
             pd_sync();
@@ -198,10 +180,13 @@ __global__ __launch_bounds__(WG) void k_pd_encode(Scratch sc, uint32_t B, uint32
     }
 }
 
-void launch_pd_encode(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s)
+// (DEFLATE: at most PD_WG_PER_FRAME workgroups per frame, fewer where a frame cannot have that many chunks)
+static dim3 pd_grid(const Scratch &sc, uint32_t B) { return dim3(std::min((sc.nchunk_max + WAVES - 1) / WAVES, (uint32_t)PD_WG_PER_FRAME), B); }
+
+void launch_values_encode(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s)
 {
-    const uint32_t wgs = (sc.nchunk_max + WAVES - 1) / WAVES;
-    hipLaunchKernelGGL(k_pd_encode, dim3(wgs < (uint32_t)PD_WG_PER_FRAME ? wgs : (uint32_t)PD_WG_PER_FRAME, B), dim3(WG), 0, s, sc, B, depth);
+    if (kind == VALUES_ZSTD_HUFF) return launch_pix_huff(sc, B, depth, s);
+    if (kind == VALUES_DEFLATE_HUFF) hipLaunchKernelGGL(k_pd_encode, pd_grid(sc, B), dim3(WG), 0, s, sc, B, depth);   // (VALUES_NONE: no table, no flat stream - nothing to launch)
 }
 
 // per frame: the chunks' sizes -> offsets behind the stream's two header bytes; frame_pbytes = images + trailer; the Adler-32 from the partials
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(WG) void k_pd_scan(Scratch sc, uint32_t depth)
     __shared__ uint32_t s_sz[WG], s_A[WG], s_W[WG];
     const uint32_t f = blockIdx.x, t = threadIdx.x;
     const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = pd_chunks(npk);
+    const uint32_t nch = value_chunks(npk, PD_CHUNK);
     const uint32_t per = (nch + WG - 1) / WG, lo = min(t * per, nch), hi = min(lo + per, nch);
     const uint32_t *size = sc.chunk_size + (uint64_t)f * sc.nchunk_max;
     uint32_t *aux = sc.chunk_aux + 2 * (uint64_t)f * (sc.nchunk_max + 1);
@@ -236,22 +221,10 @@ __global__ __launch_bounds__(WG) void k_pd_scan(Scratch sc, uint32_t depth)
     }
 }
 
-void launch_pd_scan(const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s)
+void launch_values_scan(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pd_scan, dim3(B), dim3(WG), 0, s, sc, depth);
-}
-
-// size bytes from src (4-byte aligned, readable up to the next dword boundary behind src + size + 4) to dst (any alignment), by one wavefront:
-// destination dword j = source bytes [head + 4j, +4) = the byte funnel of source dwords j, j + 1
-__device__ __forceinline__ void pd_copy(uint8_t *dst, const uint8_t *src, uint32_t size, uint32_t lane)
-{
-    const uint32_t head = min(size, (uint32_t)((4u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u));
-    const uint32_t nd = (size - head) >> 2, tail = (size - head) & 3u;
-    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
-    for (uint32_t j = lane; j < nd; j += 64)
-        reinterpret_cast<uint32_t *>(dst + head)[j] = __builtin_amdgcn_alignbyte(s32[j + 1], s32[j], head);
-    if (lane < head) dst[lane] = src[lane];
-    if (lane < tail) dst[head + 4 * nd + lane] = src[head + 4 * nd + lane];
+    if (kind == VALUES_ZSTD_HUFF) return launch_pix_scan(sc, B, depth, s);
+    if (kind == VALUES_DEFLATE_HUFF) hipLaunchKernelGGL(k_pd_scan, dim3(B), dim3(WG), 0, s, sc, depth);   // (VALUES_NONE: no table, no flat stream - nothing to launch)
 }
 
 __global__ __launch_bounds__(WG) void k_pd_gather(Scratch sc, uint32_t B, uint32_t depth, uint32_t rec_hdr, uint8_t *__restrict__ out,
@@ -262,7 +235,7 @@ __global__ __launch_bounds__(WG) void k_pd_gather(Scratch sc, uint32_t B, uint32
     const uint32_t lane = (uint32_t)lane_id();
     const uint32_t w = threadIdx.x >> 6;
     const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = pd_chunks(npk);
+    const uint32_t nch = value_chunks(npk, PD_CHUNK);
     const FrameFmt ff = frame_fmt(EMIT_DEFLATE);
     // the residual stream starts behind the record header and the binary-map stream: [78 01][chunk images][Adler-32]
     uint8_t *pf = out + rec_off[f] + rec_hdr + ff.hdr + sc.frame_cbytes[f] + ff.end;
@@ -270,14 +243,14 @@ __global__ __launch_bounds__(WG) void k_pd_gather(Scratch sc, uint32_t B, uint32
         const uint64_t fc = (uint64_t)f * sc.nchunk_max + c;
         const uint32_t word = sc.chunk_size[fc], off = sc.chunk_off[fc];
         uint8_t *dst = pf + ff.hdr + off;
-        if (word & PD_CODED) pd_copy(dst, sc.pix_chunks + fc * PD_SLOT, word & ~PD_CODED, lane);
+        if (word & PD_CODED) wave_copy_unaligned(dst, sc.pix_chunks + fc * PD_SLOT, word & ~PD_CODED, lane);
         else {   // stored block: [BFINAL][LEN][NLEN] and the chunk of the flat stream as it is
             const uint32_t n = word - 5;
             if (lane == 0) {
                 dst[0] = c + 1 == nch ? 1 : 0;
                 dst[1] = (uint8_t)n; dst[2] = (uint8_t)(n >> 8); dst[3] = (uint8_t)~n; dst[4] = (uint8_t)(~n >> 8);
             }
-            pd_copy(dst + 5, sc.pixraw + (uint64_t)f * sc.pixraw_stride + (uint64_t)c * PD_CHUNK, n, lane);
+            wave_copy_unaligned(dst + 5, sc.pixraw + (uint64_t)f * sc.pixraw_stride + (uint64_t)c * PD_CHUNK, n, lane);
         }
         if (c == 0 && lane == 0) {
             pf[0] = 0x78; pf[1] = 0x01;   // CMF, FLG as the binary-map stream's (rc_record.h)
@@ -286,10 +259,11 @@ __global__ __launch_bounds__(WG) void k_pd_gather(Scratch sc, uint32_t B, uint32
     }
 }
 
-void launch_pd_gather(const Scratch &sc, uint32_t B, uint32_t depth, uint32_t rec_hdr, uint8_t *out, const uint64_t *rec_off, hipStream_t s)
+void launch_values_gather(ValueStage kind, const Scratch &sc, uint32_t B, uint32_t depth, uint32_t rec_hdr, uint8_t *out, const uint64_t *rec_off,
+                          hipStream_t s)
 {
-    const uint32_t wgs = (sc.nchunk_max + WAVES - 1) / WAVES;
-    hipLaunchKernelGGL(k_pd_gather, dim3(wgs < (uint32_t)PD_WG_PER_FRAME ? wgs : (uint32_t)PD_WG_PER_FRAME, B), dim3(WG), 0, s, sc, B, depth, rec_hdr, out, rec_off);
+    if (kind == VALUES_ZSTD_HUFF) return launch_pix_gather(sc, B, depth, rec_hdr, out, rec_off, s);
+    if (kind == VALUES_DEFLATE_HUFF) hipLaunchKernelGGL(k_pd_gather, pd_grid(sc, B), dim3(WG), 0, s, sc, B, depth, rec_hdr, out, rec_off);   // (VALUES_NONE: no table, no flat stream - nothing to launch)
 }
 
 }  // namespace rc

@@ -14,7 +14,7 @@
 //                 lowest bits), LDS atomic ORs build the stream, coalesced dword stores write the chunk's slot
 //   k_pix_scan    (rc_reduce.hip, next to k_scan_frames whose helpers it shares) sizes -> offsets, tree into the first chunk
 //   k_pix_gather  copies the chunks behind the frame header of the record's residual stream
-#include "rc_launch.h"
+#include "rc_values.h"
 #include "rc_lz4_block.h"
 #include "rc_zstd_block.h"
 #include "rc_zstd_wave.h"
@@ -24,24 +24,19 @@ namespace rc {
 constexpr int PH_WG_PER_FRAME = 16;   // x WAVES wavefronts loop over a frame's chunks (333 chunks per 4096^2 frame at 1 %)
 constexpr int PH_DW = 360;            // LDS dwords per wavefront: 6 + 1008 * 11 / 8 = 1392 bytes + slack for the OR window
 
-__device__ __forceinline__ uint32_t pix_packed_bytes(uint32_t nnz, uint32_t depth)
-{
-    return depth == 16 ? nnz * 2u : (uint32_t)(((uint64_t)nnz * depth + 7) >> 3);
-}
-
 __global__ __launch_bounds__(WG) void k_pix_huff(Scratch sc, uint32_t B, uint32_t depth)
 {
     __shared__ uint16_t s_code[256];
     __shared__ __attribute__((aligned(16))) uint32_t s_out[WAVES][PH_DW];
-    const ZstdModel *M = reinterpret_cast<const ZstdModel *>(sc.zm_model);
+    const ZstdModel *M = sc.zm_model;
     if (threadIdx.x < 128) reinterpret_cast<uint32_t *>(s_code)[threadIdx.x] = reinterpret_cast<const uint32_t *>(M->pix_code)[threadIdx.x];
     __syncthreads();
     const uint32_t f = blockIdx.y;
     if (f >= B) return;
     const int lane = lane_id();
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t npk = pix_packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = npk ? (npk + PIX_CHUNK - 1) / PIX_CHUNK : 1u;
+    const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
+    const uint32_t nch = value_chunks(npk, PIX_CHUNK);
     const bool can = (sc.zm_valid & ZM_PIX_CODE) != 0;
     const uint32_t desc_len = M->pix_desc_len;
     uint32_t *out32 = s_out[w];
@@ -53,22 +48,9 @@ __global__ __launch_bounds__(WG) void k_pix_huff(Scratch sc, uint32_t B, uint32_
         const int vb = max(0, min(16, (int)n - 16 * lane));     // this lane's valid bytes
         u32x4 v = {0u, 0u, 0u, 0u};
         if (vb > 0) v = *reinterpret_cast<const u32x4 *>(src + 16 * lane);   // rows and chunks are 16-byte aligned and padded
-        // codes of the lane's bytes, in groups of four (<= 44 bits): inside a group the LAST byte is lowest
         uint64_t g[4];
-        uint32_t gb[4], nb = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            uint64_t a = 0;
-            uint32_t b = 0;
-#pragma unroll
-            for (int j = 3; j >= 0; --j)
-                if (4 * k + j < vb) {
-                    const uint32_t cd = s_code[(v[k] >> (8 * j)) & 0xFFu];
-                    a |= (uint64_t)(cd & 0xFFFu) << b;
-                    b += cd >> 12;
-                }
-            g[k] = a; gb[k] = b; nb += b;
-        }
+        uint32_t gb[4];
+        const uint32_t nb = value_codes<true>(v, vb, s_code, g, gb);   // (<= 44 bits per group)
         const uint32_t binc = wave_incl_scan(nb);
         const uint32_t hbits = wave_last(binc);
         const uint32_t hbytes = (hbits + 8) >> 3;
@@ -83,12 +65,7 @@ __global__ __launch_bounds__(WG) void k_pix_huff(Scratch sc, uint32_t B, uint32_
 #pragma unroll
             for (int k = 3; k >= 0; --k)
                 if (gb[k]) {
-                    const uint32_t wd = bit >> 5, s = bit & 31u;
-                    const uint64_t a = g[k] << s;
-                    const uint32_t top = s ? (uint32_t)(g[k] >> (64 - s)) : 0u;
-                    __hip_atomic_fetch_or(&out32[wd], (uint32_t)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    if (a >> 32) __hip_atomic_fetch_or(&out32[wd + 1], (uint32_t)(a >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    if (top) __hip_atomic_fetch_or(&out32[wd + 2], top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    window_or(out32, bit, g[k]);
                     bit += gb[k];
                 }
             if (lane == 0) {
@@ -129,27 +106,17 @@ __global__ __launch_bounds__(WG) void k_pix_gather(Scratch sc, uint32_t B, uint3
 {
     const uint32_t f = blockIdx.y;
     if (f >= B || sc.status->code != 0) return;
-    const int lane = lane_id();
+    const uint32_t lane = (uint32_t)lane_id();
     const uint32_t w = threadIdx.x >> 6;
-    const uint32_t npk = pix_packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = npk ? (npk + PIX_CHUNK - 1) / PIX_CHUNK : 1u;
+    const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
+    const uint32_t nch = value_chunks(npk, PIX_CHUNK);
     // the residual stream starts behind the record header and the bitmap stream: [6-byte frame header][blocks]
     uint8_t *rec = out + rec_off[f];
     const uint32_t cb = 6 + sc.frame_cbytes[f];   // the bitmap stream: frame header + its blocks
     uint8_t *pf = rec + rec_hdr + cb;
     for (uint32_t c = blockIdx.x * WAVES + w; c < nch; c += gridDim.x * WAVES) {
         const uint64_t fc = (uint64_t)f * sc.nchunk_max + c;
-        const uint32_t size = sc.chunk_size[fc], off = sc.chunk_off[fc];
-        const uint8_t *src = sc.pix_chunks + fc * PIX_SLOT;   // 4-byte aligned (slots are PIX_SLOT apart)
-        uint8_t *dst = pf + 6 + off;                          // any alignment
-        // aligned dword stores: destination dword j = source bytes [head + 4j, +4) = the byte funnel of source dwords j, j+1
-        const uint32_t head = min(size, (uint32_t)((4u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u));
-        const uint32_t nd = (size - head) >> 2, tail = (size - head) & 3u;
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
-        for (uint32_t j = lane; j < nd; j += 64)
-            reinterpret_cast<uint32_t *>(dst + head)[j] = __builtin_amdgcn_alignbyte(s32[j + 1], s32[j], head);
-        if ((uint32_t)lane < head) dst[lane] = src[lane];
-        if ((uint32_t)lane < tail) dst[head + 4 * nd + lane] = src[head + 4 * nd + lane];
+        wave_copy_unaligned(pf + 6 + sc.chunk_off[fc], sc.pix_chunks + fc * PIX_SLOT, sc.chunk_size[fc], lane);
         if (c == 0 && lane == 0) {   // magic, Frame_Header_Descriptor 0, 1 KiB window (blocks regenerate <= 1008 bytes)
             pf[0] = 0x28; pf[1] = 0xB5; pf[2] = 0x2F; pf[3] = 0xFD; pf[4] = 0; pf[5] = 0;
         }

@@ -12,7 +12,7 @@
 #include <type_traits>
 
 #include "rc_launch.h"
-#include "rc_record.h"
+#include "rc_values.h"
 #include "rc_pack.h"
 #ifdef RC_PHASE_TIMING
 __device__ unsigned long long g_phase[16];
@@ -888,16 +888,16 @@ __device__ __forceinline__ void zstd_place_defs(const uint32_t *__restrict__ row
     zstd_rewrite_defs(row, slots, stride, tree, tl, sdesc, sl, t_tree, t_seq, 3u, s_img, &s_pos);
 }
 
-// Residual stream of the modelled zstd encoder (rc_pix_huff.hip): per frame, sizes of the encoded chunks -> offsets, total;
-// the tree goes into the first Huffman-coded chunk.
+// The value stage's scan in the zstd format (rc_pix_huff.hip): per frame, sizes of the encoded chunks -> offsets, total; the tree goes into
+// the first Huffman-coded chunk.
 __global__ __launch_bounds__(SCAN_T) void k_pix_scan(Scratch sc, uint32_t depth)
 {
     __shared__ uint32_t sm[SCAN_W];
     __shared__ uint32_t s_adj[4];
     const uint32_t f = blockIdx.x;
-    const ZstdModel *M = reinterpret_cast<const ZstdModel *>(sc.zm_model);
+    const ZstdModel *M = sc.zm_model;
     const uint32_t npk = packed_bytes(sc.frame_nnz[f], depth);
-    const uint32_t nch = npk ? (npk + PIX_CHUNK - 1) / PIX_CHUNK : 1u;
+    const uint32_t nch = value_chunks(npk, PIX_CHUNK);
     uint32_t *row = sc.chunk_size + (uint64_t)f * sc.nchunk_max;
     zstd_place_defs(row, nch, sc.pix_chunks + (uint64_t)f * sc.nchunk_max * PIX_SLOT, PIX_SLOT, M->pix_desc, M->pix_desc_len, nullptr, 0, s_adj);
     scan_row<16>(row, sc.chunk_off + (uint64_t)f * sc.nchunk_max, nch, sc.frame_pbytes + f, sm, s_adj);
@@ -917,7 +917,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_frames(Scratch sc, int with_cou
     const uint64_t fr = (uint64_t)f * n;
     if (with_blocks) {
         if (sc.zm_model) {
-            const ZstdModel *M = reinterpret_cast<const ZstdModel *>(sc.zm_model);
+            const ZstdModel *M = sc.zm_model;
             zstd_place_defs(sc.blk_size + fr, n, sc.blk_slots + fr * sc.blk_stride, sc.blk_stride, M->lit_desc, M->lit_desc_len, M->seq_desc,
                             M->seq_desc_len, s_adj);
         }
@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_fix(Scratch sc, int with_counts
         uint32_t tl = 0, sl = 0;
         const uint32_t t_tree = s_v[3], t_seq = s_v[4];
         if (sc.zm_model) {
-            const ZstdModel *M = reinterpret_cast<const ZstdModel *>(sc.zm_model);
+            const ZstdModel *M = sc.zm_model;
             tl = t_tree != 0xFFFFFFFFu ? M->lit_desc_len : 0u;
             sl = t_seq != 0xFFFFFFFFu ? M->seq_desc_len : 0u;
             const uint32_t mine = (t_tree >= lo && t_tree < hi ? 1u : 0u) | (t_seq >= lo && t_seq < hi ? 2u : 0u);

@@ -98,6 +98,15 @@ inline void zm_huf_codes(const uint8_t *len, uint16_t *code_len12, int maxbits =
     for (int s = 0; s < 256; ++s) code_len12[s] = (uint16_t)(next[len[s]]++ | ((uint32_t)len[s] << 12));
 }
 
+// A residual stream gets a byte-wise code (code | length << 12 per value) only if the code takes 3 % off the sample; one it cannot shrink -
+// bit-packed depths - stays stored.  The rule of both formats of the value stage (rc_api.hip::fit_value_model, rc_deflate_model.h).
+inline bool zm_code_pays(const uint32_t *hist256, const uint16_t *code_len12)
+{
+    uint64_t bits = 0, total = 0;
+    for (int v = 0; v < 256; ++v) { bits += (uint64_t)hist256[v] * (code_len12[v] >> 12); total += hist256[v]; }
+    return total != 0 && bits <= total * 8 * 97 / 100;
+}
+
 // ---- FSE (table descriptions and the 2-state stream of the Huffman weights) -------------------------------------------
 // Normalised counts summing to 2^log.  `need[s]`: symbol s must stay encodable even if the sample never saw it (probability
 // "less than one", -1).  Returns false when the alphabet does not fit the table.

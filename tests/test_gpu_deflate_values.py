@@ -118,6 +118,27 @@ def test_data_unlike_the_table_and_refit(hip, orc):
     ctx.close()
 
 
+def test_more_than_4096_tiles_take_the_segmented_scans(hip, orc):
+    """4097 tiles: the tile scans are k_scan_seg / k_scan_fix, which must leave a DEFLATE ctx's block-size words as they are (no zstd model).
+    Three chunks (two inner, one final); two calls on one ctx - the second starts with the table fitted."""
+    ny, nx, d = 4097, 4096, 16
+    rng = np.random.default_rng(41)
+    dark = np.zeros((ny, nx), np.uint16)
+    thr = orc.threshold(dark, 0)
+    flat = np.zeros(ny * nx, np.uint16)
+    flat[rng.integers(0, ny * nx, 33600)] = rng.integers(1, 2048, 33600)      # 0.2 % of the pixels
+    ctx = hip.ReduceContext(nx, ny, d, 1, 1, 0, 2, 0, max_batch=1, device_zlib=True)
+    ctx.set_dark(dark, 0)
+    table = None
+    for call, frame in enumerate((flat.reshape(ny, nx), flat[::-1].reshape(ny, nx).copy())):
+        out, rec, md = ctx.reduce_compress_batch(frame[None], first_frame_id=call)
+        assert 2 << 15 < int(md[0][2]) <= 3 << 15
+        cp, stored, t = _check_record(orc, _records(out, rec, 1)[0], frame, thr, d, call, md[0], table)
+        assert t is not None and cp < stored
+        table = t
+    ctx.close()
+
+
 def test_uint8_sources(hip, orc):
     ny, nx = 130, 260
     rng = np.random.default_rng(3)

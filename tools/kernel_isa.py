@@ -37,8 +37,8 @@ def main():
                 ins = [l.split("//")[0].strip() for l in body.splitlines() if l.strip() and not l.strip().startswith("<")]
                 ops = [i.split()[0] for i in ins if i]
                 cls = lambda p: sum(1 for o in ops if o.startswith(p))
-                meta = re.search(r"\.name:\s+%s\n(.*?)\.wavefront_size" % re.escape(name), notes, re.S)
-                mt = meta.group(1) if meta else ""
+                # the kernel's entry of amdhsa.kernels: keys in alphabetical order, .group_segment_fixed_size in front of .name
+                mt = next((e for e in notes.split("\n  - .agpr_count") if re.search(r"\.name:\s+%s\n" % re.escape(name), e)), "")
                 g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, mt) or [None, "?"])[1]
                 print("%s\n  instructions %d: v_ %d  s_ %d  ds_ %d  global_ %d  scratch_ %d  branches %d  s_waitcnt %d | vgpr %s spill %s sgpr %s sgpr-spill %s scratch %s B lds %s"
                       % (name, len(ops), cls("v_"), cls("s_"), cls("ds_"), cls("global_"), cls("scratch_"), sum(1 for o in ops if "branch" in o), cls("s_waitcnt"),
