@@ -277,6 +277,13 @@ int64_t rc_unpack_frame_sparse(uint32_t nx, uint32_t ny, uint32_t bit_depth, con
  * recode_compressors.py:61-76) of the shape this library writes: version 2, typesize 8, blocks of 512 bytes that are not split, bit-shuffled
  * or not shuffled, or a "memcpyed" chunk of exactly 16 + nbytes bytes (either stream; the value stream only so).  A chunk whose header's
  * nbytes / cbytes disagree with the frame, or whose block starts / sizes leave the stream or exceed a block's LZ4 bound, is RC_ERR_CORRUPT.
+ * scheme RC_SCHEME_ZLIB_DEVICE (op_mode 1, reduction levels 1 and 3; rc_inflate.hip): the zlib streams of a compression_scheme-0 file that
+ * this library's device DEFLATE encoder wrote - a fixed-Huffman or stored block per 512 map bytes, a literals-only dynamic-Huffman or
+ * stored block per 32 KiB of values, coded blocks closed by an empty stored block.  The host does not walk them: the device finds the
+ * blocks' starts itself.  Any other zlib stream (stock zlib's among them) is RC_ERR_UNSUPPORTED - from the call, or, for a stream only
+ * the device can tell apart, from rc_expand_frames_wait - with nothing written to the output: use the stock decoder
+ * (rc_host_decode_streams).  The Adler-32 trailers are not checked.  scheme 0 itself stays RC_ERR_UNSUPPORTED, as does rc_expand_frames_l2
+ * with RC_SCHEME_ZLIB_DEVICE.
  * reduction_level 2: the binary map expands exactly as at level 3 (value 1) and the statistics stream - sizes[i][1] bytes - is stepped
  * over, as the reference's reader does (recode_reader.py:413-440: get_frame_sparse(level, map, None)); with triplets NULL this is the
  * counting call that sizes the buffers of rc_expand_frames_l2.  Anything else returns RC_ERR_UNSUPPORTED before any work is done and the caller falls back to

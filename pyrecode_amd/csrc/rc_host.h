@@ -292,10 +292,15 @@ struct ReadRes {
     PinBuf rd_head;                                        // page-locked (the utility context's PinMem): decoding tables + per-frame index arrays
     PinBuf h_res;                                          // ... nnz prefix (n + 1) and the error word, as the device left them (uint64)
     PinBuf h_blob;                                         // ... host copy of a DEVICE-resident input, for the header walk
+    DevBuf d_inf;                                          // device inflate (rc_inflate.hip): stream descriptors, candidate / link / unit tables
+    PinBuf h_inf;                                          // ... the descriptors as the host wrote them
     // a submitted batch waiting for its rc_expand_frames_wait
     bool pending = false;
     uint32_t n = 0, level = 0, bit_depth = 0;
     uint64_t cap = 0;
+    uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be
+    uint32_t late_value_bytes = 0;                         // good (device inflate), its COO value width (0: none) and whether it is COO at all
+    bool late_coo = false;
     std::vector<uint32_t> pv_bytes;
 };
 

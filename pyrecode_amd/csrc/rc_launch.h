@@ -10,6 +10,7 @@ namespace rc {
 
 struct ZstdModel;      // rc_zstd_block.h
 struct DeflateModel;   // rc_deflate_model.h
+struct InfStream;      // rc_inflate.h
 
 // Scratch::comb: where a tile's packed residual stream lives
 constexpr uint32_t COMB_OFF = 0u;          // in pix_slots
@@ -190,6 +191,12 @@ __host__ __device__ inline const uint8_t *residual_src(const S &sc, uint64_t ft,
     }
     return reinterpret_cast<const uint8_t *>(sc.pix_slots) + ft * sc.pix_slot_bytes;
 }
+
+// rc_inflate.hip: the batched device inflate of rc_expand_frames.  streams: n_map binary-map streams, then n_val value streams; *_cap_max /
+// *_units_max: the largest candidate room / unit count among them; cand_pos, link: one entry per candidate room, unit_cand: per unit, ncand: per stream
+void launch_inflate(const uint8_t *data, const InfStream *streams, uint32_t n_map, uint32_t n_val, uint32_t map_cap_max, uint32_t map_units_max,
+                    uint32_t val_cap_max, uint32_t val_units_max, uint32_t *cand_pos, uint32_t *ncand, uint32_t *link, uint32_t *unit_cand,
+                    uint8_t *out, int *err, hipStream_t s);
 
 void launch_roi_components(const void *frames, const void *thr, uint64_t N, uint32_t nx, uint32_t n, uint32_t first_frame_id, uint32_t gap,
                            uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t *counts, hipStream_t s, uint32_t src_bytes = 2);

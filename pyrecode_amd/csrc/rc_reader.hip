@@ -3,6 +3,7 @@
 // decoders (rc_zstd_dec.hip) and the sparse expand (rc_expand.hip) - n frames, both streams, one call, no host round trip in between.
 // Replaces ReCoDeReader._get_frame_sparse (pyrecode/recode_reader.py:379-471) for n frames at once.
 #include "rc_host.h"
+#include "rc_inflate.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
 namespace {
@@ -120,9 +121,11 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (l2out && level != 2) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2: reduction level 2");
     if (l2out && (bit_depth < 8 || bit_depth > 16))
         return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames_l2: bit_depth 8..16 (narrower fields: the stream's length does not give their count)");
-    if (op_mode != 0 && scheme != RC_SCHEME_LZ4 && scheme != RC_SCHEME_ZSTD && scheme != RC_SCHEME_BLOSC_LZ4)
+    if (op_mode != 0 && scheme != RC_SCHEME_LZ4 && scheme != RC_SCHEME_ZSTD && scheme != RC_SCHEME_BLOSC_LZ4 && scheme != RC_SCHEME_ZLIB_DEVICE)
         return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: scheme has no batched device decoder");
-    const uint32_t codec = op_mode == 0 ? EMIT_RAW : scheme;   // (EMIT_LZ4 / EMIT_ZSTD / EMIT_BLOSC are the scheme codes)
+    if (op_mode != 0 && scheme == RC_SCHEME_ZLIB_DEVICE && level == 2)
+        return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: the device inflate reads reduction levels 1 and 3");
+    const uint32_t codec = op_mode == 0 ? EMIT_RAW : scheme;   // (EMIT_LZ4 / EMIT_ZSTD / EMIT_BLOSC / EMIT_DEFLATE are the scheme codes)
     const bool vstream = level != 3;              // the frames carry a value stream (level 1: residuals, level 2: statistics) ...
     const bool values = level == 1 || l2out;      // ... which this call decodes
     const uint32_t klevel = level == 1 ? 1u : l2out ? 2u : 3u;   // what the expand kernels see: 2 = value 1, COO without the value array
@@ -292,6 +295,13 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
                     rr = lz4_index_frame(walk, o + cb, cp, n + f, 0, npk, all, RAW, &got);
                     if (rr == ZD_OK && got != npk) rr = ZD_CORRUPT;
                 }
+            } else if (codec == EMIT_DEFLATE) {
+                // No walk: the units' starts are found on the device (rc_inflate.hip).  The host only refuses what is plainly not the
+                // device encoder's: another zlib header, or a first block of a type the stream cannot start with.
+                auto own = [&](uint64_t at, uint64_t sz, uint32_t coded) {
+                    return sz >= 8 && sz < (1ull << 28) && walk[at] == 0x78 && walk[at + 1] == 0x01 && ((walk[at + 2] & 6u) == 0u || (walk[at + 2] & 6u) == coded);
+                };
+                if (!own(o, cb, 2u) || (values && !own(o + cb, cp, 4u))) rr = ZD_FOREIGN;
             } else if (codec == EMIT_BLOSC) {
                 // (every block of the map to the frame's list - stored ones too: they are shuffled like the others; a memcpyed chunk to the copy list)
                 rr = blosc_index_stream(walk, o, cb, f, nb, true, BM, RAW);
@@ -374,6 +384,35 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         launch_block_decode(EMIT_ZSTD, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, u.stream2);
         HIP_TRY(hipEventRecord(u.ev_b, u.stream2));
     }
+    if (codec == EMIT_DEFLATE) {
+        // stream descriptors (page-locked, one copy) and the tables of the candidate / chain scheme, all in one device buffer
+        const uint32_t ns = values ? 2 * n : n;
+        uint64_t cand_total = 0, unit_total = 0;
+        uint32_t cap_max[2] = {0, 0}, units_max[2] = {0, 0};
+        if ((r = u.h_inf.ensure(U.hmem, (uint64_t)ns * sizeof(InfStream))) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+        InfStream *st = u.h_inf.as<InfStream>();
+        for (uint32_t j = 0; j < ns; ++j) {
+            const uint32_t f = j < n ? j : j - n, v = j < n ? 0u : 1u;
+            InfStream &S = st[j];
+            S.src = foff[f] + (v ? sizes[3 * f] : 0u);
+            S.dst = v ? pv_base[f] : base2[f];
+            S.csize = sizes[3 * f + v];
+            S.size = v ? sizes[3 * f + 2] : (uint32_t)nb;
+            S.unit = v ? INF_VAL_UNIT : INF_MAP_UNIT;
+            S.units = inf_units(S.size, S.unit);
+            S.cand0 = (uint32_t)cand_total; S.cap = 2 * S.units + INF_CAND_EXTRA;
+            S.unit0 = (uint32_t)unit_total; S.pad = 0;
+            cand_total += S.cap; unit_total += S.units;
+            cap_max[v] = std::max(cap_max[v], S.cap); units_max[v] = std::max(units_max[v], S.units);
+        }
+        if (cand_total >= (1ull << 31)) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
+        const uint64_t o_tab = ((uint64_t)ns * sizeof(InfStream) + 15) & ~15ull;
+        if ((r = u.d_inf.ensure(U.dmem, o_tab + (2 * cand_total + unit_total + ns) * 4 + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+        HIP_TRY(hipMemcpyAsync(u.d_inf.p, st, (uint64_t)ns * sizeof(InfStream), hipMemcpyHostToDevice, s));
+        uint32_t *d_cand = reinterpret_cast<uint32_t *>(u.d_inf.p + o_tab), *d_link = d_cand + cand_total, *d_unit = d_link + cand_total, *d_ncand = d_unit + unit_total;
+        launch_inflate(d_data, u.d_inf.as<InfStream>(), n, ns - n, cap_max[0], units_max[0], cap_max[1], units_max[1], d_cand, d_ncand, d_link, d_unit, d_out,
+                       d_err, s);
+    }
     if (cbm_max) launch_bitmap_decode_compact(codec, d_data, d_cbm_list, d_src_base, n, cbm_max, d_bm_tab, U.zd_predef, d_out, d_base2, nb, d_err, s);
     if (n_bm && codec == EMIT_BLOSC) launch_blosc_decode_blocks(d_data, d_bm_list, n, bm_max, d_out, d_base2, d_err, s);
     else if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
@@ -427,9 +466,15 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
-    if (host_async && cap) HIP_TRY(hipMemcpyAsync(host_async, triplets, cap * esz, hipMemcpyDeviceToHost, s));
+    // (the device inflate may refuse a batch on the device - "use the stock decoder" - and then nothing may reach the caller's output: its
+    // page-locked destination is filled by rc_expand_frames_wait, once the batch is known to be good)
+    const bool late_copy = host_async && codec == EMIT_DEFLATE;
+    if (host_async && cap && !late_copy) HIP_TRY(hipMemcpyAsync(host_async, triplets, cap * esz, hipMemcpyDeviceToHost, s));
     if (submit_only) {   // (dev_out is a precondition, checked above)
         HIP_TRY(hipEventRecord(u.done, s));
+        u.late_dst = late_copy ? reinterpret_cast<uint8_t *>(host_async) : nullptr;
+        u.late_value_bytes = l2out ? 0 : coo;
+        u.late_coo = coo != 0;
         u.pending = true;
         u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = cap;
         u.pv_bytes.assign(pv_bytes, pv_bytes + n);
@@ -439,6 +484,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const int err = (int)(uint32_t)h_res[n + 1];
     memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
     const double t_4 = now();
+    if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     const uint64_t total = nnz_prefix[n];
     if (stats_short) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2: stats holds fewer entries than the frames have statistics");
@@ -560,8 +606,22 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
     const uint64_t *h_res = u.h_res.as<uint64_t>();
     const int err = (int)(uint32_t)h_res[n + 1];
     memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
+    if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     if (nnz_prefix[n] > u.cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
     if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
+    if (u.late_dst && nnz_prefix[n]) {
+        // the output staged in d_triplets keeps the caller's layout (triplet rows, or the COO arrays cap entries apart)
+        const uint64_t total = nnz_prefix[n];
+        const uint8_t *src = u.d_triplets.p;
+        if (!u.late_coo) HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 24, hipMemcpyDeviceToHost, u.stream));
+        else {
+            HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 4, hipMemcpyDeviceToHost, u.stream));
+            HIP_TRY(hipMemcpyAsync(u.late_dst + u.cap * 4, src + u.cap * 4, total * 4, hipMemcpyDeviceToHost, u.stream));
+            if (u.late_value_bytes)
+                HIP_TRY(hipMemcpyAsync(u.late_dst + u.cap * 8, src + u.cap * 8, total * u.late_value_bytes, hipMemcpyDeviceToHost, u.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(u.stream));
+    }
     return RC_OK;
 }

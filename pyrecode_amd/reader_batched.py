@@ -249,7 +249,7 @@ class BatchedAccess:
         self._ra_buf = None
 
     # ---- batched access (device-resident decode + expand; no counterpart in the reference, which reads frame by frame) ------
-    def get_frames_triplets(self, z0, n, out=None, coo=False, device_blosc=False):
+    def get_frames_triplets(self, z0, n, out=None, coo=False, device_blosc=False, device_zlib=False):
         """Frames z0 .. z0+n-1 of a merged file - or records z0 .. z0+n-1 of a part file, whose frame ids are part_frame_ids[z] - in ONE
         device call (rc_expand_frames): both streams of every frame are
         decompressed and expanded on the GPU without a host round trip in between.  Returns (nnz_prefix uint64[n+1],
@@ -264,15 +264,20 @@ class BatchedAccess:
         uint16), or 12 for a level-1 file of more than 16 bits (rc_expand_frames_coo32: values uint32).
         device_blosc=True: a blosc-LZ4 file (compression_scheme 8) at level 1 or 3 goes through the device call as well (the batched
         blosc decoder of rc_expand_frames).  A switch, and off by default, because the path such files take through this call is part of
-        its tested behaviour: they read frame by frame, and callers - the read-ahead among them - see 'per-frame' in last_batch_path."""
+        its tested behaviour: they read frame by frame, and callers - the read-ahead among them - see 'per-frame' in last_batch_path.
+        device_zlib=True: a zlib file (compression_scheme 0) at level 1 or 3 is offered to the batched device inflate (rc_expand_frames with
+        RC_SCHEME_ZLIB_DEVICE), which reads the streams of this library's device DEFLATE encoder and refuses every other zlib stream; a
+        refused file takes the host-decoded path below, as it does without the switch, and is not offered again.  last_batch_path is
+        'device-inflate' for a batch the device decoded.  Off by default: the host-decoded path of such files is tested behaviour."""
         h = self._header
         dst = _BatchOut.for_file(h, coo, out)
         nz = self._batch_frames()
         if z0 < 0 or n <= 0 or z0 + n > nz:
             raise ValueError('Requested frame index is greater than number of frames in dataset')
         level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        fast = level in (1, 3) and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc))
-        host_only = level in (1, 3) and mode == 1 and scheme in (0, 4, 5)   # zlib / bz2 / lzma: stock decoder on the thread pool, ONE device expand
+        zdev = bool(device_zlib) and level in (1, 3) and mode == 1 and scheme == 0 and not self._foreign_file
+        fast = level in (1, 3) and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc) or zdev)
+        host_only = level in (1, 3) and mode == 1 and scheme in (0, 4, 5) and not zdev   # zlib / bz2 / lzma: stock decoder on the thread pool, ONE device expand
         if fast or host_only:
             sizes = np.zeros((n, 3), np.uint32)
             for i in range(n):
@@ -292,7 +297,8 @@ class BatchedAccess:
             self._read_batch_into(blob, z0, n)
             prefix = np.zeros(n + 1, np.uint64)
             L = _lib.lib()
-            args = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), level, mode, scheme, _lib.ptr(blob), _lib.ptr(sizes), n)
+            args = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), level, mode, _lib.RC_SCHEME_ZLIB_DEVICE if zdev else scheme,
+                    _lib.ptr(blob), _lib.ptr(sizes), n)
             if host_only or (mode == 1 and self._foreign_file):
                 st = _lib.RC_ERR_UNSUPPORTED            # (a file whose streams the device decoders refused once is not offered again)
             elif level == 1:
@@ -307,7 +313,7 @@ class BatchedAccess:
                     st = dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap)
             if st == _lib.RC_OK:
                 self._note_batch_end(z0 + n)
-                self.last_batch_path = 'device'
+                self.last_batch_path = 'device-inflate' if zdev else 'device'
                 return prefix, dst.result(int(prefix[n]))
             # Outside the device decoders' subset - or a stream they could not make sense of (a foreign encoder's independent 64 KiB
             # LZ4 blocks look like that): the per-frame path below decodes with the stock library, which is also the judge of whether
@@ -319,7 +325,8 @@ class BatchedAccess:
                 if res is not None:
                     self._note_batch_end(z0 + n)
                     self.last_batch_path = 'host-decode + device-expand'
-                    self._foreign_file = not host_only
+                    if not host_only:            # (a host-only scheme never is the device decoders' to refuse; a zlib file the device
+                        self._foreign_file = True    # inflate refused keeps its mark through the host-decoded batches that follow)
                     return res
         # per-frame path
         self.last_batch_path = 'per-frame'
@@ -537,19 +544,19 @@ class BatchedAccess:
                 except Exception:         # (a generator finalised while the interpreter shuts down)
                     pass
 
-    def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False, device_blosc=False):
-        """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc: as in get_frames_triplets).  The read-ahead under get_frame / get_next_frame keeps
+    def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False, device_blosc=False, device_zlib=False):
+        """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc, device_zlib: as in get_frames_triplets).  The read-ahead under get_frame / get_next_frame keeps
         an iterator of its own alive on the same page-locked buffers, with one batch queued on the device: it is ended first (its queued
         batch waited for, the window it serves forgotten), and it stays off while this generator lives."""
         self._ra = None
         self._close_ra_iter()
         self._user_iters += 1
         try:
-            yield from self._iter_frames_impl(z0, n, batch, coo, device_blosc)
+            yield from self._iter_frames_impl(z0, n, batch, coo, device_blosc, device_zlib)
         finally:
             self._user_iters -= 1
 
-    def _iter_frames_impl(self, z0=0, n=None, batch=64, coo=False, device_blosc=False):
+    def _iter_frames_impl(self, z0=0, n=None, batch=64, coo=False, device_blosc=False, device_zlib=False):
         """Streams frames z0 .. z0+n-1 of a merged file (records z0 .. of a part file: the reference's own read test sums a part file's
         frames one get_next_frame at a time, tests/recode_v1_read_test.py:9-21) through the batched device reader, two batches in flight
         (rc_expand_frames_submit / _wait): while the device decodes one batch, the next one is read from the file, its block headers
@@ -567,16 +574,17 @@ class BatchedAccess:
         level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
         d = int(h['target_bit_depth'])
         starts = list(range(z0, z0 + n, batch))
-        if level in (1, 3) and mode == 1 and (scheme in (0, 4, 5) or (scheme in (1, 2) and self._foreign_file)):
+        zdev = bool(device_zlib) and level in (1, 3) and mode == 1 and scheme == 0 and not self._foreign_file
+        if level in (1, 3) and mode == 1 and not zdev and (scheme in (0, 4, 5) or (scheme in (1, 2) and self._foreign_file)):
             yield from self._iter_host_decoded(z0, n, batch, coo)  # stock decoders on the pool, one batch ahead of the device
             return
-        if not (level == 1 and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc))):
+        if not (level == 1 and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc) or zdev)):
             for a in starts:
                 k = min(batch, z0 + n - a)
-                yield (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)
+                yield (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
             return
         L = _lib.lib()
-        geom = (int(h['nx']), int(h['ny']), d, level, mode, scheme)
+        geom = (int(h['nx']), int(h['ny']), d, level, mode, _lib.RC_SCHEME_ZLIB_DEVICE if zdev else scheme)
         dst = _BatchOut.for_file(h, coo)
         if self._stream_bufs is None:
             self._stream_bufs = [None, None, None, None]       # page-locked: two input blobs, two outputs; kept until close()
@@ -607,6 +615,8 @@ class BatchedAccess:
             bufs[2 + slot] = pinned(bufs[2 + slot], cap * dst.esz)
             st = dst.fn(L, submit=True)(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap)
             if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                if zdev:
+                    self._foreign_file = True                 # another zlib encoder's file: one refused batch, the host-decoded path from here on
                 return (a, k, slot, None)
             if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
                 # the library's two streaming slots are per process and device: ANOTHER iterator (another reader) holds this one.
@@ -618,15 +628,17 @@ class BatchedAccess:
         def finish(job):
             a, k, slot, cap = job
             if cap is None:
-                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)       # (sets last_batch_path itself)
+                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)       # (sets last_batch_path itself)
             prefix = np.zeros(k + 1, np.uint64)
             st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
-            if st == _lib.RC_ERR_CORRUPT:                     # the stock decoder is the judge
-                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc)
+            if st == _lib.RC_ERR_UNSUPPORTED and zdev:        # the device inflate refused a stream: another zlib encoder's file
+                self._foreign_file = True
+            if st == _lib.RC_ERR_CORRUPT or (st == _lib.RC_ERR_UNSUPPORTED and zdev):      # the stock decoder is the judge
+                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
             _lib.check(st, 'rc_expand_frames_wait')
             total = int(prefix[k])
             trip = dst.views(bufs[2 + slot].array, cap, total, coo, dst.value_bytes)
-            self.last_batch_path = 'device'
+            self.last_batch_path = 'device-inflate' if zdev else 'device'
             return a, prefix, trip
         queued = None        # a batch submitted and not yet waited for
         try:
