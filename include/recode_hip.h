@@ -14,6 +14,11 @@
  *   - A ctx is bound to one GPU and one HIP stream and is not thread-safe; distinct ctxs are independent
  *     (reference: one ReCoDeWriter per process, recode_server.py:358-363).
  *   - All multi-byte fields the library writes are little-endian (reference uses sys.byteorder on x86).
+ *   - Ordering of device pointers: the library works on streams of its own (non-blocking streams: they do not wait for the legacy null
+ *     stream or for any stream of the caller).  Device memory handed to a synchronous or stateless entry point must therefore be
+ *     COMPLETE when the call is made - the caller synchronises the stream that produced it first (torch: torch.cuda.synchronize(), or
+ *     the producing stream's synchronize()) -, and what such a call wrote to device memory is complete when it returns.  Only the
+ *     asynchronous ctx entry points order themselves on a stream the caller names (rc_ctx_set_stream, rc_ctx_wait_results).
  */
 #ifndef RECODE_HIP_H
 #define RECODE_HIP_H
@@ -366,6 +371,37 @@ int rc_split_triplets(const uint64_t *triplets, uint64_t n, int32_t *row, int32_
 int rc_bit_pack(const uint16_t *pixvals, uint64_t n, uint32_t bit_depth, uint8_t *out, uint64_t out_n);
 /* bit_unpack_pixel_intensities -> intended semantics of reader.h:74-99: n d-bit fields -> uint64[n]. */
 int rc_bit_unpack(const uint8_t *packed, uint64_t packed_bytes, uint64_t n, uint32_t bit_depth, uint64_t *out);
+
+/* ---- calibration: from a flat-field acquisition to threshold frames --------------------------------------------
+ * The per-pixel and per-value loops of pyrecode/utils/calibration.py::make_calibration_frames (:87-138); the Gaussian fit, the thresholds
+ * floor(median + sigma * i) and the files stay on the host (pyrecode_amd/utils/calibration.py), the event counts per threshold
+ * (_count_events, :19-23) are a reduction-level-2 ctx in reduce-only mode.  Stateless, on the caller's current GPU (or RC_DEVICE);
+ * every pointer may be host or device memory.  stack: uint16[n][n_pixels] in C order, 1 <= n <= 65535 (RC_ERR_BAD_ARG beyond: the
+ * exact-integer variance n * S2 - S1^2 fits 64 bits up to there); sizes are checked before any device work.
+ *
+ * rc_calib_stats replaces _median_std_nb (:48-57):
+ *   median    float32[n_pixels] out: np.median of every pixel's n values, bit-exact (odd n: the middle value, even n: the mean of the two
+ *             middle values - a multiple of 0.5 below 2^17)
+ *   std_out   float32[n_pixels] out: np.std (population) as sqrt(n * S2 - S1^2) / n from exact integer sums, one square root in double
+ *             precision - within one float32 ulp of numpy's two-pass float64 result
+ *   range2    int32[2] out: minimum and maximum of 2 * frame - 2 * median over the LAST n_stats frames (n_stats <= n), i.e. twice the
+ *             range of what _get_fit_params (:64-71) histograms; {INT32_MAX, INT32_MIN} when n_stats is 0
+ * One read of the stack from HBM while a pixel's column fits LDS (n <= rc_calib_lds_max_frames()); longer columns are read about 17
+ * times from global memory by the same per-column code (pyrecode_amd/csrc/rc_calib.h). */
+int rc_calib_stats(const uint16_t *stack, uint32_t n, uint64_t n_pixels, uint32_t n_stats, float *median, float *std_out, int32_t *range2);
+uint32_t rc_calib_lds_max_frames(void);          /* no GPU needed */
+/* np.histogram(frames - median, bins=edges) of _get_fit_params (:71): frames uint16[n_stats][n_pixels] (the frames themselves - for the
+ * reference's choice, the address of frame n - n_stats of the stack), edges double[n_bins + 1] ascending (np.histogram_bin_edges on the
+ * host), counts uint64[n_bins] out.  A value x = double(frame) - double(median) counts for the bin with edges[i] <= x < edges[i + 1], the
+ * last bin closed on the right; values outside the edges count nowhere.  1 <= n_bins <= 1024, 1 <= n_stats <= 65535. */
+int rc_calib_histogram(const uint16_t *frames, uint32_t n_stats, uint64_t n_pixels, const float *median, const double *edges,
+                       uint32_t n_bins, uint64_t *counts);
+/* _get_pixel_thresh_2 (:26-45), the "accurate" per-pixel thresholds: acc float32[n_pixels] out = the mean of the (k + 1)-th and the k-th
+ * largest of the pixel's values that exceed median[pixel]; k = expected_n_events >= 1.  Where fewer than k + 1 values exceed the median
+ * the reference's result is np.finfo(float32).min cast to an integer - undefined; here such a pixel gets 65535, the source type's
+ * maximum, so that it never fires, and *n_undefined (uint64 out) counts those pixels. */
+int rc_calib_top_thresholds(const uint16_t *stack, uint32_t n, uint64_t n_pixels, const float *median, uint32_t k, float *acc,
+                            uint64_t *n_undefined);
 
 /* ---- synthetic stacks for tests / bench --------------------------------------------------
  * Counter-based integer generator, identical on host (pyrecode_amd/synth.py) and device:

@@ -80,6 +80,10 @@ SIGNATURES = {
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rc_bit_pack": (C.c_int, [_u16p, C.c_uint64, C.c_uint32, _u8p, C.c_uint64]),
     "rc_bit_unpack": (C.c_int, [_u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
+    "rc_calib_stats": (C.c_int, [_u16p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rc_calib_lds_max_frames": (C.c_uint32, []),
+    "rc_calib_histogram": (C.c_int, [_u16p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, _u64p]),
+    "rc_calib_top_thresholds": (C.c_int, [_u16p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, _u64p]),
     "rc_synth_dark": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _u16p]),
     "rc_synth_frames": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u16p, _u16p]),
     "rc_synth_frames_clustered": (C.c_int, [C.c_int] + [C.c_uint32] * 6 + [_u16p, _u16p]),

@@ -200,4 +200,11 @@ void launch_inflate(const uint8_t *data, const InfStream *streams, uint32_t n_ma
 
 void launch_roi_components(const void *frames, const void *thr, uint64_t N, uint32_t nx, uint32_t n, uint32_t first_frame_id, uint32_t gap,
                            uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t *counts, hipStream_t s, uint32_t src_bytes = 2);
+
+// rc_calib.hip - calibration: per-pixel median / std / range, histogram of frame - median, accurate thresholds
+constexpr uint32_t CALIB_LDS_MAX_FRAMES = 512;   // the longest column a one-wave workgroup stages in LDS (512 frames x 128 bytes = 64 KiB)
+void launch_calib_stats(const uint16_t *stack, uint32_t n, uint64_t N, uint32_t n_stats, float *median, float *sdev, int32_t *range2, hipStream_t s);
+void launch_calib_hist(const uint16_t *frames, uint32_t n_stats, uint64_t N, const float *median, const double *edges, uint32_t n_bins,
+                       uint64_t *counts, hipStream_t s);
+void launch_calib_top(const uint16_t *stack, uint32_t n, uint64_t N, const float *median, uint32_t k, float *acc, uint64_t *n_undefined, hipStream_t s);
 }  // namespace rc
