@@ -351,6 +351,38 @@ int rc_expand_frames_l2(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t o
 int rc_expand_frames_l2_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme,
                                const uint8_t *data, const uint32_t *sizes, uint32_t n, void *rc_dev, uint64_t cap, uint16_t *stats_dev,
                                uint64_t stats_cap);
+/* ---- summed views: frames added up on the device --------------------------------------------------------------
+ * What the reference's ReCoDeViewer (pyrecode/utils/viewer.py:40-75) and its Live View notebooks do with the frames of a window -
+ * np.add(view, frame.toarray()) for each of them - without a set pixel crossing the link: a batch is decoded and counted exactly as by
+ * rc_expand_frames, and in place of the emit kernel one kernel adds every frame's values to an accumulator in device memory (level 1: the
+ * pixel's bit_depth-bit value; levels 2 and 3: 1 per set pixel, a level-2 frame's statistics stream stepped over).
+ * The accumulator is an object the caller owns - one uint32 cell per pixel, row-major, ny * nx cells, zeroed, on the caller's current GPU
+ * (or RC_DEVICE) - so that several readers, the part files of one run, add into one view.  ONE thread uses a handle at a time.
+ *   rc_sum_create            NULL with *status set on failure (RC_ERR_DEVICE without a GPU, like every compute entry point)
+ *   rc_sum_add_frames        the synchronous add; bit_depth .. sizes, n, nnz_prefix and the device decoders' subset as for rc_expand_frames
+ *                            (nx, ny are the handle's; nnz_prefix may be NULL).  Has resources of its own, like rc_expand_frames
+ *   rc_sum_add_frames_submit the same batch queued on slot 0 or 1; rc_expand_frames_wait(slot, nnz_prefix) gives its verdict and the counts.
+ *                            Batches on both slots may add into one handle: their decode stages overlap, their sum kernels are ordered
+ *   rc_sum_fetch             waits for every add queued so far, then copies the ny * nx cells to dst (host or device memory); reset != 0
+ *                            also zeroes the cells and the bound
+ *   rc_sum_bound             the largest value any cell can hold so far: the sum over the accepted adds of n * (2^bit_depth - 1) at level 1
+ *                            and of n at levels 2 and 3 (a queued batch the device rejects later still counts: an upper bound)
+ *   rc_sum_destroy           waits for queued adds, frees the cells
+ * A batch the device rejects - RC_ERR_CORRUPT, RC_ERR_UNSUPPORTED, a value stream shorter than its set pixels need (RC_ERR_CORRUPT) - adds
+ * NOTHING to the cells; the call, or rc_expand_frames_wait, says which.  No silent wrap: an add that could take a cell past 2^32 - 1
+ * (rc_sum_bound() + this batch's share) is refused with RC_ERR_OUT_TOO_SMALL before anything is queued - fetch with reset, fold into a wider
+ * image on the host, go on.  RC_ERR_UNSUPPORTED: level 1 with bit_depth > 16 (64-bit cells are not offered), and what rc_expand_frames
+ * refuses.  RC_ERR_BAD_ARG: stored frames (op_mode 0) whose binary map is not ceil(nx * ny / 8) bytes - another geometry than the handle's -,
+ * a handle of another device. */
+typedef struct rc_sum rc_sum;
+rc_sum *rc_sum_create(uint32_t nx, uint32_t ny, int *status);
+int rc_sum_destroy(rc_sum *s);
+int rc_sum_add_frames(rc_sum *s, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                      const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix);
+int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                             const uint8_t *data, const uint32_t *sizes, uint32_t n);
+int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset);
+uint64_t rc_sum_bound(const rc_sum *s);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

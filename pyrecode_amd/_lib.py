@@ -75,6 +75,12 @@ SIGNATURES = {
     "rc_expand_frames_coo32_submit": (C.c_int, [C.c_uint32] * 7 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_expand_frames_l2": (C.c_int, [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, _u64p, C.c_void_p, C.c_uint64, _u16p, C.c_uint64]),
     "rc_expand_frames_l2_submit": (C.c_int, [C.c_uint32] * 6 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u16p, C.c_uint64]),
+    "rc_sum_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "rc_sum_destroy": (C.c_int, [C.c_void_p]),
+    "rc_sum_add_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, _u64p]),
+    "rc_sum_add_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32]),
+    "rc_sum_fetch": (C.c_int, [C.c_void_p, _u32p, C.c_int]),
+    "rc_sum_bound": (C.c_uint64, [C.c_void_p]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
     "rc_host_decode_streams": (C.c_int, [C.c_uint32, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32]),
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -174,6 +180,84 @@ class PinnedBuffer:
         if p and _lib is not None:
             self.array = None
             _lib.rc_host_free(p)
+
+    __del__ = close
+
+
+class FrameSum:
+    """A summed view on the device: rc_sum_create .. rc_sum_destroy (include/recode_hip.h) - one uint32 cell per pixel that batches of
+    stored frames are added into, whichever reader they come from.  `geom` is the tuple the batched readers pass to rc_expand_frames:
+    (nx, ny, bit_depth, reduction_level, op_mode, scheme); its nx, ny must be the handle's.  One thread uses a handle at a time."""
+
+    LIMIT = 0xFFFFFFFF        # what a cell holds: an add that could pass it is refused (RC_ERR_OUT_TOO_SMALL -> ValueError)
+
+    def __init__(self, nx, ny):
+        st = C.c_int(0)
+        self.nx, self.ny = int(nx), int(ny)
+        self._h = lib().rc_sum_create(self.nx, self.ny, C.byref(st))
+        if not self._h:
+            check(st.value, "rc_sum_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _codec(self, geom):
+        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("FrameSum: frames of %d x %d added to a view of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
+        return tuple(int(v) for v in geom[2:6])
+
+    @staticmethod
+    def grows_by(geom, n):
+        """what a batch of n frames adds to bound()"""
+        return int(n) * (((1 << int(geom[2])) - 1) if int(geom[3]) == 1 else 1)
+
+    def add_status(self, geom, data, sizes, n, prefix=None):
+        """rc_sum_add_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT)"""
+        return lib().rc_sum_add_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(prefix))
+
+    def add(self, geom, data, sizes, n):
+        """Add n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them); returns the
+        frames' set-pixel prefix uint64[n + 1].  A rejected batch raises and adds nothing."""
+        prefix = np.zeros(n + 1, np.uint64)
+        check(self.add_status(geom, data, sizes, n, prefix), "rc_sum_add_frames")
+        return prefix
+
+    def submit_status(self, slot, geom, data, sizes, n):
+        return lib().rc_sum_add_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n)
+
+    def submit(self, slot, geom, data, sizes, n):
+        """Queue the batch on slot 0 or 1 (data stays valid until rc_expand_frames_wait(slot) has returned, which gives the verdict)."""
+        check(self.submit_status(slot, geom, data, sizes, n), "rc_sum_add_frames_submit")
+
+    def fetch(self, reset=False, out=None):
+        """uint32[ny, nx]: the cells, after every queued add; reset=True zeroes them and the bound"""
+        if out is None:
+            out = np.empty((self.ny, self.nx), np.uint32)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint32 or out.size != self.ny * self.nx or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("FrameSum.fetch: out must be a C-contiguous uint32 array of ny * nx = %d cells" % (self.ny * self.nx))
+        check(lib().rc_sum_fetch(self._h, ptr(out), 1 if reset else 0), "rc_sum_fetch")
+        return out
+
+    def fetch_view(self, reset=False):
+        """fetch() into page-locked memory of this handle's (one copy over the link, no staging through the runtime's bounce buffers:
+        a 4096 x 4096 view is 67 MB): a VIEW, valid until the next fetch_view() or close()"""
+        if getattr(self, "_pin", None) is None:
+            self._pin = PinnedBuffer(4 * self.nx * self.ny)
+        return self.fetch(reset, self._pin.array.view(np.uint32).reshape(self.ny, self.nx))
+
+    def bound(self):
+        """the largest value a cell can hold so far - an UPPER bound: a batch that was queued (submit) and that the device then refused
+        added nothing, but has been counted"""
+        return int(lib().rc_sum_bound(self._h))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.rc_sum_destroy(h)
+        pin, self._pin = getattr(self, "_pin", None), None
+        if pin is not None:
+            pin.close()
 
     __del__ = close
 

@@ -6,6 +6,8 @@
 //        _bit_unpack_pixel_intensities   pyrecode/c_extensions/reader.h:74-99   (intended semantics)
 #include "rc_expand.h"
 
+#include <algorithm>
+
 namespace rc {
 
 
@@ -265,6 +267,89 @@ void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb
     else
         hipLaunchKernelGGL(k_expand_emit_b<false>, dim3(nblk, n), dim3(WG), 0, s, bm, bm_stride, nb8, N, nx, nblk, blk_off, frame_base, pv, pv_stride,
                            pv_bytes, d, level, cap, out, err);
+}
+
+// ---- summed frames (rc_sum_add_frames): acc[p] += value of pixel p, over the n frames of a batch -------------------------------------
+// What the reference's ReCoDeViewer does with a window of frames on the host (utils/viewer.py:65-68: np.add(view, frame.toarray())), from
+// the streams k_expand_emit_b reads and in its place: nothing per set pixel leaves the device.  A workgroup owns ONE block of WG bitmap
+// words (16 384 pixels, row-major, so the linear pixel index is the cell's address: no division) for a GROUP of consecutive frames and sums
+// them in LDS; thread t is the only writer of its word's 64 cells, so the LDS needs no atomics and the loop no barriers beyond the two of
+// block_excl_scan (uniform trip count; a frame without a set pixel in the block is stepped over after them).  Cell (word t, bit b) lies at
+// b * (WG + 1) + t: lanes that walk b in lockstep (dense frames) hit consecutive banks, lanes at different b hit (b + t) mod 32 - as random
+// as the data -, and the flush, where a wave reads one word's 64 bits, is consecutive again.  cell[64 * t + b] would put a dense frame's
+// 64 lanes on one bank, its transpose does the same to the flush.  64 x 257 dwords + the scan's = 65 812 B: two workgroups per CU.
+// The flush adds every nonzero cell to acc with one no-return atomic per pixel, lanes on consecutive pixels; zero cells cost nothing, so a
+// group's cost follows its set pixels and splitting a batch into more groups adds only pixels that two groups share.  Integer sums: the
+// result does not depend on the order.  Writes nothing once *err is set (a decoder, or k_expand_bases: value stream too short).
+constexpr uint32_t SUM_TARGET_WGS = 2048;     // workgroups a launch aims for: four rounds of the 512 that are resident on 256 CUs
+constexpr uint32_t SUM_MIN_GROUP = 4;         // ... but no group of fewer frames than this: a flush visits all 16 384 cells
+constexpr uint32_t SUM_ROW = WG + 1;
+__global__ __launch_bounds__(WG) void k_expand_sum_b(const uint8_t *__restrict__ bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nblk,
+                                                       const uint32_t *__restrict__ blk_off, const uint8_t *__restrict__ pv, uint64_t pv_stride,
+                                                       const uint32_t *__restrict__ pv_bytes, uint32_t d, uint32_t level, uint32_t n, uint32_t per_group,
+                                                       uint32_t *__restrict__ acc, const int *__restrict__ err)
+{
+    __shared__ uint32_t sm[WAVES + 1];
+    __shared__ uint32_t cell[64 * SUM_ROW];
+    if (*err) return;   // (workgroup-uniform, as in k_expand_emit_b)
+    const uint32_t t = threadIdx.x;
+    for (uint32_t b = 0; b < 64; ++b) cell[b * SUM_ROW + t] = 0;     // (its own cells: no barrier before the loop)
+    const uint32_t f0 = blockIdx.y * per_group, f1 = min(n, f0 + per_group);
+    const uint64_t i = (uint64_t)blockIdx.x * WG + t;
+    const uint32_t dmask = level == 1 ? (1u << d) - 1u : 0u;        // (level 1: 1 <= d <= 16; other levels pass whatever the file's header says)
+    uint64_t next = f0 < f1 ? expand_word(bm + f0 * bm_stride, nb8, N, i) : 0;
+    for (uint32_t f = f0; f < f1; ++f) {
+        uint64_t bits = next;
+        if (f + 1 < f1) next = expand_word(bm + (f + 1) * bm_stride, nb8, N, i);   // (in flight across this frame's barriers)
+        uint32_t tot;
+        const uint32_t local = block_excl_scan((uint32_t)__builtin_popcountll(bits), sm, &tot);
+        if (tot == 0 || !bits) continue;                             // (tot is uniform and the barriers are behind us)
+        if (level != 1) {
+            for (; bits; bits &= bits - 1) cell[(uint32_t)__builtin_ctzll(bits) * SUM_ROW + t] += 1u;
+            continue;
+        }
+        uint64_t rank = (uint64_t)blk_off[(uint64_t)f * nblk + blockIdx.x] + local;
+        const uint8_t *pix = pv + f * pv_stride;
+        const uint64_t pix_bytes = pv_bytes[f];
+        for (; bits; bits &= bits - 1, ++rank) {
+            uint32_t val;
+            // as k_expand_emit_b: d = 16 is the uint16 itself; a narrower field that ends inside the stream lies in the two dwords at its bit
+            // position, the second of which ends before pix_bytes + 8 - inside the frame's slot, zeroed behind the stream (rc_reader.hip:
+            // pv_stride; slots are 8-byte aligned); anything else goes byte by byte with every byte checked (read_field)
+            if (d == 16 && 2 * rank + 2 <= pix_bytes) val = reinterpret_cast<const uint16_t *>(pix)[rank];
+            else if (d < 16 && rank * d + d <= 8 * pix_bytes) {
+                const uint64_t bit = rank * d;
+                const uint32_t *p = reinterpret_cast<const uint32_t *>(pix) + (bit >> 5);
+                val = (uint32_t)((((uint64_t)p[0] | ((uint64_t)p[1] << 32)) >> (bit & 31u))) & dmask;
+            } else
+                val = (uint32_t)read_field(pix, pix_bytes, rank, d);
+            cell[(uint32_t)__builtin_ctzll(bits) * SUM_ROW + t] += val;
+        }
+    }
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * WG * 64;
+    for (uint32_t j = 0; j < 64; ++j) {
+        const uint32_t q = j * WG + t;                               // pixel of the block: word q >> 6 (uniform in a wave), bit = lane
+        const uint32_t v = cell[(q & 63u) * SUM_ROW + (q >> 6)];
+        if (v && p0 + q < N) (void)atomicAdd(acc + p0 + q, v);
+    }
+}
+// the frame groups (grid.y) a launch cuts n frames into, *per_group frames each
+static uint32_t expand_sum_groups(uint64_t nb8, uint32_t n, uint32_t *per_group)
+{
+    const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
+    const uint32_t want = std::max(1u, std::min((SUM_TARGET_WGS + nblk - 1) / nblk, (n + SUM_MIN_GROUP - 1) / SUM_MIN_GROUP));
+    *per_group = (n + want - 1) / want;
+    return (n + *per_group - 1) / *per_group;                       // (no empty group)
+}
+void launch_expand_batch_sum(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t n, const uint32_t *blk_off, const uint8_t *pv,
+                             uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level, uint32_t *acc, const int *err, hipStream_t s)
+{
+    const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
+    uint32_t per_group = 1;
+    const uint32_t groups = expand_sum_groups(nb8, n, &per_group);
+    hipLaunchKernelGGL(k_expand_sum_b, dim3(nblk, groups), dim3(WG), 0, s, bm, bm_stride, nb8, N, nblk, blk_off, pv, pv_stride, pv_bytes, d, level, n,
+                       per_group, acc, err);
 }
 
 // ---- level-2 statistics of a batch (rc_expand_frames_l2): frame f's decoded statistics stream at pv + f * pv_stride -> its

@@ -101,6 +101,20 @@ int blosc_index_stream(const uint8_t *base, uint64_t off, uint64_t n, uint32_t f
 }
 }  // namespace
 
+// The accumulator of the summed-view calls (rc_sum_*): a uint32 cell per pixel in device memory, owned by the caller's handle - not by the
+// utility context, so several readers (the part files of a run) add into one view and a handle is freed when its owner says so.
+// ev orders the adds: both streaming slots and the synchronous call may hold an add into the same cells, each on a stream of its own; an add's
+// sum kernel waits for ev and records it again, rc_sum_fetch / rc_sum_destroy wait for it.  (Integer adds commute and the kernel adds with
+// atomics, so the order is not needed for the sum - it is needed for "everything queued has landed" to be one event.)
+struct rc_sum {
+    int device = -1;
+    uint32_t nx = 0, ny = 0;
+    uint32_t *acc = nullptr;
+    hipEvent_t ev = nullptr;
+    hipStream_t stream = nullptr;      // fetch / reset
+    uint64_t bound = 0;                // the largest value a cell can hold: sum over the adds of n * (2^d - 1) (level 1) or n (levels 2, 3)
+};
+
 // slot, submit_only: rc_expand_frames = (RC_READ_SLOTS - its own resources -, false); rc_expand_frames_submit = (slot, true): returns once everything is queued.
 // coo (bytes of a value, 0 = not): the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] |
 // uint16 (2, rc_expand_frames_coo) or uint32 (4, rc_expand_frames_coo32) values[cap] (k_expand_emit_b<true, ...>): 10 or 12 bytes per set
@@ -108,9 +122,11 @@ int blosc_index_stream(const uint8_t *base, uint64_t off, uint64_t n, uint32_t f
 // l2out (rc_expand_frames_l2, level 2 only): rows and columns alone (coo without the value array: 8 bytes per set pixel), and every frame's
 // statistics - the fields of its value stream - as uint16 into stats[stats_cap].  Without it a level-2 frame's statistics stream is
 // stepped over and the frame expands like a level-3 one.
+// sum (rc_sum_add_frames / _submit): no entries at all - behind the count, k_expand_sum_b adds the frames' values to the handle's cells
+// (triplets NULL, cap 0).  The gate is the emit kernel's: a batch a decoder or k_expand_bases rejects adds nothing.
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
-                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0)
+                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr)
 {
     const uint64_t esz = l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
@@ -446,7 +462,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     // A submitted batch may also name PAGE-LOCKED host memory: the triplets are then staged in device memory and one asynchronous copy of
     // cap entries follows the emit kernel (the copy engine moves 64 MB in 1.3 ms under the next batch's work; letting the emit kernel
     // write over the link itself - 8-byte stores, 24 bytes apart - took 4 ms).
-    bool dev_out = triplets && is_device_ptr(triplets);
+    bool dev_out = sum || (triplets && is_device_ptr(triplets));
     uint64_t *host_async = nullptr;
     if (submit_only && !dev_out) {
         hipPointerAttribute_t a;
@@ -458,7 +474,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         } else (void)hipGetLastError();
     }
     if (submit_only && !dev_out) return bail(RC_ERR_BAD_ARG, "rc_expand_frames_submit: triplets must be device or page-locked host memory");
-    if (dev_out) {
+    if (sum) {
+        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
+        HIP_TRY(hipStreamWaitEvent(s, sum->ev, 0));
+        launch_expand_batch_sum(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, sum->acc, d_err, s);
+        HIP_TRY(hipEventRecord(sum->ev, s));
+    } else if (dev_out) {
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, cap, d_err);
         launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, triplets, s, d_err, coo);
     } else
@@ -476,7 +497,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         u.late_value_bytes = l2out ? 0 : coo;
         u.late_coo = coo != 0;
         u.pending = true;
-        u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = cap;
+        u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
         u.pv_bytes.assign(pv_bytes, pv_bytes + n);
         return RC_OK;
     }
@@ -487,6 +508,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     const uint64_t total = nnz_prefix[n];
+    if (sum) return (err & 4) ? fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits") : RC_OK;
     if (stats_short) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2: stats holds fewer entries than the frames have statistics");
     if (stats_staged) {
         HIP_TRY(hipMemcpyAsync(stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
@@ -623,5 +645,111 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
         }
         HIP_TRY(hipStreamSynchronize(u.stream));
     }
+    return RC_OK;
+}
+
+// ---- summed views: an accumulator the caller owns, and expand_run's route into it ------------------------------------------------------
+RC_EXPORT rc_sum *rc_sum_create(uint32_t nx, uint32_t ny, int *status)
+{
+    auto done = [&](int code) { if (status) *status = code; return (rc_sum *)nullptr; };
+    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_sum_create: nx, ny in 1..65535"));
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return done(r);
+    rc_sum *s = new (std::nothrow) rc_sum;
+    if (!s) return done(fail(RC_ERR_WORKSPACE, "rc_sum_create: out of host memory"));
+    s->device = g_util.device; s->nx = nx; s->ny = ny;
+    const uint64_t bytes = (uint64_t)nx * ny * 4;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->acc), bytes);
+    if (e == hipSuccess) e = hipMemset(s->acc, 0, bytes);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        r = hip_fail(e, "rc_sum_create");
+        if (s->stream) (void)hipStreamDestroy(s->stream);
+        if (s->ev) (void)hipEventDestroy(s->ev);
+        if (s->acc) (void)hipFree(s->acc);
+        delete s;
+        return done(r);
+    }
+    if (status) *status = RC_OK;
+    return s;
+}
+
+RC_EXPORT int rc_sum_destroy(rc_sum *s)
+{
+    if (!s) return RC_OK;
+    RC_ON_DEVICE(s->device);
+    (void)hipEventSynchronize(s->ev);      // (an add that is still queued writes into acc)
+    (void)hipStreamDestroy(s->stream);
+    (void)hipEventDestroy(s->ev);
+    (void)hipFree(s->acc);
+    delete s;
+    return RC_OK;
+}
+
+RC_EXPORT uint64_t rc_sum_bound(const rc_sum *s) { return s ? s->bound : 0; }
+
+// what both add calls check before anything is queued; *grow: what the batch adds to the handle's bound
+static int sum_admit(const rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint32_t *sizes, uint32_t n, uint64_t *grow)
+{
+    if (!s || !sizes || n == 0) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames: NULL / zero argument");
+    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_sum_add_frames: bit_depth above 16 (the cells are uint32; 64-bit cells are not offered)");
+    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
+    const uint64_t nb = ((uint64_t)s->nx * s->ny + 7) / 8;
+    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
+        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames: the frames' geometry differs from the handle's");
+    *grow = (uint64_t)n * (level == 1 ? (1ull << bit_depth) - 1 : 1ull);
+    if (s->bound + *grow > 0xFFFFFFFFull)
+        return fail(RC_ERR_OUT_TOO_SMALL, "rc_sum_add_frames: a cell could pass 2^32 - 1 (rc_sum_fetch with reset first)");
+    return RC_OK;
+}
+static int sum_on_its_device(const rc_sum *s)
+{
+    // (expand_run runs on the caller's current device or RC_DEVICE; the handle's cells live on the device it was created on)
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return r;
+    return g_util.device == s->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_sum_add_frames: the handle belongs to another device");
+}
+
+RC_EXPORT int rc_sum_add_frames(rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix)
+{
+    uint64_t grow = 0;
+    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
+    if (r == RC_OK) r = sum_on_its_device(s);
+    if (r != RC_OK) return r;
+    std::vector<uint64_t> own;
+    if (!nnz_prefix) { own.resize((size_t)n + 1); nnz_prefix = own.data(); }
+    r = expand_run(RC_READ_SLOTS, false, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, nullptr, 0, 0, false, nullptr, 0, s);
+    if (r == RC_OK) s->bound += grow;
+    return r;
+}
+
+RC_EXPORT int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                       const uint8_t *data, const uint32_t *sizes, uint32_t n)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_submit: slot 0 or 1");
+    uint64_t grow = 0;
+    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
+    if (r == RC_OK) r = sum_on_its_device(s);
+    if (r != RC_OK) return r;
+    r = expand_run(slot, true, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s);
+    if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
+    return r;
+}
+
+RC_EXPORT int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset)
+{
+    if (!s || !dst) return fail(RC_ERR_BAD_ARG, "rc_sum_fetch: NULL argument");
+    RC_ON_DEVICE(s->device);
+    const uint64_t bytes = (uint64_t)s->nx * s->ny * 4;
+    HIP_TRY(hipEventSynchronize(s->ev));
+    HIP_TRY(hipMemcpyAsync(dst, s->acc, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->stream));
+    if (reset) HIP_TRY(hipMemsetAsync(s->acc, 0, bytes, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (reset) s->bound = 0;
     return RC_OK;
 }

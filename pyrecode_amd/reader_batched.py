@@ -846,6 +846,227 @@ class BatchedAccess:
                 except Exception:         # (a generator finalised while the interpreter shuts down)
                     pass
 
+    # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
+    def _sum_sizes(self, a, k):
+        """(sizes uint32[k][3] as rc_sum_add_frames takes them, bytes of the k frames' data) of frames a .. a+k-1"""
+        level = int(self._header['reduction_level'])
+        sizes = np.zeros((k, 3), np.uint32)
+        for j in range(k):
+            md = self._frame_metadata[a + j]
+            sz_map, sz_val = self._stream_sizes(md)
+            sizes[j, 0] = sz_map
+            if level == 1:
+                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_pixvals'])
+            elif level == 2:
+                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_summary_stats'])     # (stepped over by the device)
+        return sizes, int(self._seek_table[a:a + k, 0].sum())
+
+    def _sum_device_scheme(self):
+        """the scheme code under which this file's batches are offered to the device decoders, or None.  sum_frames has no tested history
+        to keep, so blosc-LZ4 and - as RC_SCHEME_ZLIB_DEVICE, which refuses every zlib stream but this library's own - zlib go there by default"""
+        h = self._header
+        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
+        if mode == 0:
+            return scheme
+        if self._foreign_file:
+            return None
+        if scheme in (1, 2, 8):
+            return scheme
+        return _lib.RC_SCHEME_ZLIB_DEVICE if scheme == 0 and level in (1, 3) else None
+
+    def _sum_per_frame(self, fs, room, a, k):
+        """sum_frames' last route: frames a .. a+k-1 through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge,
+        and names the frame that is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the
+        file's own bit depth, so the handle's bound grows as for any other batch - and added like one: a caller's handle (`into`) receives
+        them too.  A dense mask, a sort and a pack per frame on the host: the slow route's price for serving `into`."""
+        h = self._header
+        nx, ny, level, d = int(h['nx']), int(h['ny']), int(h['reduction_level']), int(h['target_bit_depth'])
+        nb = (nx * ny + 7) // 8
+        sizes, parts = np.zeros((k, 3), np.uint32), []
+        shifts = np.arange(d, dtype=np.uint32)
+        keep = self._fp.tell()
+        for i in range(k):
+            self._fp.seek(self._frame_data_start_position + int(self._seek_table[a + i, 1]), 0)
+            m = self._get_frame_sparse(self._frame_metadata[a + i])
+            m = m[0] if isinstance(m, tuple) else m
+            dense, vals = np.zeros(ny * nx, bool), np.zeros(0, np.uint32)
+            if m is not None and m.nnz:
+                idx = m.row.astype(np.int64) * nx + m.col
+                dense[idx] = True
+                vals = m.data[np.argsort(idx, kind='stable')].astype(np.uint32)
+            parts.append(np.packbits(dense, bitorder='little'))
+            sizes[i, 0] = nb
+            if level == 1:
+                # d-bit fields, LSB first, zero-padded to a byte (recode_writer.py:637-652)
+                packed = np.packbits(((vals[:, None] >> shifts) & 1).astype(np.uint8).reshape(-1), bitorder='little')
+                parts.append(packed)
+                sizes[i, 1] = sizes[i, 2] = packed.size
+        self._fp.seek(keep, 0)
+        geom = (nx, ny, d, 1 if level == 1 else 3, 0, 0)
+        room(fs, _lib.FrameSum.grows_by(geom, k))
+        fs.add(geom, np.ascontiguousarray(np.concatenate(parts)), sizes, k)
+        self.last_batch_path = 'per-frame'
+
+    def _sum_stream(self, windows, batch, room):
+        """The engine of sum_frames and iter_frame_sums: windows = [(first frame, frames > 0, FrameSum)], one after the other; their batches
+        go through rc_sum_add_frames_submit / rc_expand_frames_wait on the two slots as ONE sequence, so the next batch - the next window's
+        first one, into its own handle, included - is read from the file and queued before this one is waited for.  Yields a window's
+        index once every batch of it has been added.  Every device call is made on the caller's thread.  room(fs, grow) is called before
+        an add that grows fs's bound by `grow`.  Routes and fall-backs: see sum_frames."""
+        h = self._header
+        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
+        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
+        L = _lib.lib()
+        jobs = [(w, b, min(batch, a + k - b), b + batch >= a + k) for w, (a, k, _) in enumerate(windows) for b in range(a, a + k, batch)]
+        if self._stream_bufs is None:
+            self._stream_bufs = [None, None, None, None]
+        bufs = self._stream_bufs
+
+        def start(j):
+            """read job j's bytes into its slot's page-locked blob and queue it: (window, a, k, last of its window, slot, sizes, blob, device scheme, status)"""
+            w, a, k, last = jobs[j]
+            fs, slot = windows[w][2], j & 1
+            sizes, nbytes = self._sum_sizes(a, k)
+            if bufs[slot] is None or bufs[slot].nbytes < nbytes + 64:
+                if bufs[slot] is not None:
+                    bufs[slot].close()
+                bufs[slot] = _lib.PinnedBuffer(max(int(nbytes * 1.25) + 64, 1 << 20))
+            blob = bufs[slot].array[:nbytes]
+            self._read_batch_into(blob, a, k)
+            dev = self._sum_device_scheme()
+            if dev is None:
+                return (w, a, k, last, slot, sizes, blob, None, None)
+            geom = (nx, ny, d, level, mode, dev)
+            room(fs, fs.grows_by(geom, k))
+            st = fs.submit_status(slot, geom, blob, sizes, k)
+            if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
+                st = fs.add_status(geom, blob, sizes, k)      # another reader's iterator holds the slot: the synchronous call has resources of its own
+                return (w, a, k, last, slot, sizes, blob, dev, st)
+            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_sum_add_frames_submit')
+            return (w, a, k, last, slot, sizes, blob, dev, 'queued' if st == _lib.RC_OK else st)
+
+        def finish(job):
+            w, a, k, _, slot, sizes, blob, dev, st = job
+            fs = windows[w][2]
+            if st == 'queued':
+                st = L.rc_expand_frames_wait(slot, _lib.ptr(np.zeros(k + 1, np.uint64)))
+            if dev is not None and st == _lib.RC_OK:
+                self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+                return
+            if dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_expand_frames_wait')
+            # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
+            if level in (1, 3) and mode == 1 and scheme in (0, 1, 2, 4, 5):
+                got = self._host_decode_batch(blob, sizes, k, 2)
+                if got is not None:
+                    pieces, sizes0 = got
+                    geom0 = (nx, ny, d, level, 0, scheme)
+                    room(fs, fs.grows_by(geom0, k))
+                    fs.add(geom0, pieces, sizes0, k)
+                    self.last_batch_path = 'host-decode + device-expand'
+                    if dev is not None:
+                        self._foreign_file = True        # not offered to the device decoders again
+                    return
+            self._sum_per_frame(fs, room, a, k)
+
+        self._ra = None
+        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
+        self._user_iters += 1
+        queued = None
+        try:
+            queued = start(0) if jobs else None
+            for j in range(len(jobs)):
+                job = queued
+                queued = None
+                queued = start(j + 1) if j + 1 < len(jobs) else None
+                finish(job)
+                self._note_batch_end(job[1] + job[2])
+                if job[3]:
+                    yield job[0]
+        finally:
+            self._user_iters -= 1
+            if queued is not None and queued[8] == 'queued':
+                try:
+                    L.rc_expand_frames_wait(queued[4], _lib.ptr(np.zeros(queued[2] + 1, np.uint64)))
+                except Exception:         # (a generator finalised while the interpreter shuts down)
+                    pass
+
+    def sum_frames(self, z0=0, n=None, batch=64, into=None):
+        """The sum of frames z0 .. z0+n-1 of a merged file (records of a part file) as uint64[ny, nx] - what the reference's viewer and its
+        own read test build one get_next_frame at a time (utils/viewer.py:65-68, tests/recode_v1_read_test.py:9-21) -, added up ON THE
+        DEVICE (rc_sum_add_frames_submit / rc_expand_frames_wait, two batches in flight: the next batch's bytes are read from the file while
+        the device decodes and adds the previous one); 4 bytes per pixel cross the link at the end instead of 10 per set pixel per frame.
+        Level 1: the sum of the pixels' values; levels 2 and 3: the number of frames in which a pixel is set.  The device's cells are uint32:
+        before a batch could take one past 2^32 - 1 the view is fetched, folded into the uint64 result and reset.
+        into: a _lib.FrameSum of this file's shape - the frames are added into it (with those of other readers), nothing is fetched, and the
+        number of frames added is returned; a sum that could pass 2^32 - 1 raises ValueError, with the batches before it added.  The
+        handle's bound() is an UPPER bound: a batch the device queued and then refused (the first one or two batches of a stock encoder's
+        file, which are then decoded on the host and added again) has grown it twice, so a caller's handle can be refused up to two
+        batches' share early.
+        Routes, per batch (last_batch_path): the device decoders ('device', 'device-inflate'); for streams they refuse and for host-only
+        schemes the stock decoders on the thread pool, then one add of the stored pieces ('host-decode + device-expand'); what is left
+        goes through the frame-at-a-time reader ('per-frame').  Files of more than 16 bits are not taken (NotImplementedError)."""
+        h = self._header
+        nz = self._batch_frames()
+        n = nz - z0 if n is None else n
+        if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
+            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        nx, ny = int(h['nx']), int(h['ny'])
+        self._sum_check_file()
+        fs = into if into is not None else _lib.FrameSum(nx, ny)
+        total = None if into is not None else np.zeros((ny, nx), np.uint64)
+
+        def room(view, grow):
+            """this call's own view is folded before `grow` could overflow it (rc_sum_fetch waits for every queued add itself)"""
+            if total is not None and view.bound() + grow > view.LIMIT:
+                np.add(total, view.fetch_view(reset=True), out=total)
+        try:
+            if n:
+                for _ in self._sum_stream([(z0, n, fs)], batch, room):
+                    pass
+            if total is None:
+                return n
+            np.add(total, fs.fetch_view(), out=total)
+            return total
+        finally:
+            if into is None:
+                fs.close()
+
+    def _sum_check_file(self):
+        h = self._header
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        if level not in (1, 2, 3):
+            raise NotImplementedError('sum_frames: reduction level %d' % level)
+        if level == 1 and d > 16:
+            raise NotImplementedError('sum_frames: files of more than 16 bits (target_bit_depth %d): the cells of a summed view are uint32' % d)
+
+    def iter_frame_sums(self, frames_per_view, z0=0, n=None, batch=64):
+        """Views of `frames_per_view` consecutive frames each (the last one of what is left): yields (first index, count, uint32[ny, nx]) -
+        a loop over sum_frames' engine with two device views that alternate: all windows' batches form one sequence on the two slots, so
+        the next window's first batch is read and queued - into the other view - before this window's image is fetched.  One thread does
+        it all.  The image is a VIEW of page-locked memory the device copied into, valid until the generator is advanced (copy it to keep
+        it), like the batches of iter_frames_triplets.  A window whose sum could pass 2^32 - 1 raises ValueError."""
+        if frames_per_view <= 0 or batch <= 0:
+            raise ValueError('frames_per_view and batch must be positive')
+        nz = self._batch_frames()
+        n = nz - z0 if n is None else n
+        if z0 < 0 or n < 0 or z0 + n > nz:
+            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        self._sum_check_file()
+        nx, ny = int(self._header['nx']), int(self._header['ny'])
+        views = [_lib.FrameSum(nx, ny), _lib.FrameSum(nx, ny)]
+        windows = [(a, min(frames_per_view, z0 + n - a), views[i & 1]) for i, a in enumerate(range(z0, z0 + n, frames_per_view))]
+        stream = self._sum_stream(windows, batch, lambda view, grow: None)
+        try:
+            for w in stream:
+                a, k, view = windows[w]
+                yield a, k, view.fetch_view(reset=True)
+        finally:
+            stream.close()
+            for v in views:
+                v.close()
+
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
         more than 16 bits))"""

@@ -1,0 +1,93 @@
+"""ReCoDeViewer: summed views over the part files of a run - the reference's pyrecode/utils/viewer.py on the device.
+
+The reference reads `fractionation` frames ahead from every part file, picks the frames whose ids fall into the window
+[start, start + fractionation) and adds their dense forms on the host (viewer.py:40-75).  Here a part file's share of a window is one
+contiguous range of its records (ids ascend inside a part - the reference's stated assumption, viewer.py:58), every part adds its range into
+ONE device accumulator (ReCoDeReader.sum_frames(into=FrameSum)), and the view that comes back is 4 bytes per pixel.
+
+Deviations from the reference, both on purpose:
+  * the view is (ny, nx); the reference allocates np.zeros((nx, ny)) and can therefore only add square frames (viewer.py:65-68)
+  * only part files that are complete when the viewer opens them are read: a part's records are indexed once, at open, and a file that is
+    still growing is seen as it was then.  (The reference's _get_next_frame_safely is a stub that does not handle it either.)
+get_next_view() returns None once every part is exhausted, where the reference raises on np.max of nothing (viewer.py:73).
+The device's cells are uint32 and never wrap: a window whose sum COULD pass 2^32 - 1 - fractionation * (2^bit_depth - 1) at level 1, i.e.
+more than 65 537 frames of 16 bits, or 1 048 832 of 12 - raises ValueError; the view is reset and the window stays the next one.
+"""
+import os
+
+import numpy as np
+
+
+def plan_view(part_ids, start, fractionation):
+    """The window [start, start + fractionation) over the parts' frame ids - a pure function of the id arrays (ascending inside a part).
+    Returns None when no part holds an id >= start (exhausted), else (ranges, n_frames, next_start): ranges[i] = (lo, hi), the records of
+    part i inside the window; n_frames their number; next_start the largest id found plus one (viewer.py:73) - or, for a window that no
+    frame falls into while later ones exist, the window's end."""
+    start, stop = int(start), int(start) + int(fractionation)
+    if fractionation <= 0:
+        raise ValueError('fractionation must be positive')
+    ranges, last, left = [], -1, False
+    for ids in part_ids:
+        ids = np.asarray(ids)
+        lo, hi = int(np.searchsorted(ids, start, 'left')), int(np.searchsorted(ids, stop, 'left'))
+        ranges.append((lo, hi))
+        left = left or lo < len(ids)
+        if hi > lo:
+            last = max(last, int(ids[hi - 1]))
+    if not left:
+        return None
+    n_frames = sum(hi - lo for lo, hi in ranges)
+    return ranges, n_frames, (last + 1 if n_frames else stop)
+
+
+class ReCoDeViewer:
+
+    def __init__(self, folder_path, base_filename, num_parts, fractionation):
+        from .. import _lib
+        from ..recode_reader import ReCoDeReader
+        self._fractionation = int(fractionation)
+        self._readers = []
+        self._frame_start = 0
+        self._sum = None
+        try:
+            for i in range(int(num_parts)):
+                rd = ReCoDeReader(os.path.join(folder_path, '%s_part%03d' % (base_filename, i)), is_intermediate=True)
+                rd.open(print_header=False)
+                self._readers.append(rd)
+                rd._batch_frames()                               # indexes the part's records: part_frame_ids
+            _, self._ny, self._nx = (int(v) for v in self._readers[0].get_shape())
+            self._sum = _lib.FrameSum(self._nx, self._ny)
+        except Exception:
+            self.close()
+            raise
+
+    def get_shape(self):
+        """(ny, nx) of a view"""
+        return self._ny, self._nx
+
+    def get_next_view(self):
+        plan = plan_view([rd.part_frame_ids for rd in self._readers], self._frame_start, self._fractionation)
+        if plan is None:
+            return None
+        ranges, n_frames, next_start = plan
+        try:
+            for rd, (lo, hi) in zip(self._readers, ranges):
+                if hi > lo:
+                    rd.sum_frames(lo, hi - lo, into=self._sum)
+        except Exception:
+            self._sum.fetch_view(reset=True)                     # (what earlier parts added is no view: start the window afresh)
+            raise
+        if n_frames < self._fractionation:                       # (the reference's message, viewer.py:62-63)
+            print("Warning: read fewer frames (%d) than requested (%d)." % (n_frames, self._fractionation))
+        view = self._sum.fetch_view(reset=True).astype(np.float64)    # (exact: the cells are integers below 2^32)
+        out = {'start': self._frame_start, 'n_Frames': n_frames, 'view': view}
+        self._frame_start = next_start
+        return out
+
+    def close(self):
+        for rd in self._readers:
+            rd.close()
+        self._readers = []
+        if self._sum is not None:
+            self._sum.close()
+            self._sum = None
