@@ -4,6 +4,7 @@ stock decoder takes, and the read-ahead that serves the reference's own frame-at
 (recode_reader.py) inherits BatchedAccess; the methods here use its file handle, header, metadata table and COO helpers.
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -12,38 +13,158 @@ from . import _lib
 from .misc import effective_cpus
 
 
+def _pinned(buf, nbytes):
+    """a _lib.PinnedBuffer of at least `nbytes`: `buf` itself when it is large enough, else a new one with a quarter to spare (`buf` is
+    closed first).  A caller that needs slack behind its data asks for it in `nbytes`."""
+    if buf is None or buf.nbytes < nbytes:
+        if buf is not None:
+            buf.close()
+        buf = _lib.PinnedBuffer(max(int(nbytes * 1.25), 1 << 20))
+    return buf
+
+
+def _l1_cap(sizes, d):
+    """level 1: a frame's packed stream holds one d-bit field per set pixel, so its size bounds the batch's entries without a counting call"""
+    return max(int((sizes[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
+
+
+def _slot_taken(st):
+    """the library's two streaming slots are per process and device: this status of a submit call says that ANOTHER iterator (another
+    reader's) holds the slot.  The batch then goes through the synchronous call, which has resources of its own."""
+    return st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error()
+
+
+def _stock_decoded(h):
+    """whether the stock decoders on the thread pool take the streams of this file (then one device call expands the stored pieces): the
+    route of host-only schemes (zlib / bz2 / lzma) and of zstd / LZ4 streams the device decoders refused"""
+    return int(h['reduction_level']) in (1, 3) and int(h['rc_operation_mode']) == 1 and int(h['compression_scheme']) in (0, 1, 2, 4, 5)
+
+
+def _route(h, foreign, device_blosc, device_zlib, family):
+    """Which way a file's batches go, decided in this one place: ('device', the scheme code they are offered to the device decoders under),
+    ('host-decode', None) - stock decoders on the thread pool, then one device call on the stored pieces - or ('per-frame', None).
+    foreign: the device decoders refused this file's streams once (ReCoDeReader._foreign_file).  family: 'triplets' (get_frames_triplets,
+    iter_frames_triplets, the read-ahead), 'l2' (get_frames_l2, iter_frames_l2) or 'sum' (sum_frames, iter_frame_sums).  The families
+    differ, and each difference is tested behaviour: 'triplets' offers blosc-LZ4 and zlib only behind its switches (device_blosc,
+    device_zlib); 'sum' has no such history to keep and offers both by default - zlib as RC_SCHEME_ZLIB_DEVICE, which refuses every zlib
+    stream but this library's own; 'l2' needs fields of 8 to 16 bits and has no host-decoded route."""
+    level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
+    zlib = level in (1, 3) and mode == 1 and scheme == 0 and not foreign
+    if family == 'l2':
+        taken, schemes, zlib = 8 <= int(h['target_bit_depth']) <= 16, (1, 2, 8), False
+    elif family == 'sum':
+        taken, schemes = True, (1, 2, 8)
+    else:
+        taken, schemes, zlib = level in (1, 3), (1, 2, 8) if device_blosc else (1, 2), zlib and bool(device_zlib)
+    if taken and (mode == 0 or (scheme in schemes and not foreign)):
+        return 'device', scheme
+    if taken and zlib:
+        return 'device', _lib.RC_SCHEME_ZLIB_DEVICE
+    if family != 'l2' and _stock_decoded(h):
+        return 'host-decode', None
+    return 'per-frame', None
+
+
+class _Job:
+    """One batch of a streaming pipeline: frames first .. first + count - 1, the device slot (0 or 1) it goes through, whether it is queued
+    there (submitted and not yet waited for), and what its family keeps between start and finish."""
+    __slots__ = ('first', 'count', 'slot', 'queued', 'payload')
+
+    def __init__(self, first, count, payload=None):
+        self.first, self.count, self.slot, self.queued, self.payload = first, count, 0, False, payload
+
+
+def _jobs(z0, n, batch):
+    return [_Job(a, min(batch, z0 + n - a)) for a in range(z0, z0 + n, batch)]
+
+
+def _wait(job):
+    """the verdict on a queued job: (status, nnz prefix uint64[count + 1])"""
+    prefix = np.zeros(job.count + 1, np.uint64)
+    st = _lib.lib().rc_expand_frames_wait(job.slot, _lib.ptr(prefix))
+    job.queued = False
+    return st, prefix
+
+
+def _drain(job):
+    """a consumer that stops early leaves a job queued: wait for it before its buffers go away (the verdict is of no interest)"""
+    if job is not None and job.queued:
+        _wait(job)
+
+
+class _BatchBuffers:
+    """What a reader's batched access allocates on first use and keeps until the reader is closed: page-locked buffers, host blobs, the
+    mapped file and the thread pools.  close() waits for the pools and frees everything."""
+
+    def __init__(self):
+        self.pin_blob = None                  # page-locked image of a batch's file bytes (the synchronous calls)
+        self.stream = [None] * 4              # [blob 0, blob 1, output 0, output 1] of the streaming iterators' two slots
+        self.l2 = [None, None]                # page-locked statistics of iter_frames_l2's two slots
+        self.pin_pieces = [None] * 3          # stored-pieces images of host-decoded batches: two for the iterator, one for the synchronous call
+        self.host_blobs = [None, None]        # file bytes for the host decoders where the file cannot be mapped
+        self.file_map = None                  # the file, mapped, for the host decoders
+        self.pools = {}
+
+    def pool(self, name, workers):
+        """the thread pool `name`: 'read' (a few threads for page-cache reads), 'decode' (stock decoders of the Python level) or 'coord'
+        (the thread that decodes one batch ahead, _iter_host_decoded)"""
+        if name not in self.pools:
+            from concurrent.futures import ThreadPoolExecutor
+            self.pools[name] = ThreadPoolExecutor(max_workers=workers)
+        return self.pools[name]
+
+    def mapped(self, fp):
+        if self.file_map is None:
+            import mmap
+            try:
+                self.file_map = mmap.mmap(fp.fileno(), 0, access=mmap.ACCESS_READ)
+            except (OSError, ValueError):
+                pass                              # (not mappable: positional reads into a buffer instead)
+        return self.file_map
+
+    def close(self):
+        for p in self.pools.values():
+            p.shutdown(wait=True)
+        for b in [self.pin_blob] + self.stream + self.l2 + self.pin_pieces:
+            if b is not None:
+                b.close()
+        if self.file_map is not None:
+            try:
+                self.file_map.close()
+            except BufferError:                # (a caller still holds a view of a batch: the map goes with it)
+                pass
+        self.__init__()
+
+
 class _BatchOut:
     """Where a batch's expanded entries go and how they are laid out: the reference's uint64 (row, col, value) rows (24 bytes a set
     pixel; rc_expand_frames), or the three arrays of the COO matrix its reader wraps them into - int32 rows | int32 columns | values,
     each `cap` entries long.  value_bytes is the width of a value: 2 (uint16, 10 bytes an entry; rc_expand_frames_coo) or 4 (uint32, 12
     bytes; rc_expand_frames_coo32 - level-1 files of more than 16 bits, see for_file).  holder: None (an array of its own per call) or a
-    one-element list with a _lib.PinnedBuffer / None (page-locked, reused, grown when too small: results are views, valid until its next
-    use)."""
+    list whose element `at` is a _lib.PinnedBuffer / None (page-locked, reused, grown when too small: results are views, valid until its
+    next use)."""
 
-    def __init__(self, coo=False, holder=None, value_bytes=2):
+    def __init__(self, coo=False, holder=None, value_bytes=2, at=0):
         if value_bytes not in (2, 4):
             raise ValueError('COO values are uint16 or uint32')
-        self.coo, self.holder, self.value_bytes = bool(coo), holder, int(value_bytes)
+        self.coo, self.holder, self.at, self.value_bytes = bool(coo), holder, at, int(value_bytes)
         self.esz = 8 + self.value_bytes if coo else 24
         self.buf, self.cap = None, 0
 
     @classmethod
-    def for_file(cls, header, coo=False, holder=None):
+    def for_file(cls, header, coo=False, holder=None, at=0):
         """the layout for a file: its COO values are uint32 when it is a level-1 file whose fields are wider than 16 bits (what the
         reference's reader returns for it: recode_reader.py:464-471, misc.py:41-52), uint16 otherwise"""
         wide = int(header['reduction_level']) == 1 and int(header['target_bit_depth']) > 16
-        return cls(coo, holder, 4 if wide else 2)
+        return cls(coo, holder, 4 if wide else 2, at)
 
     def room(self, cap):
         nbytes = cap * self.esz
         if self.holder is None:
             self.buf = np.empty(nbytes, np.uint8)
         else:
-            if self.holder[0] is None or self.holder[0].nbytes < nbytes:
-                if self.holder[0] is not None:
-                    self.holder[0].close()
-                self.holder[0] = _lib.PinnedBuffer(max(int(nbytes * 1.25), 1 << 20))
-            self.buf = self.holder[0].array[:nbytes]
+            self.holder[self.at] = _pinned(self.holder[self.at], nbytes)
+            self.buf = self.holder[self.at].array[:nbytes]
         self.cap = cap
         return self
 
@@ -75,7 +196,8 @@ class _BatchOut:
 
 
 class BatchedAccess:
-    """Mixin of ReCoDeReader: see the module docstring.  State it uses is declared in ReCoDeReader.__init__."""
+    """Mixin of ReCoDeReader: see the module docstring.  State it uses is declared in ReCoDeReader.__init__; its buffers and pools are
+    ReCoDeReader._bufs (a _BatchBuffers)."""
 
     def _load_part_index(self):
         """Intermediate (part) files carry no metadata table: every record is `u32 frame_id | metadata row | data` (reference
@@ -142,11 +264,96 @@ class BatchedAccess:
         nthr = 4 if int(ats[-1]) >= (8 << 20) and n >= 4 else 1      # (as _read_into: a read from the page cache is a memcpy)
         if nthr == 1:
             return some(0, n)
-        if self._read_pool is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._read_pool = ThreadPoolExecutor(max_workers=4)
         cuts = [n * t // nthr for t in range(nthr + 1)]
-        list(self._read_pool.map(lambda t: some(cuts[t], cuts[t + 1]), range(nthr)))
+        list(self._bufs.pool('read', 4).map(lambda t: some(cuts[t], cuts[t + 1]), range(nthr)))
+
+    def _frame_range(self, z0, n, batch=None):
+        """the number of frames a batched call covers (n, or None: from z0 to the end), checked against the file.  The synchronous calls
+        (batch None) take at least one frame; the iterators take none as well, and a positive batch size"""
+        nz = self._batch_frames()
+        n = nz - z0 if n is None else n
+        if z0 < 0 or z0 + n > nz or (n <= 0 if batch is None else (n < 0 or batch <= 0)):
+            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        return n
+
+    def _route_for(self, family, device_blosc=False, device_zlib=False):
+        return _route(self._header, self._foreign_file, device_blosc, device_zlib, family)
+
+    def _batch_sizes(self, a, k):
+        """(sizes uint32[k][3] as rc_expand_frames & co. take them, bytes of the k frames' data) of frames a .. a+k-1"""
+        level = int(self._header['reduction_level'])
+        sizes = np.zeros((k, 3), np.uint32)
+        for j in range(k):
+            md = self._frame_metadata[a + j]
+            sz_map, sz_val = self._stream_sizes(md)
+            sizes[j, 0] = sz_map
+            if level == 1:
+                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_pixvals'])
+            elif level == 2:
+                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_summary_stats'])     # (the summed views' device call steps over them)
+        return sizes, int(self._seek_table[a:a + k, 0].sum())
+
+    def _frames_one_by_one(self, z0, n):
+        """_get_frame_sparse's result for each of frames z0 .. z0+n-1: the frame-at-a-time path under the batched calls (the stock decoder
+        is the judge, and names the frame that is to blame).  Afterwards a part file's position - get_next_frame's cursor - is where it
+        was, and a merged file's frame counter is behind the batch."""
+        keep = self._fp.tell()
+        for i in range(n):
+            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0)
+            yield self._get_frame_sparse(self._frame_metadata[z0 + i])
+        if self._is_intermediate:
+            self._fp.seek(keep, 0)
+        else:
+            self._note_batch_end(z0 + n)
+
+    def _expand_now(self, mode, scheme, data, sizes, n, dst):
+        """One synchronous device call for n frames (rc_expand_frames & co. into `dst`, a _BatchOut), their streams back to back in `data`
+        and offered under (mode, scheme): (status, nnz prefix, the entries in dst's layout - None unless the status is RC_OK).  Level 1
+        bounds the output from the sizes; level 3 needs a counting call first."""
+        h = self._header
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        L = _lib.lib()
+        prefix = np.zeros(n + 1, np.uint64)
+        args = (int(h['nx']), int(h['ny']), d, level, mode, scheme, _lib.ptr(data), _lib.ptr(sizes), n)
+        if level == 1:
+            cap = _l1_cap(sizes, d)
+        else:
+            st = L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0)
+            if st != _lib.RC_OK:
+                return st, prefix, None
+            cap = max(int(prefix[n]), 1)
+        st = dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap)
+        return st, prefix, dst.result(int(prefix[n])) if st == _lib.RC_OK else None
+
+    def _two_slots(self, jobs, start, finish, stop=None):
+        """The driver of the streaming pipelines: two jobs in flight over the list `jobs` (_Job), job j on slot j & 1 of the whole sequence.
+        start(job) reads the job's bytes and queues it on the device (job.queued says whether it did); finish(job) waits for it and returns
+        the item to yield (None: nothing to yield for this job).  start(j + 1) runs before finish(j): while the device works on one batch
+        the next one is read and copied in.  stop(job), asked before the job behind `job` is started, ends the sequence with `job` waited
+        for and not finished (the caller goes on from job.first by other means).  However the generator ends - a consumer that stops
+        early, an exception -, a job still queued is waited for before its buffers can go away."""
+        def begin(j):
+            jobs[j].slot, jobs[j].queued = j & 1, False
+            start(jobs[j])
+            return jobs[j]
+        queued = None        # the job started last and not finished
+        try:
+            queued = begin(0) if jobs else None
+            for j in range(len(jobs)):
+                job = queued
+                if stop is not None and stop(job):
+                    return
+                queued = begin(j + 1) if j + 1 < len(jobs) else None
+                res = finish(job)
+                self._note_batch_end(job.first + job.count)
+                if res is not None:
+                    yield res
+        finally:
+            if queued is not None:
+                try:
+                    _drain(queued)
+                except Exception:         # (a generator finalised while the interpreter shuts down)
+                    pass
 
     _RA_FRAMES = 32          # frames fetched ahead once the calls turn out to be sequential
     _RA_BYTES = 512 << 20    # ... as long as their triplets fit into this much page-locked memory
@@ -197,9 +404,8 @@ class BatchedAccess:
             if self._ra_buf is None:
                 self._ra_buf = [None]
             keep = (self._current_frame_index, self._fp.tell())
-            mode, scheme = int(self._header['rc_operation_mode']), int(self._header['compression_scheme'])
             try:
-                if (mode == 1 and (scheme in (0, 4, 5) or self._foreign_file)) or self._RA_PIPELINED:
+                if self._route_for('triplets')[0] == 'host-decode' or self._RA_PIPELINED:
                     # The streaming iterator, kept alive between calls: while the caller works through this batch the next one is on its
                     # way - decoded by the helper thread (streams only a stock decoder takes), or read, walked and queued on the device
                     # (this library's own streams; the iterator of another reader that finds the slot taken goes through the
@@ -271,79 +477,40 @@ class BatchedAccess:
         'device-inflate' for a batch the device decoded.  Off by default: the host-decoded path of such files is tested behaviour."""
         h = self._header
         dst = _BatchOut.for_file(h, coo, out)
-        nz = self._batch_frames()
-        if z0 < 0 or n <= 0 or z0 + n > nz:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        zdev = bool(device_zlib) and level in (1, 3) and mode == 1 and scheme == 0 and not self._foreign_file
-        fast = level in (1, 3) and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc) or zdev)
-        host_only = level in (1, 3) and mode == 1 and scheme in (0, 4, 5) and not zdev   # zlib / bz2 / lzma: stock decoder on the thread pool, ONE device expand
-        if fast or host_only:
-            sizes = np.zeros((n, 3), np.uint32)
-            for i in range(n):
-                md = self._frame_metadata[z0 + i]
-                sz_map, sz_val = self._stream_sizes(md)
-                sizes[i, 0] = sz_map
-                if level == 1:
-                    sizes[i, 1] = sz_val
-                    sizes[i, 2] = int(md['bytes_in_packed_pixvals'])
-            lo = self._frame_data_start_position + int(self._seek_table[z0, 1])
-            total = int(self._seek_table[z0:z0 + n, 0].sum())
-            if self._pin_blob is None or self._pin_blob.nbytes < total:   # file -> page-locked memory, no copy in between
-                if self._pin_blob is not None:
-                    self._pin_blob.close()
-                self._pin_blob = _lib.PinnedBuffer(max(int(total * 1.25), 1 << 20))
-            blob = self._pin_blob.array[:total]
+        n = self._frame_range(z0, n)
+        route, dev = self._route_for('triplets', device_blosc, device_zlib)
+        if route != 'per-frame':
+            sizes, total = self._batch_sizes(z0, n)
+            self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total)        # file -> page-locked memory, no copy in between
+            blob = self._bufs.pin_blob.array[:total]
             self._read_batch_into(blob, z0, n)
-            prefix = np.zeros(n + 1, np.uint64)
-            L = _lib.lib()
-            args = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), level, mode, _lib.RC_SCHEME_ZLIB_DEVICE if zdev else scheme,
-                    _lib.ptr(blob), _lib.ptr(sizes), n)
-            if host_only or (mode == 1 and self._foreign_file):
-                st = _lib.RC_ERR_UNSUPPORTED            # (a file whose streams the device decoders refused once is not offered again)
-            elif level == 1:
-                # a frame's packed stream holds one depth-bit field per set pixel: its size bounds the count, one call does it all
-                d = int(h['target_bit_depth'])
-                cap = max(int((sizes[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-                st = dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap)
-            else:
-                st = L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0)        # level 3: a counting call sizes the output
+            if route == 'device':
+                st, prefix, res = self._expand_now(int(h['rc_operation_mode']), dev, blob, sizes, n, dst)
                 if st == _lib.RC_OK:
-                    cap = max(int(prefix[n]), 1)
-                    st = dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap)
-            if st == _lib.RC_OK:
-                self._note_batch_end(z0 + n)
-                self.last_batch_path = 'device-inflate' if zdev else 'device'
-                return prefix, dst.result(int(prefix[n]))
-            # Outside the device decoders' subset - or a stream they could not make sense of (a foreign encoder's independent 64 KiB
-            # LZ4 blocks look like that): the per-frame path below decodes with the stock library, which is also the judge of whether
-            # the file is really damaged.
-            if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_expand_frames')
-            if mode == 1 and scheme != 8:
+                    self._note_batch_end(z0 + n)
+                    self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+                    return prefix, res
+                # Outside the device decoders' subset - or a stream they could not make sense of (a foreign encoder's independent 64 KiB
+                # LZ4 blocks look like that): the paths below decode with the stock library, which is also the judge of whether
+                # the file is really damaged.
+                if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                    _lib.check(st, 'rc_expand_frames')
+            if _stock_decoded(h):
                 res = self._foreign_batch_triplets(z0, n, blob, sizes, dst)
                 if res is not None:
                     self._note_batch_end(z0 + n)
                     self.last_batch_path = 'host-decode + device-expand'
-                    if not host_only:            # (a host-only scheme never is the device decoders' to refuse; a zlib file the device
+                    if route == 'device':            # (a host-only scheme never is the device decoders' to refuse; a zlib file the device
                         self._foreign_file = True    # inflate refused keeps its mark through the host-decoded batches that follow)
                     return res
-        # per-frame path
         self.last_batch_path = 'per-frame'
         parts, prefix = [], np.zeros(n + 1, np.uint64)
-        keep = self._fp.tell()
-        for i in range(n):
-            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0)
-            m = self._get_frame_sparse(self._frame_metadata[z0 + i])     # (not `coo`: that is the caller's layout flag, used below)
+        for i, m in enumerate(self._frames_one_by_one(z0, n)):
             m = m[0] if isinstance(m, tuple) else m
             t = np.stack([m.row.astype(np.uint64), m.col.astype(np.uint64), m.data.astype(np.uint64)], axis=1) if m is not None and m.nnz \
                 else np.zeros((0, 3), np.uint64)
             parts.append(t)
             prefix[i + 1] = prefix[i] + t.shape[0]
-        if self._is_intermediate:
-            self._fp.seek(keep, 0)           # (get_next_frame's cursor)
-        else:
-            self._note_batch_end(z0 + n)
         return prefix, dst.from_triplets(np.concatenate(parts) if parts else np.zeros((0, 3), np.uint64), coo, dst.value_bytes)
 
     def _note_batch_end(self, z):
@@ -358,24 +525,12 @@ class BatchedAccess:
         thread pool (the libraries release the GIL), into the stored-pieces layout of a mode-0 file, and ONE device call expands
         them (rc_expand_frames, op_mode 0).  None: a stock decoder is not available or rejected a stream (the per-frame path
         then reports it)."""
-        h = self._header
-        level, scheme = int(h['reduction_level']), int(h['compression_scheme'])
         got = self._host_decode_batch(blob, sizes, n, 2)        # (an image of its own: the iterator's two may be in use between its steps)
         if got is None:
             return None
-        pieces, sizes0 = got
-        L = _lib.lib()
-        prefix = np.zeros(n + 1, np.uint64)
-        args = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), level, 0, scheme, _lib.ptr(pieces), _lib.ptr(sizes0), n)
-        if level == 1:
-            d = int(h['target_bit_depth'])
-            cap = max(int((sizes0[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-        else:
-            _lib.check(L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0), 'rc_expand_frames')
-            cap = max(int(prefix[n]), 1)
-        dst = dst if dst is not None else _BatchOut()
-        _lib.check(dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap), 'rc_expand_frames')
-        return prefix, dst.result(int(prefix[n]))
+        st, prefix, res = self._expand_now(0, int(self._header['compression_scheme']), *got, n, dst if dst is not None else _BatchOut())
+        _lib.check(st, 'rc_expand_frames')
+        return prefix, res
 
     def _host_decode_batch(self, blob, sizes, n, slot):
         """The 2 n streams of a batch (file bytes in `blob`, stream sizes in `sizes`) through the stock decoder of the file's scheme on the
@@ -383,7 +538,6 @@ class BatchedAccess:
         binary map's nb bytes, the value stream's bytes_in_packed_pixvals).  Returns (pieces, sizes of a mode-0 batch), or None when
         there is no stock decoder for the scheme or it rejected a stream.  `slot` picks one of three images: two for the streaming
         iterator (a batch is decoded while the device still copies the previous one in), one for the synchronous call."""
-        from concurrent.futures import ThreadPoolExecutor
         h = self._header
         level, scheme = int(h['reduction_level']), int(h['compression_scheme'])
         nb = self._structures.binary_image_sz_bytes
@@ -403,14 +557,9 @@ class BatchedAccess:
                 off += int(sizes[i, 1])
                 dst += npk
                 sizes0[i, 1] = sizes0[i, 2] = npk
-        if self._pin_pieces is None:
-            self._pin_pieces = [None, None, None]
-        buf = self._pin_pieces[slot]
-        if buf is None or buf.nbytes < dst + 64:
-            if buf is not None:
-                buf.close()
-            buf = self._pin_pieces[slot] = _lib.PinnedBuffer(int(dst * 1.25) + (1 << 20))
-        pieces = buf.array[:dst]
+        images = self._bufs.pin_pieces
+        images[slot] = _pinned(images[slot], dst + 64)
+        pieces = images[slot].array[:dst]
         # zstd / LZ4 / zlib: the library's own worker threads make the stock library's calls (rc_host_decode_streams) - no
         # interpreter in the loop; the other schemes, or a host without those shared libraries: the Python-level decoders on a pool
         L = _lib.lib()
@@ -429,10 +578,8 @@ class BatchedAccess:
             if want:
                 dec(view[src_off:src_off + src_n], want, pieces[at:at + want])
         try:
-            if self._decode_pool is None:
-                self._decode_pool = ThreadPoolExecutor(max_workers=min(16, effective_cpus()[0]))
             spans.sort(key=lambda sp: -sp[1])            # longest streams first: the pool's tail is then a short one
-            list(self._decode_pool.map(one, spans))
+            list(self._bufs.pool('decode', min(16, effective_cpus()[0])).map(one, spans))
         except Exception:
             return None
         return pieces, sizes0
@@ -441,108 +588,76 @@ class BatchedAccess:
         """iter_frames_triplets for files whose streams only a stock decoder takes (foreign encoders, zlib / bz2 / lzma): batch i + 1 is
         read and decoded on the host's thread pool while the device expands batch i (rc_expand_frames_submit / _wait, op_mode 0, on the
         page-locked stored-pieces image) and the consumer works on its triplets."""
-        from concurrent.futures import ThreadPoolExecutor
         h = self._header
         level, scheme, d = int(h['reduction_level']), int(h['compression_scheme']), int(h['target_bit_depth'])
         L = _lib.lib()
         geom0 = (int(h['nx']), int(h['ny']), d, level, 0, scheme)
-        starts = list(range(z0, z0 + n, batch))
-        if self._stream_bufs is None:
-            self._stream_bufs = [None, None, None, None]
-        if self._host_blobs is None:
-            self._host_blobs = [None, None]
-        if self._decode_coord is None:
-            self._decode_coord = ThreadPoolExecutor(max_workers=1)
-        if self._file_map is None:
-            import mmap
-            try:
-                self._file_map = mmap.mmap(self._fp.fileno(), 0, access=mmap.ACCESS_READ)
-            except (OSError, ValueError):
-                self._file_map = None                                          # (not mappable: positional reads into a buffer instead)
-        bufs = self._stream_bufs
+        jobs = _jobs(z0, n, batch)
+        bufs = self._bufs
+        coord = bufs.pool('coord', 1)
+        file_map = bufs.mapped(self._fp) if not self._is_intermediate else None
 
         def prepare(i):
-            a = starts[i]
-            k = min(batch, z0 + n - a)
-            slot = i & 1
-            sizes = np.zeros((k, 3), np.uint32)
-            for j in range(k):
-                md = self._frame_metadata[a + j]
-                sz_map, sz_val = self._stream_sizes(md)
-                sizes[j, 0] = sz_map
-                if level == 1:
-                    sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_pixvals'])
-            total = int(self._seek_table[a:a + k, 0].sum())
-            lo = self._frame_data_start_position + int(self._seek_table[a, 1])
-            if self._file_map is not None and not self._is_intermediate:
-                blob = np.frombuffer(self._file_map, np.uint8, total, lo)      # the decoders read the page cache itself
+            """read and decode job i on the helper thread: its payload is _host_decode_batch's result"""
+            job = jobs[i]
+            job.slot = i & 1
+            sizes, total = self._batch_sizes(job.first, job.count)
+            if file_map is not None:
+                lo = self._frame_data_start_position + int(self._seek_table[job.first, 1])
+                blob = np.frombuffer(file_map, np.uint8, total, lo)             # the decoders read the page cache itself
             else:
-                if self._host_blobs[slot] is None or self._host_blobs[slot].size < total:
-                    self._host_blobs[slot] = np.empty(int(total * 1.25) + 64, np.uint8)
-                blob = self._host_blobs[slot][:total]
-                self._read_batch_into(blob, a, k, move_fp=False)
-            return a, k, slot, self._host_decode_batch(blob, sizes, k, slot)
+                if bufs.host_blobs[job.slot] is None or bufs.host_blobs[job.slot].size < total:
+                    bufs.host_blobs[job.slot] = np.empty(int(total * 1.25) + 64, np.uint8)
+                blob = bufs.host_blobs[job.slot][:total]
+                self._read_batch_into(blob, job.first, job.count, move_fp=False)
+            job.payload = self._host_decode_batch(blob, sizes, job.count, job.slot)
+            return job
 
-        fut = self._decode_coord.submit(prepare, 0) if starts else None
-        submitted = None
+        fut = coord.submit(prepare, 0) if jobs else None
+        job = None
         try:
-            for i in range(len(starts)):
-                a, k, slot, got = fut.result()
+            for i in range(len(jobs)):
+                job = fut.result()
                 fut = None
-                if got is None:
+                if job.payload is None:
                     # the stock decoder rejected a stream: the synchronous call goes frame by frame and names it (nothing decodes ahead
                     # meanwhile: that call reads the same file and may use the same pools)
-                    res = (a,) + self.get_frames_triplets(a, k, coo=coo)
-                fut = self._decode_coord.submit(prepare, i + 1) if i + 1 < len(starts) else None
-                if got is None:
-                    pass
-                elif level != 1:
-                    # (level 3 needs a counting call to size its output: the synchronous form does both)
-                    pieces, sizes0 = got
-                    prefix = np.zeros(k + 1, np.uint64)
-                    args = geom0 + (_lib.ptr(pieces), _lib.ptr(sizes0), k)
-                    _lib.check(L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0), 'rc_expand_frames')
-                    dst = _BatchOut.for_file(h, coo).room(max(int(prefix[k]), 1))
-                    _lib.check(dst.fn(L)(*args, _lib.ptr(prefix), dst.ptr(), dst.cap), 'rc_expand_frames')
-                    self.last_batch_path = 'host-decode + device-expand'
-                    res = (a, prefix, dst.result(int(prefix[k])))
-                else:
-                    pieces, sizes0 = got
-                    cap = max(int((sizes0[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-                    dst = _BatchOut.for_file(h, coo)
-                    esz = dst.esz
-                    if bufs[2 + slot] is None or bufs[2 + slot].nbytes < cap * esz:
-                        if bufs[2 + slot] is not None:
-                            bufs[2 + slot].close()
-                        bufs[2 + slot] = _lib.PinnedBuffer(max(int(cap * esz * 1.25), 1 << 20))
-                    prefix = np.zeros(k + 1, np.uint64)
-                    st = dst.fn(L, submit=True)(slot, *geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, bufs[2 + slot]._p, cap)
-                    if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
-                        # another iterator of this process holds the slot: the synchronous call has resources of its own
-                        _lib.check(dst.fn(L)(*geom0, _lib.ptr(pieces), _lib.ptr(sizes0), k, _lib.ptr(prefix), bufs[2 + slot]._p, cap),
-                                   'rc_expand_frames')
+                    res = self.get_frames_triplets(job.first, job.count, coo=coo)
+                fut = coord.submit(prepare, i + 1) if i + 1 < len(jobs) else None
+                if job.payload is not None:
+                    pieces, sizes0 = job.payload
+                    res = None
+                    if level == 1:
+                        dst = _BatchOut.for_file(h, coo, bufs.stream, 2 + job.slot)
+                        cap = _l1_cap(sizes0, d)
+                        st = dst.fn(L, submit=True)(job.slot, *geom0, _lib.ptr(pieces), _lib.ptr(sizes0), job.count, dst.room(cap).ptr(), cap)
+                        if not _slot_taken(st):
+                            _lib.check(st, 'rc_expand_frames_submit')
+                            job.queued = True
+                            st, prefix = _wait(job)
+                            _lib.check(st, 'rc_expand_frames_wait')
+                            res = prefix, dst.result(int(prefix[job.count]))
                     else:
-                        _lib.check(st, 'rc_expand_frames_submit')
-                        submitted = (slot, k)
-                        st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
-                        submitted = None
-                        _lib.check(st, 'rc_expand_frames_wait')
-                    total = int(prefix[k])
+                        dst = _BatchOut.for_file(h, coo)
+                    if res is None:
+                        # level 3 needs a counting call to size its output, and the synchronous form does both; at level 1 another
+                        # iterator of this process holds the slot, and the synchronous call has resources of its own
+                        st, prefix, out = self._expand_now(0, scheme, pieces, sizes0, job.count, dst)
+                        _lib.check(st, 'rc_expand_frames')
+                        res = prefix, out
                     self.last_batch_path = 'host-decode + device-expand'
-                    res = (a, prefix, dst.views(bufs[2 + slot].array, cap, total, coo, dst.value_bytes))
-                self._note_batch_end(a + k)
-                yield res
+                self._note_batch_end(job.first + job.count)
+                yield (job.first,) + res
         finally:
             if fut is not None:
                 try:
                     fut.result()          # the decode that runs ahead writes into buffers close() frees
                 except Exception:
                     pass
-            if submitted is not None:
-                try:
-                    L.rc_expand_frames_wait(submitted[0], _lib.ptr(np.zeros(submitted[1] + 1, np.uint64)))
-                except Exception:         # (a generator finalised while the interpreter shuts down)
-                    pass
+            try:
+                _drain(job)
+            except Exception:             # (a generator finalised while the interpreter shuts down)
+                pass
 
     def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False, device_blosc=False, device_zlib=False):
         """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc, device_zlib: as in get_frames_triplets).  The read-ahead under get_frame / get_next_frame keeps
@@ -567,120 +682,71 @@ class BatchedAccess:
         10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo_submit: values uint16), 12 for a level-1 file of more than
         16 bits (rc_expand_frames_coo32_submit: values uint32)."""
         h = self._header
-        nz = self._batch_frames()
-        n = nz - z0 if n is None else n
-        if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        d = int(h['target_bit_depth'])
-        starts = list(range(z0, z0 + n, batch))
-        zdev = bool(device_zlib) and level in (1, 3) and mode == 1 and scheme == 0 and not self._foreign_file
-        if level in (1, 3) and mode == 1 and not zdev and (scheme in (0, 4, 5) or (scheme in (1, 2) and self._foreign_file)):
+        n = self._frame_range(z0, n, batch)
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        route, dev = self._route_for('triplets', device_blosc, device_zlib)
+        if route == 'host-decode':
             yield from self._iter_host_decoded(z0, n, batch, coo)  # stock decoders on the pool, one batch ahead of the device
             return
-        if not (level == 1 and (mode == 0 or scheme in (1, 2) or (scheme == 8 and device_blosc) or zdev)):
-            for a in starts:
-                k = min(batch, z0 + n - a)
-                yield (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
+        jobs = _jobs(z0, n, batch)
+
+        def one_call(job):
+            """the batch through the synchronous call, which knows every fall-back (and sets last_batch_path itself)"""
+            return (job.first,) + self.get_frames_triplets(job.first, job.count, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
+        if not (route == 'device' and level == 1):       # (level 3 needs a counting call per batch: the synchronous form has it)
+            for job in jobs:
+                yield one_call(job)
             return
         L = _lib.lib()
-        geom = (int(h['nx']), int(h['ny']), d, level, mode, _lib.RC_SCHEME_ZLIB_DEVICE if zdev else scheme)
-        dst = _BatchOut.for_file(h, coo)
-        if self._stream_bufs is None:
-            self._stream_bufs = [None, None, None, None]       # page-locked: two input blobs, two outputs; kept until close()
-        bufs = self._stream_bufs
+        zdev = dev == _lib.RC_SCHEME_ZLIB_DEVICE
+        geom = (int(h['nx']), int(h['ny']), d, level, int(h['rc_operation_mode']), dev)
+        bufs = self._bufs.stream                         # page-locked: two input blobs, two outputs; kept until close()
+        outs = [_BatchOut.for_file(h, coo, bufs, 2), _BatchOut.for_file(h, coo, bufs, 3)]
+        resume = []
 
-        def pinned(buf, nbytes):
-            if buf is None or buf.nbytes < nbytes:
-                if buf is not None:
-                    buf.close()
-                buf = _lib.PinnedBuffer(max(int(nbytes * 1.25), 1 << 20))
-            return buf
-
-        def submit(i):
-            """read batch i's bytes into its slot's page-locked blob and queue it; returns what wait needs, or None for 'not on the device'"""
-            a = starts[i]
-            k = min(batch, z0 + n - a)
-            slot = i & 1
-            sizes = np.zeros((k, 3), np.uint32)
-            for j in range(k):
-                md = self._frame_metadata[a + j]
-                sizes[j, 0], sizes[j, 1] = self._stream_sizes(md)
-                sizes[j, 2] = int(md['bytes_in_packed_pixvals'])
-            total = int(self._seek_table[a:a + k, 0].sum())
-            bufs[slot] = pinned(bufs[slot], total + 64)
-            blob = bufs[slot].array[:total]
-            self._read_batch_into(blob, a, k)
-            cap = max(int((sizes[:, 2].astype(np.uint64) * 8 // d).sum()), 1)
-            bufs[2 + slot] = pinned(bufs[2 + slot], cap * dst.esz)
-            st = dst.fn(L, submit=True)(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap)
+        def start(job):
+            """read the job's bytes into its slot's page-locked blob and queue it; not queued: 'not on the device'"""
+            sizes, total = self._batch_sizes(job.first, job.count)
+            bufs[job.slot] = _pinned(bufs[job.slot], total + 64)
+            blob = bufs[job.slot].array[:total]
+            self._read_batch_into(blob, job.first, job.count)
+            cap, dst = _l1_cap(sizes, d), outs[job.slot]
+            st = dst.fn(L, submit=True)(job.slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), job.count, dst.room(cap).ptr(), cap)
             if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
                 if zdev:
                     self._foreign_file = True                 # another zlib encoder's file: one refused batch, the host-decoded path from here on
-                return (a, k, slot, None)
-            if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
-                # the library's two streaming slots are per process and device: ANOTHER iterator (another reader) holds this one.
-                # This batch goes through the synchronous call, which has resources of its own.
-                return (a, k, slot, None)
-            _lib.check(st, 'rc_expand_frames_submit')
-            return (a, k, slot, cap)
+            elif not _slot_taken(st):
+                _lib.check(st, 'rc_expand_frames_submit')
+                job.queued = True
 
         def finish(job):
-            a, k, slot, cap = job
-            if cap is None:
-                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)       # (sets last_batch_path itself)
-            prefix = np.zeros(k + 1, np.uint64)
-            st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
+            if not job.queued:
+                return one_call(job)
+            st, prefix = _wait(job)
             if st == _lib.RC_ERR_UNSUPPORTED and zdev:        # the device inflate refused a stream: another zlib encoder's file
                 self._foreign_file = True
             if st == _lib.RC_ERR_CORRUPT or (st == _lib.RC_ERR_UNSUPPORTED and zdev):      # the stock decoder is the judge
-                return (a,) + self.get_frames_triplets(a, k, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
+                return one_call(job)
             _lib.check(st, 'rc_expand_frames_wait')
-            total = int(prefix[k])
-            trip = dst.views(bufs[2 + slot].array, cap, total, coo, dst.value_bytes)
             self.last_batch_path = 'device-inflate' if zdev else 'device'
-            return a, prefix, trip
-        queued = None        # a batch submitted and not yet waited for
-        try:
-            queued = submit(0) if starts else None
-            for i in range(len(starts)):
-                job = queued
-                if self._foreign_file:
-                    # the previous batch turned out to be a foreign encoder's: the rest of the file goes through the host-decoded pipeline
-                    if job[3] is not None:
-                        L.rc_expand_frames_wait(job[2], _lib.ptr(np.zeros(job[1] + 1, np.uint64)))
-                    queued = None
-                    yield from self._iter_host_decoded(job[0], z0 + n - job[0], batch, coo)
-                    return
-                queued = submit(i + 1) if i + 1 < len(starts) else None
-                res = finish(job)
-                self._note_batch_end(job[0] + job[1])
-                yield res
-        finally:
-            # a consumer that stops early leaves a batch queued: wait for it before its buffers go away
-            if queued is not None and queued[3] is not None:
-                try:
-                    L.rc_expand_frames_wait(queued[2], _lib.ptr(np.zeros(queued[1] + 1, np.uint64)))
-                except Exception:         # (a generator finalised while the interpreter shuts down)
-                    pass
+            return job.first, prefix, outs[job.slot].result(int(prefix[job.count]))
+
+        def stop(job):
+            """a batch turned out to be a foreign encoder's: the rest of the file, from `job` on, goes through the host-decoded pipeline"""
+            if self._foreign_file:
+                resume.append(job.first)
+            return self._foreign_file
+        yield from self._two_slots(jobs, start, finish, stop)
+        if resume:
+            yield from self._iter_host_decoded(resume[0], z0 + n - resume[0], batch, coo)
 
     # ---- level 2 in batches: set pixels and summary statistics (rc_expand_frames_l2) ------------------------------------------
     def _l2_sizes(self, a, k):
         """(sizes uint32[k][3], bytes of the k frames' data, statistics prefix int64[k+1]) of frames a .. a+k-1 of a level-2 file"""
-        d = int(self._header['target_bit_depth'])
-        sizes = np.zeros((k, 3), np.uint32)
-        for j in range(k):
-            md = self._frame_metadata[a + j]
-            sizes[j, 0], sizes[j, 1] = self._stream_sizes(md)
-            sizes[j, 2] = int(md['bytes_in_packed_summary_stats'])
+        sizes, nbytes = self._batch_sizes(a, k)
         sp = np.zeros(k + 1, np.int64)
-        np.cumsum(sizes[:, 2].astype(np.int64) * 8 // d, out=sp[1:])
-        return sizes, int(self._seek_table[a:a + k, 0].sum()), sp
-
-    def _l2_on_device(self):
-        h = self._header
-        mode, scheme = int(h['rc_operation_mode']), int(h['compression_scheme'])
-        return 8 <= int(h['target_bit_depth']) <= 16 and (mode == 0 or scheme in (1, 2, 8)) and not (mode == 1 and self._foreign_file)
+        np.cumsum(sizes[:, 2].astype(np.int64) * 8 // int(self._header['target_bit_depth']), out=sp[1:])
+        return sizes, nbytes, sp
 
     def _l2_per_frame(self, z0, n):
         """get_frames_l2's result from the frame-at-a-time path (_get_frame_sparse): fields narrower than a byte, host-only schemes,
@@ -688,10 +754,7 @@ class BatchedAccess:
         self.last_batch_path = 'per-frame'
         rows, cols, stats = [], [], []
         prefix, sp = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.int64)
-        keep = self._fp.tell()
-        for i in range(n):
-            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0)
-            m, st = self._get_frame_sparse(self._frame_metadata[z0 + i])
+        for i, (m, st) in enumerate(self._frames_one_by_one(z0, n)):
             if m is not None and m.nnz:
                 rows.append(m.row.astype(np.int32))
                 cols.append(m.col.astype(np.int32))
@@ -699,10 +762,6 @@ class BatchedAccess:
                 stats.append(np.asarray(st, self._numpy_dtype))
             prefix[i + 1] = prefix[i] + (m.nnz if m is not None else 0)
             sp[i + 1] = sp[i] + (len(st) if st is not None else 0)
-        if self._is_intermediate:
-            self._fp.seek(keep, 0)
-        else:
-            self._note_batch_end(z0 + n)
         cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
         return prefix, cat(rows, np.int32), cat(cols, np.int32), sp, cat(stats, self._numpy_dtype)
 
@@ -717,17 +776,12 @@ class BatchedAccess:
         h = self._header
         if int(h['reduction_level']) != 2:
             raise ValueError('get_frames_l2 reads reduction level 2 files')
-        nz = self._batch_frames()
-        if z0 < 0 or n <= 0 or z0 + n > nz:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
-        if not self._l2_on_device():
+        n = self._frame_range(z0, n)
+        if self._route_for('l2')[0] != 'device':
             return self._l2_per_frame(z0, n)
         sizes, total, sp = self._l2_sizes(z0, n)
-        if self._pin_blob is None or self._pin_blob.nbytes < total:
-            if self._pin_blob is not None:
-                self._pin_blob.close()
-            self._pin_blob = _lib.PinnedBuffer(max(int(total * 1.25), 1 << 20))
-        blob = self._pin_blob.array[:total]
+        self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total)
+        blob = self._bufs.pin_blob.array[:total]
         self._read_batch_into(blob, z0, n)
         L = _lib.lib()
         geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']))
@@ -757,123 +811,70 @@ class BatchedAccess:
         h = self._header
         if int(h['reduction_level']) != 2:
             raise ValueError('iter_frames_l2 reads reduction level 2 files')
-        nz = self._batch_frames()
-        n = nz - z0 if n is None else n
-        if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
-        starts = list(range(z0, z0 + n, batch))
-        if not self._l2_on_device():
-            for a in starts:
-                yield (a,) + self.get_frames_l2(a, min(batch, z0 + n - a))
+        n = self._frame_range(z0, n, batch)
+        jobs = _jobs(z0, n, batch)
+
+        def one_call(job):
+            """the batch through get_frames_l2, which has resources of its own and knows the fall-back"""
+            return (job.first,) + self.get_frames_l2(job.first, job.count)
+        if self._route_for('l2')[0] != 'device':
+            for job in jobs:
+                yield one_call(job)
             return
         self._ra = None
         self._close_ra_iter()
         L = _lib.lib()
         geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['rc_operation_mode']), int(h['compression_scheme']))
-        if self._stream_bufs is None:
-            self._stream_bufs = [None, None, None, None]
-        if self._l2_bufs is None:
-            self._l2_bufs = [None, None]                       # page-locked statistics of the two slots
-        bufs, sbufs = self._stream_bufs, self._l2_bufs
+        bufs, sbufs = self._bufs.stream, self._bufs.l2
         per_frame = [None]                                     # set pixels per frame of the densest batch so far
 
-        def pinned(buf, nbytes):
-            if buf is None or buf.nbytes < nbytes:
-                if buf is not None:
-                    buf.close()
-                buf = _lib.PinnedBuffer(max(int(nbytes * 1.25), 1 << 20))
-            return buf
-
-        def submit(i):
-            a = starts[i]
-            k = min(batch, z0 + n - a)
-            slot = i & 1
-            sizes, total, sp = self._l2_sizes(a, k)
-            bufs[slot] = pinned(bufs[slot], total + 64)
+        def start(job):
+            """read, size and queue the job: its payload is (room for set pixels, statistics prefix)"""
+            k, slot = job.count, job.slot
+            sizes, total, sp = self._l2_sizes(job.first, k)
+            bufs[slot] = _pinned(bufs[slot], total + 64)
             blob = bufs[slot].array[:total]
-            self._read_batch_into(blob, a, k)
+            self._read_batch_into(blob, job.first, k)
             if per_frame[0] is None:
                 prefix = np.zeros(k + 1, np.uint64)
                 st = L.rc_expand_frames(*geom[:3], 2, *geom[3:], _lib.ptr(blob), _lib.ptr(sizes), k, _lib.ptr(prefix), None, 0)
                 if st != _lib.RC_OK:
-                    return (a, k, slot, None, sp)
+                    return
                 cap = max(int(prefix[k]), 1)
             else:
                 cap = int(per_frame[0] * k * 1.25) + 1024
             ns = int(sp[k])
-            bufs[2 + slot] = pinned(bufs[2 + slot], 8 * cap)
-            sbufs[slot] = pinned(sbufs[slot], 2 * max(ns, 1))
+            bufs[2 + slot] = _pinned(bufs[2 + slot], 8 * cap)
+            sbufs[slot] = _pinned(sbufs[slot], 2 * max(ns, 1))
             st = L.rc_expand_frames_l2_submit(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap, sbufs[slot]._p, ns)
-            if st != _lib.RC_OK:
-                # outside the device subset, or ANOTHER iterator holds the slot: get_frames_l2 has resources of its own and knows the fallback
-                if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT) and not (st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error()):
-                    _lib.check(st, 'rc_expand_frames_l2_submit')
-                return (a, k, slot, None, sp)
-            return (a, k, slot, cap, sp)
+            # not queued: outside the device subset, or ANOTHER iterator holds the slot
+            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT) and not _slot_taken(st):
+                _lib.check(st, 'rc_expand_frames_l2_submit')
+            job.payload, job.queued = SimpleNamespace(cap=cap, sp=sp), st == _lib.RC_OK
 
         def finish(job):
-            a, k, slot, cap, sp = job
-            if cap is None:
-                return (a,) + self.get_frames_l2(a, k)
-            prefix = np.zeros(k + 1, np.uint64)
-            st = L.rc_expand_frames_wait(slot, _lib.ptr(prefix))
+            if not job.queued:
+                return one_call(job)
+            k, cap, sp = job.count, job.payload.cap, job.payload.sp
+            st, prefix = _wait(job)
             if st == _lib.RC_ERR_OUT_TOO_SMALL:
                 per_frame[0] = max(per_frame[0] or 0, int(prefix[k]) / k)
             if st in (_lib.RC_ERR_CORRUPT, _lib.RC_ERR_OUT_TOO_SMALL):
-                return (a,) + self.get_frames_l2(a, k)
+                return one_call(job)
             _lib.check(st, 'rc_expand_frames_wait')
             tot, ns = int(prefix[k]), int(sp[k])
             per_frame[0] = max(per_frame[0] or 0, tot / k)
-            rc = bufs[2 + slot].array[:8 * cap].view(np.int32)
+            rc = bufs[2 + job.slot].array[:8 * cap].view(np.int32)
             self.last_batch_path = 'device'
-            return (a, prefix, rc[:tot].copy(), rc[cap:cap + tot].copy(), sp,
-                    sbufs[slot].array[:2 * ns].view(np.uint16).astype(self._numpy_dtype))
-        queued = None
+            return (job.first, prefix, rc[:tot].copy(), rc[cap:cap + tot].copy(), sp,
+                    sbufs[job.slot].array[:2 * ns].view(np.uint16).astype(self._numpy_dtype))
         self._user_iters += 1
         try:
-            queued = submit(0) if starts else None
-            for i in range(len(starts)):
-                job = queued
-                queued = submit(i + 1) if i + 1 < len(starts) else None
-                res = finish(job)
-                self._note_batch_end(job[0] + job[1])
-                yield res
+            yield from self._two_slots(jobs, start, finish)
         finally:
             self._user_iters -= 1
-            if queued is not None and queued[3] is not None:
-                try:
-                    L.rc_expand_frames_wait(queued[2], _lib.ptr(np.zeros(queued[1] + 1, np.uint64)))
-                except Exception:         # (a generator finalised while the interpreter shuts down)
-                    pass
 
     # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
-    def _sum_sizes(self, a, k):
-        """(sizes uint32[k][3] as rc_sum_add_frames takes them, bytes of the k frames' data) of frames a .. a+k-1"""
-        level = int(self._header['reduction_level'])
-        sizes = np.zeros((k, 3), np.uint32)
-        for j in range(k):
-            md = self._frame_metadata[a + j]
-            sz_map, sz_val = self._stream_sizes(md)
-            sizes[j, 0] = sz_map
-            if level == 1:
-                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_pixvals'])
-            elif level == 2:
-                sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_summary_stats'])     # (stepped over by the device)
-        return sizes, int(self._seek_table[a:a + k, 0].sum())
-
-    def _sum_device_scheme(self):
-        """the scheme code under which this file's batches are offered to the device decoders, or None.  sum_frames has no tested history
-        to keep, so blosc-LZ4 and - as RC_SCHEME_ZLIB_DEVICE, which refuses every zlib stream but this library's own - zlib go there by default"""
-        h = self._header
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        if mode == 0:
-            return scheme
-        if self._foreign_file:
-            return None
-        if scheme in (1, 2, 8):
-            return scheme
-        return _lib.RC_SCHEME_ZLIB_DEVICE if scheme == 0 and level in (1, 3) else None
-
     def _sum_per_frame(self, fs, room, a, k):
         """sum_frames' last route: frames a .. a+k-1 through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge,
         and names the frame that is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the
@@ -884,10 +885,7 @@ class BatchedAccess:
         nb = (nx * ny + 7) // 8
         sizes, parts = np.zeros((k, 3), np.uint32), []
         shifts = np.arange(d, dtype=np.uint32)
-        keep = self._fp.tell()
-        for i in range(k):
-            self._fp.seek(self._frame_data_start_position + int(self._seek_table[a + i, 1]), 0)
-            m = self._get_frame_sparse(self._frame_metadata[a + i])
+        for i, m in enumerate(self._frames_one_by_one(a, k)):
             m = m[0] if isinstance(m, tuple) else m
             dense, vals = np.zeros(ny * nx, bool), np.zeros(0, np.uint32)
             if m is not None and m.nnz:
@@ -901,7 +899,6 @@ class BatchedAccess:
                 packed = np.packbits(((vals[:, None] >> shifts) & 1).astype(np.uint8).reshape(-1), bitorder='little')
                 parts.append(packed)
                 sizes[i, 1] = sizes[i, 2] = packed.size
-        self._fp.seek(keep, 0)
         geom = (nx, ny, d, 1 if level == 1 else 3, 0, 0)
         room(fs, _lib.FrameSum.grows_by(geom, k))
         fs.add(geom, np.ascontiguousarray(np.concatenate(parts)), sizes, k)
@@ -916,81 +913,63 @@ class BatchedAccess:
         h = self._header
         nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
         level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        L = _lib.lib()
-        jobs = [(w, b, min(batch, a + k - b), b + batch >= a + k) for w, (a, k, _) in enumerate(windows) for b in range(a, a + k, batch)]
-        if self._stream_bufs is None:
-            self._stream_bufs = [None, None, None, None]
-        bufs = self._stream_bufs
+        # a job's payload: its window, whether it is the window's last; from start on: sizes, blob, the device scheme (None: not offered),
+        # and the status so far
+        jobs = [_Job(b, min(batch, a + k - b), SimpleNamespace(window=w, last=b + batch >= a + k))
+                for w, (a, k, _) in enumerate(windows) for b in range(a, a + k, batch)]
+        bufs = self._bufs.stream
 
-        def start(j):
-            """read job j's bytes into its slot's page-locked blob and queue it: (window, a, k, last of its window, slot, sizes, blob, device scheme, status)"""
-            w, a, k, last = jobs[j]
-            fs, slot = windows[w][2], j & 1
-            sizes, nbytes = self._sum_sizes(a, k)
-            if bufs[slot] is None or bufs[slot].nbytes < nbytes + 64:
-                if bufs[slot] is not None:
-                    bufs[slot].close()
-                bufs[slot] = _lib.PinnedBuffer(max(int(nbytes * 1.25) + 64, 1 << 20))
-            blob = bufs[slot].array[:nbytes]
-            self._read_batch_into(blob, a, k)
-            dev = self._sum_device_scheme()
-            if dev is None:
-                return (w, a, k, last, slot, sizes, blob, None, None)
-            geom = (nx, ny, d, level, mode, dev)
+        def start(job):
+            """read the job's bytes into its slot's page-locked blob and offer them to the device"""
+            p, k = job.payload, job.count
+            fs = windows[p.window][2]
+            p.sizes, nbytes = self._batch_sizes(job.first, k)
+            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
+            p.blob = bufs[job.slot].array[:nbytes]
+            self._read_batch_into(p.blob, job.first, k)
+            p.dev, p.status = self._route_for('sum')[1], None
+            if p.dev is None:
+                return
+            geom = (nx, ny, d, level, mode, p.dev)
             room(fs, fs.grows_by(geom, k))
-            st = fs.submit_status(slot, geom, blob, sizes, k)
-            if st == _lib.RC_ERR_BAD_ARG and 'submitted batch' in _lib.last_error():
-                st = fs.add_status(geom, blob, sizes, k)      # another reader's iterator holds the slot: the synchronous call has resources of its own
-                return (w, a, k, last, slot, sizes, blob, dev, st)
-            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_sum_add_frames_submit')
-            return (w, a, k, last, slot, sizes, blob, dev, 'queued' if st == _lib.RC_OK else st)
+            p.status = fs.submit_status(job.slot, geom, p.blob, p.sizes, k)
+            if _slot_taken(p.status):
+                p.status = fs.add_status(geom, p.blob, p.sizes, k)      # another reader's iterator holds the slot: the synchronous call has resources of its own
+                return
+            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(p.status, 'rc_sum_add_frames_submit')
+            job.queued = p.status == _lib.RC_OK
 
         def finish(job):
-            w, a, k, _, slot, sizes, blob, dev, st = job
-            fs = windows[w][2]
-            if st == 'queued':
-                st = L.rc_expand_frames_wait(slot, _lib.ptr(np.zeros(k + 1, np.uint64)))
-            if dev is not None and st == _lib.RC_OK:
-                self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-                return
-            if dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+            p, k = job.payload, job.count
+            fs, st = windows[p.window][2], p.status
+            if job.queued:
+                st, _ = _wait(job)
+            if p.dev is not None and st == _lib.RC_OK:
+                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
                 _lib.check(st, 'rc_expand_frames_wait')
-            # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
-            if level in (1, 3) and mode == 1 and scheme in (0, 1, 2, 4, 5):
-                got = self._host_decode_batch(blob, sizes, k, 2)
+            else:
+                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
+                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
                 if got is not None:
-                    pieces, sizes0 = got
                     geom0 = (nx, ny, d, level, 0, scheme)
                     room(fs, fs.grows_by(geom0, k))
-                    fs.add(geom0, pieces, sizes0, k)
+                    fs.add(geom0, *got, k)
                     self.last_batch_path = 'host-decode + device-expand'
-                    if dev is not None:
+                    if p.dev is not None:
                         self._foreign_file = True        # not offered to the device decoders again
-                    return
-            self._sum_per_frame(fs, room, a, k)
+                else:
+                    self._sum_per_frame(fs, room, job.first, k)
+            return p.window if p.last else None
 
         self._ra = None
         self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
         self._user_iters += 1
-        queued = None
         try:
-            queued = start(0) if jobs else None
-            for j in range(len(jobs)):
-                job = queued
-                queued = None
-                queued = start(j + 1) if j + 1 < len(jobs) else None
-                finish(job)
-                self._note_batch_end(job[1] + job[2])
-                if job[3]:
-                    yield job[0]
+            yield from self._two_slots(jobs, start, finish)
         finally:
             self._user_iters -= 1
-            if queued is not None and queued[8] == 'queued':
-                try:
-                    L.rc_expand_frames_wait(queued[4], _lib.ptr(np.zeros(queued[2] + 1, np.uint64)))
-                except Exception:         # (a generator finalised while the interpreter shuts down)
-                    pass
 
     def sum_frames(self, z0=0, n=None, batch=64, into=None):
         """The sum of frames z0 .. z0+n-1 of a merged file (records of a part file) as uint64[ny, nx] - what the reference's viewer and its
@@ -1008,10 +987,7 @@ class BatchedAccess:
         schemes the stock decoders on the thread pool, then one add of the stored pieces ('host-decode + device-expand'); what is left
         goes through the frame-at-a-time reader ('per-frame').  Files of more than 16 bits are not taken (NotImplementedError)."""
         h = self._header
-        nz = self._batch_frames()
-        n = nz - z0 if n is None else n
-        if z0 < 0 or n < 0 or z0 + n > nz or batch <= 0:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        n = self._frame_range(z0, n, batch)
         nx, ny = int(h['nx']), int(h['ny'])
         self._sum_check_file()
         fs = into if into is not None else _lib.FrameSum(nx, ny)
@@ -1049,10 +1025,7 @@ class BatchedAccess:
         it), like the batches of iter_frames_triplets.  A window whose sum could pass 2^32 - 1 raises ValueError."""
         if frames_per_view <= 0 or batch <= 0:
             raise ValueError('frames_per_view and batch must be positive')
-        nz = self._batch_frames()
-        n = nz - z0 if n is None else n
-        if z0 < 0 or n < 0 or z0 + n > nz:
-            raise ValueError('Requested frame index is greater than number of frames in dataset')
+        n = self._frame_range(z0, n, batch)
         self._sum_check_file()
         nx, ny = int(self._header['nx']), int(self._header['ny'])
         views = [_lib.FrameSum(nx, ny), _lib.FrameSum(nx, ny)]

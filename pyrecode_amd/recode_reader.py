@@ -17,7 +17,7 @@ from . import recode_compressors as compressors
 from . import _lib
 from . import c_recode
 from .misc import map_dtype
-from .reader_batched import BatchedAccess, _BatchOut
+from .reader_batched import BatchedAccess, _BatchBuffers, _BatchOut
 from .recode_header import ReCoDeHeader
 from .structures import ReCoDeStructures
 
@@ -41,16 +41,8 @@ class ReCoDeReader(BatchedAccess):
         self._structures = None
         self._numpy_dtype = None
         self._decompressor_context = None
-        # batched access (rc_expand_frames & co.): buffers, pools and bookkeeping, created on first use and released by close()
-        self._pin_blob = None            # page-locked image of a batch's file bytes (get_frames_triplets)
-        self._stream_bufs = None         # [blob 0, blob 1, triplets 0, triplets 1] of the streaming iterator
-        self._l2_bufs = None             # page-locked statistics of iter_frames_l2's two slots
-        self._read_pool = None           # a few threads for page-cache reads
-        self._decode_pool = None         # stock decoders of the Python level (bz2, lzma; zstd / LZ4 without the shared libraries)
-        self._decode_coord = None        # the thread that decodes one batch ahead (_iter_host_decoded)
-        self._pin_pieces = None          # stored-pieces images of host-decoded batches: two for the iterator, one for the synchronous call
-        self._host_blobs = None
-        self._file_map = None            # the file, mapped, for the host decoders
+        # batched access (rc_expand_frames & co.): buffers and pools - created on first use, released by close() - and bookkeeping
+        self._bufs = _BatchBuffers()
         self._foreign_file = False       # the device decoders refused this file's streams once: a stock encoder wrote them
         self._no_fused_frame = False
         self.part_frame_ids = None       # part files: frame id of every record (index built on first batched access)
@@ -163,33 +155,7 @@ class ReCoDeReader(BatchedAccess):
     def close(self):
         self._drop_readahead()
         self._fp.close()
-        if self._pin_blob is not None:
-            self._pin_blob.close()
-            self._pin_blob = None
-        for b in (self._stream_bufs or []) + (self._l2_bufs or []):
-            if b is not None:
-                b.close()
-        self._stream_bufs = self._l2_bufs = None
-        if self._read_pool is not None:
-            self._read_pool.shutdown(wait=True)
-            self._read_pool = None
-        if self._decode_pool is not None:
-            self._decode_pool.shutdown(wait=True)
-            self._decode_pool = None
-        if self._decode_coord is not None:
-            self._decode_coord.shutdown(wait=True)
-            self._decode_coord = None
-        for b in self._pin_pieces or []:
-            if b is not None:
-                b.close()
-        self._pin_pieces = None
-        self._host_blobs = None
-        if self._file_map is not None:
-            try:
-                self._file_map.close()
-            except BufferError:                # (a caller still holds a view of a batch: the map goes with it)
-                pass
-            self._file_map = None
+        self._bufs.close()
 
     def _read_into(self, view, pos, move_fp=True):
         """file bytes [pos, pos + len(view)) -> view (page-locked memory), in a few pieces on worker threads: a read from the page
@@ -202,9 +168,6 @@ class ReCoDeReader(BatchedAccess):
             if self._fp.readinto(memoryview(view)) != total:
                 raise ValueError('file shorter than its seek table says')
             return
-        if self._read_pool is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._read_pool = ThreadPoolExecutor(max_workers=4)
         fd = self._fp.fileno()
         step = -(-total // nthr)
 
@@ -216,7 +179,7 @@ class ReCoDeReader(BatchedAccess):
                 if k <= 0:
                     raise ValueError('file shorter than its seek table says')
                 got += k
-        list(self._read_pool.map(piece, range(nthr)))
+        list(self._bufs.pool('read', 4).map(piece, range(nthr)))
         if move_fp:
             self._fp.seek(pos + total, 0)      # (where a plain read would have left the file)
 

@@ -975,11 +975,13 @@ def test_frame_at_a_time_calls_read_ahead_and_return_the_same_frames(scheme, tmp
         r.close()
 
 
+@pytest.mark.parametrize("family", ["triplets", "sums"])
 @pytest.mark.parametrize("scheme", [0, 1])
-def test_two_streaming_iterators_side_by_side(scheme, tmp_path, orc):
+def test_two_streaming_iterators_side_by_side(scheme, family, tmp_path, orc):
     """The library's two streaming slots belong to the process, not to a reader: two iterators advanced in turn (two readers of two
     files, as a program comparing datasets would) both deliver every frame - the one that finds a slot taken sends that batch through
-    the synchronous call."""
+    the synchronous call.  family: iter_frames_triplets' batches, or iter_frame_sums' views of 4 frames - the second family on the
+    shared two-slot driver, each view compared with the dense sum of its frames."""
     from pyrecode_amd.recode_reader import ReCoDeReader, merge_parts
     ny, nx, d, nz = 64, 256, 12, 13
     g = load_npz("g3_l1z12.npz")
@@ -995,7 +997,10 @@ def test_two_streaming_iterators_side_by_side(scheme, tmp_path, orc):
         rd = ReCoDeReader(str(sub / (tag + ".rc1")), is_intermediate=False)
         rd.open(print_header=False)
         sets.append((rd, np.where(frames > thr, frames - thr, 0).astype(np.uint16)))
-    its = [rd.iter_frames_triplets(batch=3) for rd, _ in sets]
+    if family == "sums":
+        its = [rd.iter_frame_sums(frames_per_view=4, batch=3) for rd, _ in sets]
+    else:
+        its = [rd.iter_frames_triplets(batch=3) for rd, _ in sets]
     seen = [0, 0]
     alive = [True, True]
     while any(alive):
@@ -1006,6 +1011,10 @@ def test_two_streaming_iterators_side_by_side(scheme, tmp_path, orc):
                 a, pre, tr = next(its[j])
             except StopIteration:
                 alive[j] = False
+                continue
+            if family == "sums":           # (first frame, frames, the view)
+                assert np.array_equal(tr, sets[j][1][a:a + pre].sum(axis=0, dtype=np.uint32)), "reader %d view at %d" % (j, a)
+                seen[j] += pre
                 continue
             for i in range(len(pre) - 1):
                 t = tr[int(pre[i]):int(pre[i + 1])]

@@ -424,3 +424,172 @@ def test_out_of_memory_has_a_status_and_an_exception_of_its_own():
             _lib.check(_lib.RC_ERR_WORKSPACE, "rc_ctx_create")
     finally:
         m.last_error = orig
+
+
+def _recording_driver(monkeypatch, njobs, finish_raises_at=None, stop_at=None):
+    """BatchedAccess._two_slots over njobs jobs of 3 frames each with recording fakes: (the generator, its jobs, the log)"""
+    from pyrecode_amd import reader_batched as rb
+    log = []
+
+    class Bare(rb.BatchedAccess):
+        def _note_batch_end(self, z):
+            log.append(("note", z))
+    jobs = rb._jobs(10, 3 * njobs, 3)
+
+    def start(job):
+        log.append(("start", jobs.index(job), job.slot))
+        job.queued = True
+
+    def finish(job):
+        log.append(("finish", jobs.index(job)))
+        job.queued = False
+        if jobs.index(job) == finish_raises_at:
+            raise ValueError("finish %d" % jobs.index(job))
+        return "item %d" % jobs.index(job)
+    monkeypatch.setattr(rb, "_drain", lambda job: log.append(("drain", jobs.index(job))))
+    stop = None if stop_at is None else (lambda job: (log.append(("stop?", jobs.index(job))), jobs.index(job) == stop_at)[1])
+    return Bare()._two_slots(jobs, start, finish, stop), jobs, log
+
+
+def test_two_slot_driver_order_slots_and_drain(monkeypatch):
+    """The driver of the streaming pipelines (BatchedAccess._two_slots): start(j + 1) runs before finish(j), job j goes through slot j & 1,
+    the frame counter is noted after finish and before the item is handed out, and however the generator ends a job that is still queued
+    is drained - once."""
+    gen, jobs, log = _recording_driver(monkeypatch, 0)
+    assert list(gen) == [] and log == []
+    gen, jobs, log = _recording_driver(monkeypatch, 1)
+    assert list(gen) == ["item 0"] and log == [("start", 0, 0), ("finish", 0), ("note", 13)]
+    gen, jobs, log = _recording_driver(monkeypatch, 3)
+    assert [(j.first, j.count) for j in jobs] == [(10, 3), (13, 3), (16, 3)]
+    assert next(gen) == "item 0"
+    assert log == [("start", 0, 0), ("start", 1, 1), ("finish", 0), ("note", 13)]              # noted before the item is handed out
+    assert list(gen) == ["item 1", "item 2"]
+    assert [e for e in log if e[0] in ("start", "finish")] == [("start", 0, 0), ("start", 1, 1), ("finish", 0), ("start", 2, 0), ("finish", 1),
+                                                               ("finish", 2)]
+    assert [j.slot for j in jobs] == [0, 1, 0] and not any(e[0] == "drain" for e in log)
+    # closed after the first item: job 1 is queued and is drained, once
+    gen, jobs, log = _recording_driver(monkeypatch, 3)
+    assert next(gen) == "item 0"
+    gen.close()
+    assert [e for e in log if e[0] == "drain"] == [("drain", 1)] and ("start", 2, 0) not in log
+    # finish raises: the job queued behind it is still drained, and the exception reaches the caller
+    gen, jobs, log = _recording_driver(monkeypatch, 3, finish_raises_at=0)
+    with pytest.raises(ValueError, match="finish 0"):
+        next(gen)
+    assert log == [("start", 0, 0), ("start", 1, 1), ("finish", 0), ("drain", 1)]
+    # the stop hook, asked before the next job is started: the queued job is drained, not finished, and the driver ends
+    gen, jobs, log = _recording_driver(monkeypatch, 3, stop_at=1)
+    assert list(gen) == ["item 0"]
+    assert log == [("start", 0, 0), ("stop?", 0), ("start", 1, 1), ("finish", 0), ("note", 13), ("stop?", 1), ("drain", 1)]
+
+
+def test_drain_waits_only_for_a_queued_job(monkeypatch):
+    """the drain routine proper: a job that is not queued (never submitted, or already waited for) costs no device call"""
+    from pyrecode_amd import reader_batched as rb
+    waited = []
+    monkeypatch.setattr(rb, "_wait", lambda job: waited.append(job.first))
+    job = rb._Job(4, 2)
+    rb._drain(None)
+    rb._drain(job)
+    assert waited == []
+    job.queued = True
+    rb._drain(job)
+    assert waited == [4]
+
+
+# (family, reduction level, operation mode, _foreign_file, then one string per (device_blosc, device_zlib) = (F, F), (F, T), (T, F), (T, T)
+# with one letter per compression scheme 0, 1, 2, 4, 5, 8): D = 'device' under the file's scheme, Z = 'device' under RC_SCHEME_ZLIB_DEVICE,
+# H = 'host-decode', P = 'per-frame'
+ROUTE_TABLE = [
+    ('triplets', 1, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('triplets', 1, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('triplets', 1, 1, False, 'HDDHHP', 'ZDDHHP', 'HDDHHD', 'ZDDHHD'),
+    ('triplets', 1, 1, True , 'HHHHHP', 'HHHHHP', 'HHHHHP', 'HHHHHP'),
+    ('triplets', 2, 0, False, 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('triplets', 2, 0, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('triplets', 2, 1, False, 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('triplets', 2, 1, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('triplets', 3, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('triplets', 3, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('triplets', 3, 1, False, 'HDDHHP', 'ZDDHHP', 'HDDHHD', 'ZDDHHD'),
+    ('triplets', 3, 1, True , 'HHHHHP', 'HHHHHP', 'HHHHHP', 'HHHHHP'),
+    ('l2'      , 1, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 1, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 1, 1, False, 'PDDPPD', 'PDDPPD', 'PDDPPD', 'PDDPPD'),
+    ('l2'      , 1, 1, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('l2'      , 2, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 2, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 2, 1, False, 'PDDPPD', 'PDDPPD', 'PDDPPD', 'PDDPPD'),
+    ('l2'      , 2, 1, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('l2'      , 3, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 3, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('l2'      , 3, 1, False, 'PDDPPD', 'PDDPPD', 'PDDPPD', 'PDDPPD'),
+    ('l2'      , 3, 1, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('sum'     , 1, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 1, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 1, 1, False, 'ZDDHHD', 'ZDDHHD', 'ZDDHHD', 'ZDDHHD'),
+    ('sum'     , 1, 1, True , 'HHHHHP', 'HHHHHP', 'HHHHHP', 'HHHHHP'),
+    ('sum'     , 2, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 2, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 2, 1, False, 'PDDPPD', 'PDDPPD', 'PDDPPD', 'PDDPPD'),
+    ('sum'     , 2, 1, True , 'PPPPPP', 'PPPPPP', 'PPPPPP', 'PPPPPP'),
+    ('sum'     , 3, 0, False, 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 3, 0, True , 'DDDDDD', 'DDDDDD', 'DDDDDD', 'DDDDDD'),
+    ('sum'     , 3, 1, False, 'ZDDHHD', 'ZDDHHD', 'ZDDHHD', 'ZDDHHD'),
+    ('sum'     , 3, 1, True , 'HHHHHP', 'HHHHHP', 'HHHHHP', 'HHHHHP'),
+]
+
+
+@pytest.mark.parametrize("row", ROUTE_TABLE, ids=lambda r: "%s-L%d-m%d-%s" % (r[0].strip(), r[1], r[2], "foreign" if r[3] else "own"))
+def test_route_table(row):
+    """reader_batched._route against the table above.  The table was filled once by evaluating, for every combination, the expressions
+    the readers carried before there was one route function (zdev / fast / host_only of get_frames_triplets, which the two conditions of
+    the streaming iterator agreed with; _l2_on_device; _sum_device_scheme and the host-decode condition of the summed views' finish) - it
+    records that behaviour, it is not derived from _route.  Fields of 12 bits throughout; the level-2 family's limits of 8 and 16 bits
+    are checked at the end.  One cell differs from what the old iterator did and cannot occur: blosc-LZ4 with device_blosc on a
+    file marked foreign was queued by the iterator and then handed on at once; no reader marks a blosc file foreign, and the frames came
+    out frame by frame either way ('P', what get_frames_triplets did)."""
+    from pyrecode_amd import _lib
+    from pyrecode_amd.reader_batched import _route
+    family, level, mode, foreign = row[0].strip(), row[1], row[2], row[3]
+    names = {'D': 'device', 'Z': 'device', 'H': 'host-decode', 'P': 'per-frame'}
+    for cells, (blosc, zl) in zip(row[4:], ((False, False), (False, True), (True, False), (True, True))):
+        for letter, scheme in zip(cells, (0, 1, 2, 4, 5, 8)):
+            h = {'reduction_level': level, 'rc_operation_mode': mode, 'compression_scheme': scheme, 'target_bit_depth': 12}
+            code = {'D': scheme, 'Z': _lib.RC_SCHEME_ZLIB_DEVICE}.get(letter)
+            assert _route(h, foreign, blosc, zl, family) == (names[letter], code), (scheme, blosc, zl)
+            if family == 'l2':
+                for d, ok in ((7, False), (8, True), (16, True), (17, False)):
+                    want = (names[letter], code) if ok else ('per-frame', None)
+                    assert _route(dict(h, target_bit_depth=d), foreign, blosc, zl, family) == want, (scheme, d)
+
+
+def test_pinned_buffer_growth_rule(monkeypatch):
+    """reader_batched._pinned, the one place page-locked buffers are made: a quarter more than asked for and 1 MiB at least; a buffer that
+    is large enough is reused; a smaller one is closed before its successor is made"""
+    from pyrecode_amd import _lib
+    from pyrecode_amd.reader_batched import _pinned, _BatchOut
+    log = []
+
+    class Stub:
+        def __init__(self, nbytes):
+            self.nbytes = nbytes
+            self.array = np.zeros(nbytes, np.uint8)
+            log.append(("new", nbytes))
+
+        def close(self):
+            log.append(("close", self.nbytes))
+    monkeypatch.setattr(_lib, "PinnedBuffer", Stub)
+    a = _pinned(None, 100)
+    assert a.nbytes == 1 << 20 and log == [("new", 1 << 20)]
+    assert _pinned(a, 1 << 20) is a and _pinned(a, 5) is a and len(log) == 1                    # large enough: reused
+    b = _pinned(a, (1 << 20) + 1)
+    assert b is not a and b.nbytes == int(((1 << 20) + 1) * 1.25) and log[1:] == [("close", 1 << 20), ("new", b.nbytes)]   # old one closed first
+    c = _pinned(b, 4 << 20)
+    assert c.nbytes == 5 << 20 and log[3:] == [("close", b.nbytes), ("new", 5 << 20)]
+    # _BatchOut.room goes through it: element `at` of its holder
+    holder = [None, c]
+    out = _BatchOut(coo=True, holder=holder, at=1).room(1000)
+    assert holder[1] is c and out.buf.size == 10000 and len(log) == 5
+    out.room(1 << 20)
+    assert holder[1] is not c and holder[1].nbytes == int(10 * (1 << 20) * 1.25) and log[5] == ("close", 5 << 20) and holder[0] is None
