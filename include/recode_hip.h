@@ -383,6 +383,37 @@ int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint3
                              const uint8_t *data, const uint32_t *sizes, uint32_t n);
 int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset);
 uint64_t rc_sum_bound(const rc_sum *s);
+/* ---- electron counting: one event per connected component ----------------------------------------------------
+ * What l1_to_l4_converter (pyrecode/utils/converters.py:59-123) does with the frames of a level-1 file one at a time on the host -
+ * scipy.ndimage.label with the 3 x 3 structure (:75, :88), then a centroid per label (_get_centroids_2d_nb_w :167-197, _nb_u :200-226,
+ * _nb_m :229-259) - for n frames in one device call: a batch is decoded and counted exactly as by rc_expand_frames, and in place of the
+ * emit kernel the kernels of rc_count.hip label the set pixels (8-connected, within a frame, no wrap from a row's last column to the next
+ * row's first) and reduce every component.  With v a pixel's stored value (level 1: the bit_depth-bit field; levels 2 and 3: 1, a
+ * level-2 frame's statistics stream stepped over): area = pixels, weight = sum v, Sr = sum v * row, Sc = sum v * col - exact integers.
+ *   method          0 weighted average: row = rhe(Sr / weight), col = rhe(Sc / weight), rhe = nearest integer of the exact rational, ties
+ *                     to the even one (np.round, :92); a component of weight 0 is placed as by method 1
+ *                   1 unweighted average: the same with v = 1 for the position (weight stays sum v)
+ *                   2 maximum: the pixel with the largest v, the first in raster order among equals (:243, a strict >)
+ *   area_threshold  an event is kept iff area > area_threshold (:195, :224, :257: a strict >)
+ *   nev_prefix      uint64[n+1] out (host): frame i's events are [nev_prefix[i], nev_prefix[i+1]), ordered by the raster position of
+ *                   their component's first pixel (scipy's label order); two events of a frame on one pixel are both kept
+ *   events          uint64 weight[cap] | int32 rows[cap] | int32 cols[cap] | uint32 area[cap] (20 * cap bytes; host or device), or NULL
+ *                   with cap 0: the counting call.  Events <= set pixels bounds cap
+ * Unlike the reference: the sums are exact (it accumulates in float32), positions are (row, col) (it hands (col, row) to coo_matrix as
+ * (row, col), :100-101), every method is what its helper computes (it sends all three names to the weighted one, :157-164).
+ * nx, ny <= 65535; op_mode / scheme / data / sizes and the device decoders' subset as for rc_expand_frames.  RC_ERR_OUT_TOO_SMALL:
+ * nev_prefix is valid, no byte of events written.  RC_ERR_CORRUPT: a value stream shorter than its set pixels need (or a stream that does
+ * not decode); nothing written.  RC_ERR_UNSUPPORTED: level 1 with bit_depth > 16, 2^32 set pixels or more in one call, and what
+ * rc_expand_frames refuses.  RC_ERR_BAD_ARG: method > 2, NULL / zero arguments.  RC_ERR_DEVICE: no GPU.
+ * rc_count_frames_submit queues the batch on slot 0 or 1 (events_dev: device or page-locked host memory, which is filled only once the
+ * batch is known to be good); rc_expand_frames_wait(slot, nev_prefix) gives its verdict and the prefix.  At levels 2 and 3 the set
+ * pixels are not bounded by the streams' sizes: both forms wait for their count before the workspace is sized. */
+int rc_count_frames(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                    const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold,
+                    uint64_t *nev_prefix, void *events, uint64_t cap);
+int rc_count_frames_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
+                           uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
+                           uint32_t area_threshold, void *events_dev, uint64_t cap);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

@@ -3,6 +3,51 @@
 #include "rc_device.h"
 
 namespace rc {
+// ---- what the kernels of rc_expand.hip and rc_count.hip read a decoded frame with ----------------------------------------------------
+// bitmap is padded with zero bytes to a multiple of 8 by the host wrapper, so 8-byte loads are always in bounds.
+// 64 bitmap bits of word i with the bits of pixels at or past N cleared: a well-formed bitmap has them zero, a foreign or
+// damaged file may not, and the count pass and the emit pass must agree on what they see
+__device__ __forceinline__ uint64_t expand_word(const uint8_t *__restrict__ bitmap, uint64_t nb8, uint64_t N, uint64_t i)
+{
+    if (i >= nb8) return 0;
+    const u32x2 v = reinterpret_cast<const u32x2 *>(bitmap)[i];
+    uint64_t bits = (uint64_t)v[0] | ((uint64_t)v[1] << 32);
+    const uint64_t k0 = i * 64;
+    if (k0 + 64 > N) bits = k0 >= N ? 0 : bits & ((1ull << (N - k0)) - 1);
+    return bits;
+}
+
+// d-bit LSB-first field number `idx` of a packed stream of `nbytes` bytes (bytes past the end read as zero)
+__device__ __forceinline__ uint64_t read_field(const uint8_t *__restrict__ p, uint64_t nbytes, uint64_t idx, uint32_t d)
+{
+    const uint64_t bit = idx * d;
+    uint64_t byte = bit >> 3;
+    const uint32_t sh = (uint32_t)(bit & 7);
+    const uint32_t need = (sh + d + 7) >> 3;  // <= 9 bytes for d <= 64
+    uint64_t lo = 0, hi = 0;
+    for (uint32_t k = 0; k < need && k < 8; ++k)
+        if (byte + k < nbytes) lo |= (uint64_t)p[byte + k] << (8 * k);
+    if (need > 8 && byte + 8 < nbytes) hi = p[byte + 8];
+    uint64_t v = lo >> sh;
+    if (sh && need > 8) v |= hi << (64 - sh);
+    return d >= 64 ? v : (v & ((1ull << d) - 1));
+}
+
+// field `rank` of a frame's decoded value stream, 1 <= d <= 16 (dmask = 2^d - 1): d = 16 is the uint16 itself; a narrower field that ends
+// inside the stream lies in the two dwords at its bit position, the second of which ends before pix_bytes + 8 - inside the frame's slot,
+// zeroed behind the stream (rc_reader.hip: pv_stride; slots are 16-byte aligned); anything else goes byte by byte with every byte
+// checked (read_field)
+__device__ __forceinline__ uint32_t expand_field16(const uint8_t *__restrict__ pix, uint64_t pix_bytes, uint64_t rank, uint32_t d, uint32_t dmask)
+{
+    if (d == 16 && 2 * rank + 2 <= pix_bytes) return reinterpret_cast<const uint16_t *>(pix)[rank];
+    if (d < 16 && rank * d + d <= 8 * pix_bytes) {
+        const uint64_t bit = rank * d;
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(pix) + (bit >> 5);
+        return (uint32_t)((((uint64_t)p[0] | ((uint64_t)p[1] << 32)) >> (bit & 31u))) & dmask;
+    }
+    return (uint32_t)read_field(pix, pix_bytes, rank, d);
+}
+
 void launch_expand_count(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, uint32_t *blk_cnt, uint32_t *blk_off,
                          uint64_t *nnz_dev, hipStream_t s);
 void launch_expand_emit(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, uint32_t nx, const uint32_t *blk_off,
@@ -11,6 +56,8 @@ void launch_expand_emit(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, ui
 void launch_expand_batch_count(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t n, uint32_t *blk_cnt, uint32_t *blk_off,
                                uint64_t *frame_nnz, uint64_t *frame_base, hipStream_t s, const uint32_t *pv_bytes = nullptr, uint32_t d = 0,
                                uint32_t level = 0, uint64_t cap = 0, int *err = nullptr);
+void launch_expand_batch_scan(const uint32_t *cnt, uint32_t *off, uint64_t nb8, uint32_t n, uint64_t *frame_nnz, uint64_t *frame_base, uint64_t cap,
+                              int *err, hipStream_t s);
 // coo_value_bytes: 0 = uint64 (row, col, value) rows; 2 / 4 = int32 rows[cap] | int32 columns[cap] | uint16 / uint32 values[cap]
 void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                               const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d,

@@ -294,6 +294,7 @@ struct ReadRes {
     PinBuf h_blob;                                         // ... host copy of a DEVICE-resident input, for the header walk
     DevBuf d_inf;                                          // device inflate (rc_inflate.hip): stream descriptors, candidate / link / unit tables
     PinBuf h_inf;                                          // ... the descriptors as the host wrote them
+    DevBuf d_count;                                        // electron counting (rc_count.hip): directory, union-find nodes, per-component sums, event counters
     // a submitted batch waiting for its rc_expand_frames_wait
     bool pending = false;
     uint32_t n = 0, level = 0, bit_depth = 0;
@@ -301,6 +302,7 @@ struct ReadRes {
     uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be
     uint32_t late_value_bytes = 0;                         // good (device inflate), its COO value width (0: none) and whether it is COO at all
     bool late_coo = false;
+    bool late_events = false;                              // rc_count_frames_submit: the four event arrays, always copied late (a refused batch writes nothing)
     std::vector<uint32_t> pv_bytes;
 };
 

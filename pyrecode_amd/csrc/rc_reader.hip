@@ -3,6 +3,7 @@
 // decoders (rc_zstd_dec.hip) and the sparse expand (rc_expand.hip) - n frames, both streams, one call, no host round trip in between.
 // Replaces ReCoDeReader._get_frame_sparse (pyrecode/recode_reader.py:379-471) for n frames at once.
 #include "rc_host.h"
+#include "rc_count.h"
 #include "rc_inflate.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
@@ -115,6 +116,15 @@ struct rc_sum {
     uint64_t bound = 0;                // the largest value a cell can hold: sum over the adds of n * (2^d - 1) (level 1) or n (levels 2, 3)
 };
 
+// rc_count_frames' events, staged on the device with the caller's stride: uint64 weight[cap] | int32 rows[cap] | int32 cols[cap] | uint32 area[cap]
+static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, uint64_t total, hipStream_t s)
+{
+    hipError_t e = hipMemcpyAsync(dst, src, total * 8, hipMemcpyDeviceToHost, s);
+    for (uint64_t k = 0; k < 3 && e == hipSuccess; ++k)
+        e = hipMemcpyAsync(dst + cap * (8 + 4 * k), src + cap * (8 + 4 * k), total * 4, hipMemcpyDeviceToHost, s);
+    return e;
+}
+
 // slot, submit_only: rc_expand_frames = (RC_READ_SLOTS - its own resources -, false); rc_expand_frames_submit = (slot, true): returns once everything is queued.
 // coo (bytes of a value, 0 = not): the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] |
 // uint16 (2, rc_expand_frames_coo) or uint32 (4, rc_expand_frames_coo32) values[cap] (k_expand_emit_b<true, ...>): 10 or 12 bytes per set
@@ -124,11 +134,15 @@ struct rc_sum {
 // stepped over and the frame expands like a level-3 one.
 // sum (rc_sum_add_frames / _submit): no entries at all - behind the count, k_expand_sum_b adds the frames' values to the handle's cells
 // (triplets NULL, cap 0).  The gate is the emit kernel's: a batch a decoder or k_expand_bases rejects adds nothing.
+// cnt (rc_count_frames / _submit): no entry per set pixel either - behind the count the kernels of rc_count.hip label the frames' set
+// pixels and write one event per connected component (`triplets` = the event arrays, cap events, 20 bytes each; nnz_prefix = the frames'
+// EVENT prefix).  A level-2 file's statistics stream is stepped over, as for the sum.
+struct CountReq { uint32_t method, area_threshold; };
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
-                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr)
+                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr)
 {
-    const uint64_t esz = l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
+    const uint64_t esz = cnt ? 20 : l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
     if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
         return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
@@ -462,6 +476,63 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     // A submitted batch may also name PAGE-LOCKED host memory: the triplets are then staged in device memory and one asynchronous copy of
     // cap entries follows the emit kernel (the copy engine moves 64 MB in 1.3 ms under the next batch's work; letting the emit kernel
     // write over the link itself - 8-byte stores, 24 bytes apart - took 4 ms).
+    if (cnt) {
+        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
+        // The workspace is sized by the set pixels the batch can hold.  Level 1: a frame's value stream bounds them (k_expand_bases refuses
+        // a frame with more set pixels than its stream has fields), so nothing waits.  Levels 2 and 3: only the frame's size does - the
+        // count is fetched first (one synchronisation, in the submit form too).
+        uint64_t id_cap = 0;
+        if (level == 1)
+            for (uint32_t f = 0; f < n; ++f) id_cap += std::min<uint64_t>(N, 8ull * sizes[3 * f + 2] / bit_depth);
+        else {
+            HIP_TRY(hipMemcpyAsync(h_res, d_fbase + n, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            id_cap = h_res[0];
+        }
+        if (id_cap >= 0xFFFFFFFEull) return bail(RC_ERR_UNSUPPORTED, "rc_count_frames: 2^32 set pixels or more in one call (fewer frames per call)");
+        id_cap = std::max<uint64_t>(id_cap, 1);
+        if ((r = u.d_count.ensure(U.dmem, cnt_workspace_bytes(nb8, n, id_cap, cnt->method) + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+        // events for host memory are staged and copied once the batch is known to be good: a refused batch writes nothing
+        void *events = triplets;
+        const bool staged = triplets && !is_device_ptr(triplets);
+        if (staged) {
+            hipPointerAttribute_t a;
+            if (submit_only && (hipPointerGetAttributes(&a, triplets) != hipSuccess || a.type != hipMemoryTypeHost)) {
+                (void)hipGetLastError();
+                return bail(RC_ERR_BAD_ARG, "rc_count_frames_submit: events must be device or page-locked host memory");
+            }
+            if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+            events = u.d_triplets.p;
+        }
+        launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
+                            cnt->area_threshold, u.d_count.p, id_cap, events, cap, d_err, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_res, cnt_ev_base(u.d_count.p, n), (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
+        if (submit_only) {
+            HIP_TRY(hipEventRecord(u.done, s));
+            u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
+            u.late_events = true; u.late_coo = false; u.late_value_bytes = 0;
+            u.pending = true;
+            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = cap;
+            u.pv_bytes.assign(pv_bytes, pv_bytes + n);
+            return RC_OK;
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        const int err = (int)(uint32_t)h_res[n + 1];
+        memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
+        if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
+        if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
+        if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
+        if (!triplets) return RC_OK;
+        const uint64_t total = nnz_prefix[n];
+        if (total > cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_count_frames: events holds fewer entries than the frames have events");
+        if (staged && total) {
+            HIP_TRY(copy_events(reinterpret_cast<uint8_t *>(triplets), u.d_triplets.p, cap, total, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        return RC_OK;
+    }
     bool dev_out = sum || (triplets && is_device_ptr(triplets));
     uint64_t *host_async = nullptr;
     if (submit_only && !dev_out) {
@@ -496,6 +567,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         u.late_dst = late_copy ? reinterpret_cast<uint8_t *>(host_async) : nullptr;
         u.late_value_bytes = l2out ? 0 : coo;
         u.late_coo = coo != 0;
+        u.late_events = false;
         u.pending = true;
         u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
         u.pv_bytes.assign(pv_bytes, pv_bytes + n);
@@ -636,7 +708,8 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
         // the output staged in d_triplets keeps the caller's layout (triplet rows, or the COO arrays cap entries apart)
         const uint64_t total = nnz_prefix[n];
         const uint8_t *src = u.d_triplets.p;
-        if (!u.late_coo) HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 24, hipMemcpyDeviceToHost, u.stream));
+        if (u.late_events) HIP_TRY(copy_events(u.late_dst, src, u.cap, total, u.stream));
+        else if (!u.late_coo) HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 24, hipMemcpyDeviceToHost, u.stream));
         else {
             HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 4, hipMemcpyDeviceToHost, u.stream));
             HIP_TRY(hipMemcpyAsync(u.late_dst + u.cap * 4, src + u.cap * 4, total * 4, hipMemcpyDeviceToHost, u.stream));
@@ -646,6 +719,38 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
         HIP_TRY(hipStreamSynchronize(u.stream));
     }
     return RC_OK;
+}
+
+// ---- electron counting: one event per connected component of a frame's set pixels (rc_count.hip) -------------------------------------
+static int count_admit(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t method)
+{
+    if (method > rc::CNT_MAX) return fail(RC_ERR_BAD_ARG, "rc_count_frames: method 0 (weighted average), 1 (unweighted average) or 2 (maximum)");
+    if (nx > 65535u || ny > 65535u) return fail(RC_ERR_BAD_ARG, "rc_count_frames: nx, ny in 1..65535");
+    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_count_frames: bit_depth above 16 (the sums are exact in 64 bits for 16-bit values)");
+    return RC_OK;
+}
+
+RC_EXPORT int rc_count_frames(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                              const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, uint64_t *nev_prefix, void *events, uint64_t cap)
+{
+    const int r = count_admit(nx, ny, bit_depth, level, method);
+    if (r != RC_OK) return r;
+    const CountReq req{method, area_threshold};
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, static_cast<uint64_t *>(events), cap, 0, false,
+                      nullptr, 0, nullptr, &req);
+}
+
+RC_EXPORT int rc_count_frames_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                     const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, void *events_dev,
+                                     uint64_t cap)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: slot 0 or 1");
+    if (!events_dev) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: events must be device or page-locked host memory");
+    const int r = count_admit(nx, ny, bit_depth, level, method);
+    if (r != RC_OK) return r;
+    const CountReq req{method, area_threshold};
+    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(events_dev), cap, 0, false, nullptr,
+                      0, nullptr, &req);
 }
 
 // ---- summed views: an accumulator the caller owns, and expand_run's route into it ------------------------------------------------------

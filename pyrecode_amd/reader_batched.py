@@ -44,7 +44,7 @@ def _route(h, foreign, device_blosc, device_zlib, family):
     """Which way a file's batches go, decided in this one place: ('device', the scheme code they are offered to the device decoders under),
     ('host-decode', None) - stock decoders on the thread pool, then one device call on the stored pieces - or ('per-frame', None).
     foreign: the device decoders refused this file's streams once (ReCoDeReader._foreign_file).  family: 'triplets' (get_frames_triplets,
-    iter_frames_triplets, the read-ahead), 'l2' (get_frames_l2, iter_frames_l2) or 'sum' (sum_frames, iter_frame_sums).  The families
+    iter_frames_triplets, the read-ahead), 'l2' (get_frames_l2, iter_frames_l2) or 'sum' (sum_frames, iter_frame_sums; get_frames_counted, iter_frames_counted).  The families
     differ, and each difference is tested behaviour: 'triplets' offers blosc-LZ4 and zlib only behind its switches (device_blosc,
     device_zlib); 'sum' has no such history to keep and offers both by default - zlib as RC_SCHEME_ZLIB_DEVICE, which refuses every zlib
     stream but this library's own; 'l2' needs fields of 8 to 16 bits and has no host-decoded route."""
@@ -63,6 +63,41 @@ def _route(h, foreign, device_blosc, device_zlib, family):
     if family != 'l2' and _stock_decoded(h):
         return 'host-decode', None
     return 'per-frame', None
+
+
+COUNT_METHODS = {'weighted_average': 0, 'unweighted_average': 1, 'max': 2}
+
+
+def count_method(method):
+    """rc_count_frames' code of a method name of the reference's l1_to_l4_converter"""
+    if method not in COUNT_METHODS:
+        raise ValueError("method must be one of 'weighted_average', 'unweighted_average', 'max'")
+    return COUNT_METHODS[method]
+
+
+def _event_views(buf, cap, total):
+    """(rows int32, cols int32, area uint32, weight uint64): the first `total` events of rc_count_frames' output of capacity `cap`"""
+    return (buf[8 * cap:12 * cap].view(np.int32)[:total], buf[12 * cap:16 * cap].view(np.int32)[:total],
+            buf[16 * cap:20 * cap].view(np.uint32)[:total], buf[:8 * cap].view(np.uint64)[:total])
+
+
+def count_frames_now(geom, data, sizes, k, method, area_threshold):
+    """One synchronous rc_count_frames for k frames, their streams back to back in `data` and offered under geom = (nx, ny, bit depth,
+    level, op_mode, scheme): (status, event prefix, (rows, cols, area, weight) - None unless the status is RC_OK).  Events <= set
+    pixels: level 1 bounds them from the sizes; levels 2 and 3 need the counting call first."""
+    L = _lib.lib()
+    prefix = np.zeros(k + 1, np.uint64)
+    args = tuple(geom) + (_lib.ptr(data), _lib.ptr(sizes), k, method, area_threshold)
+    if geom[3] == 1:
+        cap = _l1_cap(sizes, geom[2])
+    else:
+        st = L.rc_count_frames(*args, _lib.ptr(prefix), None, 0)
+        if st != _lib.RC_OK:
+            return st, prefix, None
+        cap = max(int(prefix[k]), 1)
+    buf = np.empty(20 * cap, np.uint8)
+    st = L.rc_count_frames(*args, _lib.ptr(prefix), _lib.ptr(buf), cap)
+    return st, prefix, _event_views(buf, cap, int(prefix[k])) if st == _lib.RC_OK else None
 
 
 class _Job:
@@ -875,11 +910,10 @@ class BatchedAccess:
             self._user_iters -= 1
 
     # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
-    def _sum_per_frame(self, fs, room, a, k):
-        """sum_frames' last route: frames a .. a+k-1 through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge,
-        and names the frame that is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the
-        file's own bit depth, so the handle's bound grows as for any other batch - and added like one: a caller's handle (`into`) receives
-        them too.  A dense mask, a sort and a pack per frame on the host: the slow route's price for serving `into`."""
+    def _stored_pieces_per_frame(self, a, k):
+        """frames a .. a+k-1 through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge, and names the frame that
+        is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the file's own bit depth:
+        (geometry of a mode-0 batch, its bytes, its sizes).  A dense mask, a sort and a pack per frame on the host: the slow route's price."""
         h = self._header
         nx, ny, level, d = int(h['nx']), int(h['ny']), int(h['reduction_level']), int(h['target_bit_depth'])
         nb = (nx * ny + 7) // 8
@@ -899,9 +933,14 @@ class BatchedAccess:
                 packed = np.packbits(((vals[:, None] >> shifts) & 1).astype(np.uint8).reshape(-1), bitorder='little')
                 parts.append(packed)
                 sizes[i, 1] = sizes[i, 2] = packed.size
-        geom = (nx, ny, d, 1 if level == 1 else 3, 0, 0)
+        return (nx, ny, d, 1 if level == 1 else 3, 0, 0), np.ascontiguousarray(np.concatenate(parts)), sizes
+
+    def _sum_per_frame(self, fs, room, a, k):
+        """sum_frames' last route: frames a .. a+k-1 as _stored_pieces_per_frame restates them - so the handle's bound grows as for any
+        other batch - and added like one: a caller's handle (`into`) receives them too."""
+        geom, pieces, sizes = self._stored_pieces_per_frame(a, k)
         room(fs, _lib.FrameSum.grows_by(geom, k))
-        fs.add(geom, np.ascontiguousarray(np.concatenate(parts)), sizes, k)
+        fs.add(geom, pieces, sizes, k)
         self.last_batch_path = 'per-frame'
 
     def _sum_stream(self, windows, batch, room):
@@ -1039,6 +1078,119 @@ class BatchedAccess:
             stream.close()
             for v in views:
                 v.close()
+
+    # ---- electron counting (rc_count_frames): one event per connected component, labelled and reduced on the device -------------------
+    def _count_check_file(self):
+        h = self._header
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        if level not in (1, 2, 3):
+            raise NotImplementedError('counting: reduction level %d' % level)
+        if level == 1 and d > 16:
+            raise NotImplementedError('counting: files of more than 16 bits (target_bit_depth %d): the sums are exact in 64 bits for '
+                                      '16-bit values' % d)
+
+    def _count_stream(self, z0, n, batch, area_threshold, method):
+        """The engine of get_frames_counted and iter_frames_counted: the batches go through rc_count_frames_submit / rc_expand_frames_wait
+        on the two slots, so the next batch is read from the file and queued before this one is waited for.  Levels 2 and 3 have no bound
+        on a batch's events short of its pixels: they go through the synchronous call, which counts first.  Routes and fall-backs are the
+        summed views' (sum_frames)."""
+        h = self._header
+        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
+        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
+        code, thr = count_method(method), int(area_threshold)
+        if not 0 <= thr < 1 << 32:
+            raise ValueError('area_threshold must fit 32 bits')
+        L = _lib.lib()
+        jobs = _jobs(z0, n, batch)
+        bufs = self._bufs.stream
+
+        def start(job):
+            """read the job's bytes into its slot's page-locked blob and offer them to the device; payload: what finish needs"""
+            k = job.count
+            p = job.payload = SimpleNamespace(result=None, cap=0)
+            p.sizes, nbytes = self._batch_sizes(job.first, k)
+            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
+            p.blob = bufs[job.slot].array[:nbytes]
+            self._read_batch_into(p.blob, job.first, k)
+            p.dev, p.status = self._route_for('sum')[1], None
+            if p.dev is None:
+                return
+            geom = (nx, ny, d, level, mode, p.dev)
+            if level == 1:
+                p.cap = _l1_cap(p.sizes, d)
+                bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], 20 * p.cap)
+                p.status = L.rc_count_frames_submit(job.slot, *geom, _lib.ptr(p.blob), _lib.ptr(p.sizes), k, code, thr, bufs[2 + job.slot]._p, p.cap)
+                if p.status == _lib.RC_OK:
+                    job.queued = True
+                    return
+                if not _slot_taken(p.status):
+                    if p.status not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                        _lib.check(p.status, 'rc_count_frames_submit')
+                    return
+            # another reader's iterator holds the slot, or a level without a bound: the synchronous call has resources of its own
+            p.status, p.prefix, p.result = count_frames_now(geom, p.blob, p.sizes, k, code, thr)
+
+        def finish(job):
+            p, k = job.payload, job.count
+            st = p.status
+            if job.queued:
+                st, p.prefix = _wait(job)
+                if st == _lib.RC_OK:
+                    p.result = tuple(a.copy() for a in _event_views(bufs[2 + job.slot].array, p.cap, int(p.prefix[k])))
+            if p.dev is not None and st == _lib.RC_OK:
+                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_count_frames')
+            else:
+                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
+                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
+                if got is not None:
+                    st, p.prefix, p.result = count_frames_now((nx, ny, d, level, 0, scheme), *got, k, code, thr)
+                    self.last_batch_path = 'host-decode + device-expand'
+                    if p.dev is not None:
+                        self._foreign_file = True        # not offered to the device decoders again
+                else:
+                    geom0, pieces, sizes0 = self._stored_pieces_per_frame(job.first, k)
+                    st, p.prefix, p.result = count_frames_now(geom0, pieces, sizes0, k, code, thr)
+                    self.last_batch_path = 'per-frame'
+                _lib.check(st, 'rc_count_frames')
+            return (job.first, p.prefix) + p.result
+
+        self._ra = None
+        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
+        self._user_iters += 1
+        try:
+            yield from self._two_slots(jobs, start, finish)
+        finally:
+            self._user_iters -= 1
+
+    def get_frames_counted(self, z0, n, area_threshold=0, method='weighted_average'):
+        """Electron counting of frames z0 .. z0+n-1 of a merged file (records of a part file) in ONE device call (rc_count_frames): what the
+        reference's l1_to_l4_converter does frame by frame on the host (utils/converters.py:59-123) - every 8-connected puddle of set pixels
+        becomes one event.  Returns (nev_prefix uint64[n+1], rows int32, cols int32, area uint32, weight uint64): frame i's events are
+        [nev_prefix[i], nev_prefix[i+1]) of the four arrays, ordered as scipy.ndimage.label numbers their components; area = the
+        component's pixels, weight = the sum of their values (levels 2 and 3: every value is 1); an event is kept iff area > area_threshold.
+        method: 'weighted_average' (the intensity-weighted centroid, a component of weight 0 placed as by 'unweighted_average'),
+        'unweighted_average' or 'max' (the brightest pixel, the first in raster order among equals).  Centroids are the exact rational
+        rounded half to even - no floating point.  Unlike the reference: it accumulates in float32; it hands (col, row) to coo_matrix as
+        (row, col), here rows are rows; it sends every method name to the weighted helper, here each does what its helper was written
+        for.  Only the events cross the link (20 bytes each).  Routes and last_batch_path as for sum_frames; files of more than 16 bits are
+        not taken (NotImplementedError)."""
+        n = self._frame_range(z0, n)
+        self._count_check_file()
+        stream = self._count_stream(z0, n, n, area_threshold, method)      # (one batch of n frames)
+        try:
+            return next(stream)[1:]
+        finally:
+            stream.close()
+
+    def iter_frames_counted(self, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average'):
+        """get_frames_counted for a whole file, streamed: yields (first frame index, nev_prefix, rows, cols, area, weight) per batch of up to
+        `batch` frames, two batches in flight (rc_count_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
+        n = self._frame_range(z0, n, batch)
+        self._count_check_file()
+        count_method(method)
+        yield from self._count_stream(z0, n, batch, area_threshold, method)
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
