@@ -414,6 +414,35 @@ int rc_count_frames(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduc
 int rc_count_frames_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
                            uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
                            uint32_t area_threshold, void *events_dev, uint64_t cap);
+/* ---- counted views: events summed on the device, with sub-pixel placement ---------------------------------------
+ * The two above together: what a caller of l1_to_l4_converter (pyrecode/utils/converters.py:59-123) who wants the counted IMAGE of a dose
+ * fraction does next - add the frames' events up, as the viewer adds frames (np.add at pyrecode/utils/viewer.py:65-68) - without an event
+ * crossing the link: the batch is decoded, labelled and reduced exactly as by rc_count_frames (method, area_threshold as there), and in the
+ * place of the event arrays every kept component adds ONE count to a cell of an rc_sum handle.
+ *   upsample  1..16: the view's grid is `upsample` times finer than the frame's, the handle is (upsample * nx) x (upsample * ny) cells.
+ *             Pixel centres lie at integers, fine cell k of an axis has its centre at (k - (upsample - 1) / 2) / upsample; the count goes
+ *             to the cell whose centre is nearest to the exact centroid S / w: k = (2 s S + (s - 1) w) / (2 w) rounded to the nearest
+ *             integer, ties to the even one - integer arithmetic, nothing rounded before.  upsample 1 is rc_count_frames' (row, col).
+ *             Method 2 places the winning pixel's centre.  A component of weight 0 is placed by its unweighted sums.
+ *   nx, ny    the FRAME's shape
+ *   nev_prefix  uint64[n+1] out (host), may be NULL: the frames' EVENT prefix, as rc_count_frames gives it
+ * Everything that holds for rc_sum_add_frames holds here: the cells are the caller's handle; the same handle takes plain and counted adds;
+ * batches on both slots may add into one handle; rc_expand_frames_wait(slot, nev_prefix) gives a submitted batch's verdict and the event
+ * prefix; a batch the device rejects adds NOTHING.  At levels 2 and 3 both forms wait for the set-pixel count before the workspace is sized.
+ * No silent wrap: a batch grows rc_sum_bound() by the sum over its frames of
+ *     min(ceil(nx / 2) * ceil(ny / 2), floor(8 * sizes[3 f + 2] / bit_depth))       (levels 2 and 3: the first term alone)
+ * - the components a frame can hold (an aligned 2 x 2 block of pixels belongs to at most one of them) and the set pixels its value stream
+ * has room for; every component is one count and all of them could share a cell - and an add that could take a cell past 2^32 - 1 is refused
+ * with RC_ERR_OUT_TOO_SMALL before anything is queued.
+ * RC_ERR_BAD_ARG: upsample outside 1..16, method > 2, a slot above 1, NULL / zero arguments, nx or ny above 65535, a handle whose shape is
+ * not (upsample * nx, upsample * ny), a handle of another device.  RC_ERR_UNSUPPORTED: level 1 with bit_depth > 16, and what
+ * rc_expand_frames and rc_count_frames refuse.  RC_ERR_CORRUPT: as rc_count_frames.  RC_ERR_DEVICE: no GPU. */
+int rc_sum_add_counted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t reduction_level,
+                       uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
+                       uint32_t area_threshold, uint64_t *nev_prefix);
+int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth,
+                              uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
+                              uint32_t n, uint32_t method, uint32_t area_threshold);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

@@ -81,6 +81,8 @@ SIGNATURES = {
     "rc_count_frames_submit": (C.c_int, [C.c_uint32] * 7 + [_u8p, _u32p] + [C.c_uint32] * 3 + [C.c_void_p, C.c_uint64]),
     "rc_sum_add_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, _u64p]),
     "rc_sum_add_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32]),
+    "rc_sum_add_counted": (C.c_int, [C.c_void_p] + [C.c_uint32] * 7 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_u64p]),
+    "rc_sum_add_counted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 8 + [_u8p, _u32p] + [C.c_uint32] * 3),
     "rc_sum_fetch": (C.c_int, [C.c_void_p, _u32p, C.c_int]),
     "rc_sum_bound": (C.c_uint64, [C.c_void_p]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
@@ -231,6 +233,40 @@ class FrameSum:
     def submit(self, slot, geom, data, sizes, n):
         """Queue the batch on slot 0 or 1 (data stays valid until rc_expand_frames_wait(slot) has returned, which gives the verdict)."""
         check(self.submit_status(slot, geom, data, sizes, n), "rc_sum_add_frames_submit")
+
+    # ---- counted views (rc_sum_add_counted): one count per event of the frames, on a grid `upsample` times finer than theirs --------------
+    def _codec_counted(self, geom, upsample):
+        s = int(upsample)
+        if (s * int(geom[0]), s * int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("FrameSum: frames of %d x %d counted at upsample %d into a view of %d x %d" % (geom[0], geom[1], s, self.nx, self.ny))
+        return (int(geom[0]), int(geom[1]), s) + tuple(int(v) for v in geom[2:6])
+
+    @staticmethod
+    def grows_by_counted(geom, sizes, n):
+        """what a counted batch of n frames adds to bound(): per frame the components it can hold - an aligned 2 x 2 block of pixels belongs
+        to at most one - and, at level 1, no more than the set pixels its value stream has room for"""
+        nx, ny, d, level = (int(v) for v in geom[:4])
+        blocks = ((nx + 1) // 2) * ((ny + 1) // 2)
+        if level != 1:
+            return int(n) * blocks
+        return sum(min(blocks, 8 * int(b) // d) for b in np.asarray(sizes).reshape(-1, 3)[:int(n), 2])
+
+    def add_counted_status(self, geom, data, sizes, n, method=0, area_threshold=0, upsample=1, prefix=None):
+        """rc_sum_add_counted, status returned; method: the code (reader_batched.count_method)"""
+        return lib().rc_sum_add_counted(self._h, *self._codec_counted(geom, upsample), ptr(data), ptr(sizes), n, int(method), int(area_threshold), ptr(prefix))
+
+    def add_counted(self, geom, data, sizes, n, method=0, area_threshold=0, upsample=1):
+        """Count n stored frames' events (rc_count_frames' components, method and area_threshold) into the view, which is `upsample` times
+        finer than the frames: a FrameSum(upsample * nx, upsample * ny).  Returns the frames' EVENT prefix uint64[n + 1].  A rejected batch
+        raises and adds nothing."""
+        prefix = np.zeros(n + 1, np.uint64)
+        check(self.add_counted_status(geom, data, sizes, n, method, area_threshold, upsample, prefix), "rc_sum_add_counted")
+        return prefix
+
+    def submit_counted_status(self, slot, geom, data, sizes, n, method=0, area_threshold=0, upsample=1):
+        """rc_sum_add_counted_submit on slot 0 or 1; rc_expand_frames_wait(slot) gives the verdict and the event prefix"""
+        nx, ny, s, *codec = self._codec_counted(geom, upsample)
+        return lib().rc_sum_add_counted_submit(self._h, slot, nx, ny, s, *codec, ptr(data), ptr(sizes), n, int(method), int(area_threshold))
 
     def fetch(self, reset=False, out=None):
         """uint32[ny, nx]: the cells, after every queued add; reset=True zeroes them and the bound"""

@@ -16,6 +16,8 @@
 //                the wave joins the lanes that share one, before a 64-bit no-return atomic is issued
 //   k_cnt_roots  roots that pass area_threshold, counted per (frame, block); rc_expand.hip's two scans turn the counts into offsets
 //   k_cnt_emit   the events, in id order, with their divisions (rc_count.h: cnt_finish)
+//   k_cnt_place  counted views (rc_sum_add_counted), in the place of k_cnt_roots, the scans and k_cnt_emit: one count per kept component
+//                added to its cell of the caller's view, on a grid up to 16 times finer (rc_count.h: cnt_finish_fine)
 //
 // Every kernel is one lane per 64-pixel word, grid (blocks of WG words, frames), and starts with the same gate: nothing happens once *err
 // is set (a decoder, a short value stream, too many events for the caller's buffer).  Loops: a word's set bits are consumed one per
@@ -46,6 +48,9 @@ struct CntArgs {
     const uint64_t *ev_base;
     uint64_t cap;
     void *events;
+    uint32_t *view;                // counted views: the caller's cells, a grid `up` times finer than the frame (NULL: events)
+    uint64_t view_cells;
+    uint32_t up;
     int *err;
 };
 
@@ -274,6 +279,21 @@ __global__ __launch_bounds__(WG) void k_cnt_roots(CntArgs A)
     if (threadIdx.x == 0) A.ev_cnt[(uint64_t)f * A.nblk + blockIdx.x] = tot;
 }
 
+// the sums of root `id` as k_cnt_acc<M> left them
+template <uint32_t M>
+__device__ __forceinline__ CntSums cnt_sums(const CntArgs &A, uint32_t id)
+{
+    const unsigned long long *s = A.acc + id;
+    CntSums S;
+    S.area = A.area[id];
+    S.a = s[0];
+    S.b = M == CNT_MAX ? 0 : s[A.id_cap];
+    S.w = s[(M == CNT_MAX ? 1 : 2) * A.id_cap];
+    S.za = M == CNT_WEIGHTED ? s[3 * A.id_cap] : 0;
+    S.zb = M == CNT_WEIGHTED ? s[4 * A.id_cap] : 0;
+    return S;
+}
+
 // events = uint64 weight[cap] | int32 rows[cap] | int32 cols[cap] | uint32 area[cap]
 template <uint32_t M>
 __global__ __launch_bounds__(WG) void k_cnt_emit(CntArgs A)
@@ -297,20 +317,44 @@ __global__ __launch_bounds__(WG) void k_cnt_emit(CntArgs A)
         if (e >= A.cap) break;
         const uint32_t b = (uint32_t)__builtin_ctzll(keep);
         const uint32_t id = id0 + (uint32_t)__builtin_popcountll(w & ((1ull << b) - 1ull));
-        const unsigned long long *s = A.acc + id;
-        CntSums S;
-        S.area = A.area[id];
-        S.a = s[0];
-        S.b = M == CNT_MAX ? 0 : s[A.id_cap];
-        S.w = s[(M == CNT_MAX ? 1 : 2) * A.id_cap];
-        S.za = M == CNT_WEIGHTED ? s[3 * A.id_cap] : 0;
-        S.zb = M == CNT_WEIGHTED ? s[4 * A.id_cap] : 0;
+        const CntSums S = cnt_sums<M>(A, id);
         int32_t row, col;
         cnt_finish(M, S, A.nx, &row, &col);
         o_w[e] = S.w;
         o_row[e] = row;
         o_col[e] = col;
         o_area[e] = S.area;
+    }
+}
+
+// Counted views: k_cnt_roots and k_cnt_emit in one pass, and no event.  Every kept root of the lane's word is finished on the finer grid
+// (cnt_finish_fine) and counted into its cell with one 32-bit no-return atomic - the cells belong to the caller's handle, other batches
+// and earlier calls have added to them, and several components of a frame may share one (a ring around a dot).  The block's number of
+// events goes to ev_cnt for the frames' event prefix.  A centroid lies inside its frame, so a cell inside the view (cnt_place); an
+// index that did not would be dropped, not written.
+template <uint32_t M>
+__global__ __launch_bounds__(WG) void k_cnt_place(CntArgs A)
+{
+    __shared__ uint32_t sm[WAVES + 1];
+    if (!cnt_gate(A)) return;
+    const uint32_t f = blockIdx.y;
+    const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    const CntFrame F = cnt_frame(A, f);
+    const uint64_t w = expand_word(F.bm, A.nb8, A.N, i);
+    uint64_t keep = cnt_keep_mask(A, F, w, i);
+    uint32_t tot;
+    (void)block_excl_scan((uint32_t)__builtin_popcountll(keep), sm, &tot);
+    if (threadIdx.x == 0) A.ev_cnt[(uint64_t)f * A.nblk + blockIdx.x] = tot;
+    if (!keep) return;
+    const uint32_t id0 = F.base + F.dir[i];
+    const uint64_t fnx = (uint64_t)A.up * A.nx;
+    for (; keep; keep &= keep - 1) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(keep);
+        const uint32_t id = id0 + (uint32_t)__builtin_popcountll(w & ((1ull << b) - 1ull));
+        uint32_t frow, fcol;
+        cnt_finish_fine(M, cnt_sums<M>(A, id), A.nx, A.up, &frow, &fcol);
+        const uint64_t cell = frow * fnx + fcol;
+        if (fcol < fnx && cell < A.view_cells) (void)atomicAdd(A.view + cell, 1u);
     }
 }
 
@@ -334,12 +378,19 @@ CntLayout cnt_layout(uint64_t nb8, uint32_t n, uint64_t id_cap, uint32_t method)
 }
 
 template <uint32_t M>
-void cnt_launch(const CntArgs &A, uint64_t nb8, uint64_t *ev_nnz, uint64_t *ev_base, uint32_t *ev_off, hipStream_t s)
+void cnt_launch(const CntArgs &A, uint64_t nb8, uint64_t *ev_nnz, uint64_t *ev_base, uint32_t *ev_off, hipEvent_t order, hipStream_t s)
 {
     const dim3 grid(A.nblk, A.n), wg(WG);
     hipLaunchKernelGGL(k_cnt_dir, grid, wg, 0, s, A);
     hipLaunchKernelGGL(k_cnt_link, grid, wg, 0, s, A);
     hipLaunchKernelGGL(k_cnt_acc<M>, grid, wg, 0, s, A);
+    if (A.view) {
+        (void)hipStreamWaitEvent(s, order, 0);
+        hipLaunchKernelGGL(k_cnt_place<M>, grid, wg, 0, s, A);
+        (void)hipEventRecord(order, s);
+        launch_expand_batch_scan(A.ev_cnt, ev_off, nb8, A.n, ev_nnz, ev_base, ~0ull, A.err, s);
+        return;
+    }
     hipLaunchKernelGGL(k_cnt_roots, grid, wg, 0, s, A);
     launch_expand_batch_scan(A.ev_cnt, ev_off, nb8, A.n, ev_nnz, ev_base, A.events ? A.cap : ~0ull, A.err, s);
     if (A.events) hipLaunchKernelGGL(k_cnt_emit<M>, grid, wg, 0, s, A);
@@ -350,10 +401,11 @@ void cnt_launch(const CntArgs &A, uint64_t nb8, uint64_t *ev_nnz, uint64_t *ev_b
 uint64_t cnt_workspace_bytes(uint64_t nb8, uint32_t n, uint64_t id_cap, uint32_t method) { return cnt_layout(nb8, n, id_cap, method).bytes; }
 uint64_t *cnt_ev_base(uint8_t *workspace, uint32_t n) { return reinterpret_cast<uint64_t *>(workspace) + n; }
 
-void launch_count_events(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
-                         const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level,
-                         uint32_t method, uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, void *events, uint64_t cap, int *err,
-                         hipStream_t s)
+namespace {
+void cnt_run(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
+             const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level, uint32_t method,
+             uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, void *events, uint64_t cap, uint32_t *view, uint64_t view_cells,
+             uint32_t upsample, hipEvent_t order, int *err, hipStream_t s)
 {
     const CntLayout L = cnt_layout(nb8, n, id_cap, method);
     uint64_t *ev_nnz = reinterpret_cast<uint64_t *>(workspace), *ev_base = cnt_ev_base(workspace, n);
@@ -371,11 +423,32 @@ void launch_count_events(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, ui
     A.acc = reinterpret_cast<unsigned long long *>(workspace + L.o_sums);
     A.ev_cnt = reinterpret_cast<uint32_t *>(workspace + L.o_evcnt);
     A.ev_off = ev_off; A.ev_base = ev_base;
-    A.cap = cap; A.events = events; A.err = err;
+    A.cap = cap; A.events = events;
+    A.view = view; A.view_cells = view_cells; A.up = upsample;
+    A.err = err;
     (void)hipMemsetAsync(workspace + L.o_sums, 0, L.o_evoff - L.o_sums, s);
-    if (method == CNT_WEIGHTED) cnt_launch<CNT_WEIGHTED>(A, nb8, ev_nnz, ev_base, ev_off, s);
-    else if (method == CNT_UNWEIGHTED) cnt_launch<CNT_UNWEIGHTED>(A, nb8, ev_nnz, ev_base, ev_off, s);
-    else cnt_launch<CNT_MAX>(A, nb8, ev_nnz, ev_base, ev_off, s);
+    if (method == CNT_WEIGHTED) cnt_launch<CNT_WEIGHTED>(A, nb8, ev_nnz, ev_base, ev_off, order, s);
+    else if (method == CNT_UNWEIGHTED) cnt_launch<CNT_UNWEIGHTED>(A, nb8, ev_nnz, ev_base, ev_off, order, s);
+    else cnt_launch<CNT_MAX>(A, nb8, ev_nnz, ev_base, ev_off, order, s);
+}
+}  // namespace
+
+void launch_count_events(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
+                         const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level,
+                         uint32_t method, uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, void *events, uint64_t cap, int *err,
+                         hipStream_t s)
+{
+    cnt_run(bm, bm_stride, nb8, N, nx, n, blk_off, frame_base, pv, pv_stride, pv_bytes, d, level, method, area_threshold, workspace, id_cap, events, cap,
+            nullptr, 0, 1, nullptr, err, s);
+}
+
+void launch_count_place(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
+                        const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level,
+                        uint32_t method, uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, uint32_t *view, uint64_t view_cells,
+                        uint32_t upsample, hipEvent_t order, int *err, hipStream_t s)
+{
+    cnt_run(bm, bm_stride, nb8, N, nx, n, blk_off, frame_base, pv, pv_stride, pv_bytes, d, level, method, area_threshold, workspace, id_cap, nullptr, 0,
+            view, view_cells, upsample, order, err, s);
 }
 
 }  // namespace rc

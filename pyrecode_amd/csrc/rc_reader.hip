@@ -113,7 +113,8 @@ struct rc_sum {
     uint32_t *acc = nullptr;
     hipEvent_t ev = nullptr;
     hipStream_t stream = nullptr;      // fetch / reset
-    uint64_t bound = 0;                // the largest value a cell can hold: sum over the adds of n * (2^d - 1) (level 1) or n (levels 2, 3)
+    uint64_t bound = 0;                // the largest value a cell can hold: sum over the adds of n * (2^d - 1) (level 1) or n (levels 2, 3);
+                                       // a counted add: of the events its frames can hold (counted_admit)
 };
 
 // rc_count_frames' events, staged on the device with the caller's stride: uint64 weight[cap] | int32 rows[cap] | int32 cols[cap] | uint32 area[cap]
@@ -137,7 +138,9 @@ static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, ui
 // cnt (rc_count_frames / _submit): no entry per set pixel either - behind the count the kernels of rc_count.hip label the frames' set
 // pixels and write one event per connected component (`triplets` = the event arrays, cap events, 20 bytes each; nnz_prefix = the frames'
 // EVENT prefix).  A level-2 file's statistics stream is stepped over, as for the sum.
-struct CountReq { uint32_t method, area_threshold; };
+// cnt and sum together (rc_sum_add_counted / _submit): no event array either - the counting kernels end in k_cnt_place, which adds one
+// count per event to the handle's cells, a grid cnt->upsample times finer than the frame (nx, ny are the FRAME's; triplets NULL, cap 0).
+struct CountReq { uint32_t method, area_threshold, upsample; };
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
                       bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr)
@@ -504,8 +507,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
             events = u.d_triplets.p;
         }
-        launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
-                            cnt->area_threshold, u.d_count.p, id_cap, events, cap, d_err, s);
+        if (sum)
+            launch_count_place(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
+                               cnt->area_threshold, u.d_count.p, id_cap, sum->acc, (uint64_t)sum->nx * sum->ny, cnt->upsample, sum->ev, d_err, s);
+        else
+            launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
+                                cnt->area_threshold, u.d_count.p, id_cap, events, cap, d_err, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_res, cnt_ev_base(u.d_count.p, n), (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
@@ -514,7 +521,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
             u.late_events = true; u.late_coo = false; u.late_value_bytes = 0;
             u.pending = true;
-            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = cap;
+            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
             u.pv_bytes.assign(pv_bytes, pv_bytes + n);
             return RC_OK;
         }
@@ -857,4 +864,60 @@ RC_EXPORT int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset)
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (reset) s->bound = 0;
     return RC_OK;
+}
+
+// ---- counted views: one count per event, added to a view up to 16 times finer than the frame (rc_count.hip: k_cnt_place) -------------
+// what both counted adds check before anything is queued - first what needs no device and no look at the handle, then the device, then
+// the handle; *grow: what the batch adds to the handle's bound
+static int counted_admit(const rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level, const uint32_t *sizes,
+                         uint32_t n, uint32_t method, uint64_t *grow)
+{
+    if (!s || !sizes || n == 0 || nx == 0 || ny == 0) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: NULL / zero argument");
+    if (upsample < 1 || upsample > 16) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: upsample in 1..16");
+    int r = count_admit(nx, ny, bit_depth, level, method);
+    if (r != RC_OK) return r;
+    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    {
+        UtilScope util_scope;
+        if ((r = util_scope.enter()) != RC_OK) return r;
+        if (g_util.device != s->device) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: the handle belongs to another device");
+    }
+    if ((uint64_t)upsample * nx != s->nx || (uint64_t)upsample * ny != s->ny)
+        return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: the handle's shape is not (upsample * nx, upsample * ny)");
+    // a frame's events: an aligned 2 x 2 block of pixels belongs to at most one 8-connected component; at level 1 the value stream has room
+    // for floor(8 * bytes / bit_depth) set pixels and k_expand_bases refuses a frame with more
+    const uint64_t blocks = (uint64_t)((nx + 1) / 2) * ((ny + 1) / 2);
+    *grow = 0;
+    for (uint32_t f = 0; f < n; ++f) *grow += level == 1 ? std::min<uint64_t>(blocks, 8ull * sizes[3 * f + 2] / bit_depth) : blocks;
+    if (s->bound + *grow > 0xFFFFFFFFull)
+        return fail(RC_ERR_OUT_TOO_SMALL, "rc_sum_add_counted: a cell could pass 2^32 - 1 (rc_sum_fetch with reset first)");
+    return RC_OK;
+}
+
+RC_EXPORT int rc_sum_add_counted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                 const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, uint64_t *nev_prefix)
+{
+    uint64_t grow = 0;
+    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
+    if (r != RC_OK) return r;
+    std::vector<uint64_t> own;
+    if (!nev_prefix) { own.resize((size_t)n + 1); nev_prefix = own.data(); }
+    const CountReq req{method, area_threshold, upsample};
+    r = expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, nullptr, 0, 0, false, nullptr, 0, s, &req);
+    if (r == RC_OK) s->bound += grow;
+    return r;
+}
+
+RC_EXPORT int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level,
+                                        uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
+                                        uint32_t area_threshold)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_submit: slot 0 or 1");
+    uint64_t grow = 0;
+    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
+    if (r != RC_OK) return r;
+    const CountReq req{method, area_threshold, upsample};
+    r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req);
+    if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
+    return r;
 }

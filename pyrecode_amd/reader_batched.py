@@ -100,6 +100,63 @@ def count_frames_now(geom, data, sizes, k, method, area_threshold):
     return st, prefix, _event_views(buf, cap, int(prefix[k])) if st == _lib.RC_OK else None
 
 
+class _PlainAdder:
+    """What _sum_stream drives into a _lib.FrameSum: the frames' values (rc_sum_add_frames / _submit).  geom is a batch's tuple for
+    rc_expand_frames, frame shape first."""
+    what = 'rc_sum_add_frames'
+
+    @staticmethod
+    def queues(level):
+        """whether batches of this level go through the two slots"""
+        return True
+
+    @staticmethod
+    def view_shape(nx, ny):
+        return nx, ny
+
+    @staticmethod
+    def grows_by(geom, sizes, n):
+        return _lib.FrameSum.grows_by(geom, n)
+
+    @staticmethod
+    def submit_status(fs, slot, geom, data, sizes, n):
+        return fs.submit_status(slot, geom, data, sizes, n)
+
+    @staticmethod
+    def add_status(fs, geom, data, sizes, n):
+        return fs.add_status(geom, data, sizes, n)
+
+
+class _CountedAdder:
+    """The counted add (rc_sum_add_counted / _submit): one count per event of the frames, the view `upsample` times finer than they are.
+    Levels 2 and 3 wait for their set-pixel count inside the call: they go through the synchronous one, as in _count_stream."""
+    what = 'rc_sum_add_counted'
+
+    def __init__(self, method, area_threshold, upsample):
+        self.code, self.thr, self.s = count_method(method), int(area_threshold), int(upsample)
+        if not 0 <= self.thr < 1 << 32:
+            raise ValueError('area_threshold must fit 32 bits')
+        if not 1 <= self.s <= 16:
+            raise ValueError('upsample must be in 1..16')
+
+    @staticmethod
+    def queues(level):
+        return level == 1
+
+    def view_shape(self, nx, ny):
+        return self.s * nx, self.s * ny
+
+    @staticmethod
+    def grows_by(geom, sizes, n):
+        return _lib.FrameSum.grows_by_counted(geom, sizes, n)
+
+    def submit_status(self, fs, slot, geom, data, sizes, n):
+        return fs.submit_counted_status(slot, geom, data, sizes, n, self.code, self.thr, self.s)
+
+    def add_status(self, fs, geom, data, sizes, n):
+        return fs.add_counted_status(geom, data, sizes, n, self.code, self.thr, self.s)
+
+
 class _Job:
     """One batch of a streaming pipeline: frames first .. first + count - 1, the device slot (0 or 1) it goes through, whether it is queued
     there (submitted and not yet waited for), and what its family keeps between start and finish."""
@@ -935,20 +992,21 @@ class BatchedAccess:
                 sizes[i, 1] = sizes[i, 2] = packed.size
         return (nx, ny, d, 1 if level == 1 else 3, 0, 0), np.ascontiguousarray(np.concatenate(parts)), sizes
 
-    def _sum_per_frame(self, fs, room, a, k):
+    def _sum_per_frame(self, fs, room, a, k, adder=_PlainAdder):
         """sum_frames' last route: frames a .. a+k-1 as _stored_pieces_per_frame restates them - so the handle's bound grows as for any
         other batch - and added like one: a caller's handle (`into`) receives them too."""
         geom, pieces, sizes = self._stored_pieces_per_frame(a, k)
-        room(fs, _lib.FrameSum.grows_by(geom, k))
-        fs.add(geom, pieces, sizes, k)
+        room(fs, adder.grows_by(geom, sizes, k))
+        _lib.check(adder.add_status(fs, geom, pieces, sizes, k), adder.what)
         self.last_batch_path = 'per-frame'
 
-    def _sum_stream(self, windows, batch, room):
+    def _sum_stream(self, windows, batch, room, adder=_PlainAdder):
         """The engine of sum_frames and iter_frame_sums: windows = [(first frame, frames > 0, FrameSum)], one after the other; their batches
         go through rc_sum_add_frames_submit / rc_expand_frames_wait on the two slots as ONE sequence, so the next batch - the next window's
         first one, into its own handle, included - is read from the file and queued before this one is waited for.  Yields a window's
         index once every batch of it has been added.  Every device call is made on the caller's thread.  room(fs, grow) is called before
-        an add that grows fs's bound by `grow`.  Routes and fall-backs: see sum_frames."""
+        an add that grows fs's bound by `grow`.  adder: what is added - the frames' values (_PlainAdder) or their events (_CountedAdder).
+        Routes and fall-backs: see sum_frames."""
         h = self._header
         nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
         level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
@@ -970,13 +1028,16 @@ class BatchedAccess:
             if p.dev is None:
                 return
             geom = (nx, ny, d, level, mode, p.dev)
-            room(fs, fs.grows_by(geom, k))
-            p.status = fs.submit_status(job.slot, geom, p.blob, p.sizes, k)
-            if _slot_taken(p.status):
-                p.status = fs.add_status(geom, p.blob, p.sizes, k)      # another reader's iterator holds the slot: the synchronous call has resources of its own
+            room(fs, adder.grows_by(geom, p.sizes, k))
+            if adder.queues(level):
+                p.status = adder.submit_status(fs, job.slot, geom, p.blob, p.sizes, k)
+            if not adder.queues(level) or _slot_taken(p.status):
+                # (a level that waits for its count inside the call, or another reader's iterator holds the slot) the synchronous call
+                # has resources of its own
+                p.status = adder.add_status(fs, geom, p.blob, p.sizes, k)
                 return
             if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(p.status, 'rc_sum_add_frames_submit')
+                _lib.check(p.status, adder.what + '_submit')
             job.queued = p.status == _lib.RC_OK
 
         def finish(job):
@@ -993,13 +1054,13 @@ class BatchedAccess:
                 got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
                 if got is not None:
                     geom0 = (nx, ny, d, level, 0, scheme)
-                    room(fs, fs.grows_by(geom0, k))
-                    fs.add(geom0, *got, k)
+                    room(fs, adder.grows_by(geom0, got[1], k))
+                    _lib.check(adder.add_status(fs, geom0, *got, k), adder.what)
                     self.last_batch_path = 'host-decode + device-expand'
                     if p.dev is not None:
                         self._foreign_file = True        # not offered to the device decoders again
                 else:
-                    self._sum_per_frame(fs, room, job.first, k)
+                    self._sum_per_frame(fs, room, job.first, k, adder)
             return p.window if p.last else None
 
         self._ra = None
@@ -1025,12 +1086,15 @@ class BatchedAccess:
         Routes, per batch (last_batch_path): the device decoders ('device', 'device-inflate'); for streams they refuse and for host-only
         schemes the stock decoders on the thread pool, then one add of the stored pieces ('host-decode + device-expand'); what is left
         goes through the frame-at-a-time reader ('per-frame').  Files of more than 16 bits are not taken (NotImplementedError)."""
-        h = self._header
         n = self._frame_range(z0, n, batch)
-        nx, ny = int(h['nx']), int(h['ny'])
         self._sum_check_file()
-        fs = into if into is not None else _lib.FrameSum(nx, ny)
-        total = None if into is not None else np.zeros((ny, nx), np.uint64)
+        return self._sum_into(z0, n, batch, into, _PlainAdder)
+
+    def _sum_into(self, z0, n, batch, into, adder):
+        """sum_frames and sum_frames_counted behind their argument checks"""
+        vx, vy = adder.view_shape(int(self._header['nx']), int(self._header['ny']))
+        fs = into if into is not None else _lib.FrameSum(vx, vy)
+        total = None if into is not None else np.zeros((vy, vx), np.uint64)
 
         def room(view, grow):
             """this call's own view is folded before `grow` could overflow it (rc_sum_fetch waits for every queued add itself)"""
@@ -1038,7 +1102,7 @@ class BatchedAccess:
                 np.add(total, view.fetch_view(reset=True), out=total)
         try:
             if n:
-                for _ in self._sum_stream([(z0, n, fs)], batch, room):
+                for _ in self._sum_stream([(z0, n, fs)], batch, room, adder):
                     pass
             if total is None:
                 return n
@@ -1066,10 +1130,14 @@ class BatchedAccess:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
-        nx, ny = int(self._header['nx']), int(self._header['ny'])
-        views = [_lib.FrameSum(nx, ny), _lib.FrameSum(nx, ny)]
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _PlainAdder)
+
+    def _iter_sums(self, frames_per_view, z0, n, batch, adder):
+        """iter_frame_sums and iter_frame_sums_counted behind their argument checks"""
+        vx, vy = adder.view_shape(int(self._header['nx']), int(self._header['ny']))
+        views = [_lib.FrameSum(vx, vy), _lib.FrameSum(vx, vy)]
         windows = [(a, min(frames_per_view, z0 + n - a), views[i & 1]) for i, a in enumerate(range(z0, z0 + n, frames_per_view))]
-        stream = self._sum_stream(windows, batch, lambda view, grow: None)
+        stream = self._sum_stream(windows, batch, lambda view, grow: None, adder)
         try:
             for w in stream:
                 a, k, view = windows[w]
@@ -1191,6 +1259,33 @@ class BatchedAccess:
         self._count_check_file()
         count_method(method)
         yield from self._count_stream(z0, n, batch, area_threshold, method)
+
+    # ---- counted views (rc_sum_add_counted): the events of a range of frames summed on the device, on a grid up to 16 times finer ---------
+    def sum_frames_counted(self, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1, into=None):
+        """The counted image of frames z0 .. z0+n-1 as uint64[upsample * ny, upsample * nx]: every event of get_frames_counted (same
+        components, method and area_threshold) is ONE count, added on the device to the cell of a grid `upsample` (1..16) times finer
+        than the sensor's whose centre lies nearest to the event's exact centroid (ties to the even cell index; pixel centres at
+        integers, fine cell k at (k - (upsample - 1) / 2) / upsample).  upsample = 1 is np.add.at of get_frames_counted's (rows, cols).
+        What a caller of the reference's l1_to_l4_converter does with its result on the host (utils/converters.py:59-123, then the
+        viewer's np.add, utils/viewer.py:65-68) - no event crosses the link, 4 bytes per cell do at the end.  The view costs
+        4 * upsample^2 * nx * ny bytes on the device and as much page-locked memory on the host (1 GiB for 4096 x 4096 at 4).
+        into: a _lib.FrameSum(upsample * nx, upsample * ny) - the counts are added into it and the number of frames is returned.
+        Engine, routes, fall-backs, last_batch_path and the fold before a cell could overflow: sum_frames.  Levels 2 and 3 (every value 1)
+        go through the synchronous call.  Files of more than 16 bits are not taken (NotImplementedError)."""
+        n = self._frame_range(z0, n, batch)
+        self._sum_check_file()
+        self._count_check_file()
+        return self._sum_into(z0, n, batch, into, _CountedAdder(method, area_threshold, upsample))
+
+    def iter_frame_sums_counted(self, frames_per_view, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1):
+        """iter_frame_sums with sum_frames_counted's images: yields (first index, count, uint32[upsample * ny, upsample * nx]) per window of
+        `frames_per_view` frames - a VIEW of page-locked memory, valid until the generator is advanced."""
+        if frames_per_view <= 0 or batch <= 0:
+            raise ValueError('frames_per_view and batch must be positive')
+        n = self._frame_range(z0, n, batch)
+        self._sum_check_file()
+        self._count_check_file()
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _CountedAdder(method, area_threshold, upsample))
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of

@@ -12,6 +12,10 @@ Deviations from the reference, both on purpose:
 get_next_view() returns None once every part is exhausted, where the reference raises on np.max of nothing (viewer.py:73).
 The device's cells are uint32 and never wrap: a window whose sum COULD pass 2^32 - 1 - fractionation * (2^bit_depth - 1) at level 1, i.e.
 more than 65 537 frames of 16 bits, or 1 048 832 of 12 - raises ValueError; the view is reset and the window stays the next one.
+
+counting (not in the reference): ReCoDeViewer(..., counting=dict(area_threshold=0, method='weighted_average', upsample=1)) - any subset of
+the keys - makes every view the COUNTED image of its window (ReCoDeReader.sum_frames_counted): one count per electron event, on a grid
+`upsample` times finer than the sensor's; get_shape() is then (upsample * ny, upsample * nx).
 """
 import os
 
@@ -42,10 +46,16 @@ def plan_view(part_ids, start, fractionation):
 
 class ReCoDeViewer:
 
-    def __init__(self, folder_path, base_filename, num_parts, fractionation):
+    def __init__(self, folder_path, base_filename, num_parts, fractionation, counting=None):
         from .. import _lib
         from ..recode_reader import ReCoDeReader
         self._fractionation = int(fractionation)
+        self._counting = None
+        if counting is not None:
+            unknown = set(counting) - {'area_threshold', 'method', 'upsample'}
+            if unknown:
+                raise ValueError('counting: unknown keys %s' % sorted(unknown))
+            self._counting = dict(dict(area_threshold=0, method='weighted_average', upsample=1), **counting)
         self._readers = []
         self._frame_start = 0
         self._sum = None
@@ -55,7 +65,8 @@ class ReCoDeViewer:
                 rd.open(print_header=False)
                 self._readers.append(rd)
                 rd._batch_frames()                               # indexes the part's records: part_frame_ids
-            _, self._ny, self._nx = (int(v) for v in self._readers[0].get_shape())
+            s = int(self._counting['upsample']) if self._counting else 1
+            _, self._ny, self._nx = (s * int(v) for v in self._readers[0].get_shape())
             self._sum = _lib.FrameSum(self._nx, self._ny)
         except Exception:
             self.close()
@@ -72,7 +83,9 @@ class ReCoDeViewer:
         ranges, n_frames, next_start = plan
         try:
             for rd, (lo, hi) in zip(self._readers, ranges):
-                if hi > lo:
+                if hi > lo and self._counting:
+                    rd.sum_frames_counted(lo, hi - lo, into=self._sum, **self._counting)
+                elif hi > lo:
                     rd.sum_frames(lo, hi - lo, into=self._sum)
         except Exception:
             self._sum.fetch_view(reset=True)                     # (what earlier parts added is no view: start the window afresh)
