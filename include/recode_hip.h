@@ -443,6 +443,36 @@ int rc_sum_add_counted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, u
 int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth,
                               uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                               uint32_t n, uint32_t method, uint32_t area_threshold);
+/* ---- dense frame batches: a region of every frame as an array, written on the device ----------------------------
+ * What ReCoDeReader.get_sub_volume would return in the reference, where it is a stub (pyrecode/recode_reader.py:185-186), and what its
+ * callers do instead with every frame on the host - frame.toarray(), a memset and a scatter (pyrecode/utils/viewer.py:65-68): a batch is
+ * decoded and counted exactly as by rc_expand_frames, and in place of the emit kernel one kernel (k_expand_dense_b) writes
+ *   out[f][j][i] = the value of source pixel (y0 + j * step_y, x0 + i * step_x) of frame f,   f < n, j < h, i < w,
+ * row-major, frames back to back, cells of cell_bytes bytes.  Level 1: a set pixel's bit_depth-bit field; levels 2 and 3: 1 (a level-2
+ * frame's statistics stream is stepped over); an unset pixel: 0.  EVERY cell is written exactly once, zeros included: out needs no
+ * memset and what it held does not matter.  Levels 2 and 3 need no counting call first.
+ *   x0, y0, w, h, step_x, step_y  the region; w and h are the OUTPUT's size.  RC_ERR_BAD_ARG: a step, w or h of 0,
+ *                 x0 + (w - 1) * step_x >= nx, y0 + (h - 1) * step_y >= ny, nx or ny above 65535
+ *   cell_bytes    1, 2 or 4 (unsigned cells); at level 1 bit_depth > 8 * cell_bytes is RC_ERR_BAD_ARG, bit_depth > 32 RC_ERR_UNSUPPORTED
+ *   out           cell_bytes-aligned (no more: frames of 3 x 21 uint16 cells are 126 bytes each), device or host memory: device memory is
+ *                 written by the kernel itself, host memory is staged on the device and copied once the batch is known to be good
+ *   out_cells     cells out has room for; fewer than n * w * h is RC_ERR_OUT_TOO_SMALL
+ *   nnz_prefix    uint64[n+1] out (host), may be NULL: the frames' set-pixel prefix over the WHOLE frames, not the region - what
+ *                 rc_expand_frames gives, to cross-check against the COO route
+ * All of the above are known from the arguments alone and reported before any device work, in both forms.
+ * op_mode / scheme, data (host or device), sizes and the device decoders' subset as for rc_expand_frames.  A batch that is refused - a
+ * decoder's RC_ERR_CORRUPT or RC_ERR_UNSUPPORTED, a level-1 value stream shorter than its set pixels need (RC_ERR_CORRUPT) - writes NOTHING
+ * to out.  RC_ERR_DEVICE: no GPU.
+ * rc_expand_frames_dense_submit queues the batch on slot 0 or 1 (out: device memory, or page-locked host memory, which gets ONE
+ * asynchronous copy from the staged cells after the verdict, like rc_count_frames_submit's events; anything else is RC_ERR_BAD_ARG);
+ * rc_expand_frames_wait(slot, nnz_prefix) gives its verdict and the prefix. */
+int rc_expand_frames_dense(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                           const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                           uint32_t step_x, uint32_t step_y, uint32_t cell_bytes, void *out, uint64_t out_cells, uint64_t *nnz_prefix);
+int rc_expand_frames_dense_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode,
+                                  uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0,
+                                  uint32_t w, uint32_t h, uint32_t step_x, uint32_t step_y, uint32_t cell_bytes, void *out,
+                                  uint64_t out_cells);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

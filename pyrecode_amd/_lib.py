@@ -75,6 +75,8 @@ SIGNATURES = {
     "rc_expand_frames_coo32_submit": (C.c_int, [C.c_uint32] * 7 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_expand_frames_l2": (C.c_int, [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, _u64p, C.c_void_p, C.c_uint64, _u16p, C.c_uint64]),
     "rc_expand_frames_l2_submit": (C.c_int, [C.c_uint32] * 6 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u16p, C.c_uint64]),
+    "rc_expand_frames_dense": (C.c_int, [C.c_uint32] * 6 + [_u8p, _u32p] + [C.c_uint32] * 8 + [C.c_void_p, C.c_uint64, _u64p]),
+    "rc_expand_frames_dense_submit": (C.c_int, [C.c_uint32] * 7 + [_u8p, _u32p] + [C.c_uint32] * 8 + [C.c_void_p, C.c_uint64]),
     "rc_sum_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "rc_sum_destroy": (C.c_int, [C.c_void_p]),
     "rc_count_frames": (C.c_int, [C.c_uint32] * 6 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_u64p, C.c_void_p, C.c_uint64]),

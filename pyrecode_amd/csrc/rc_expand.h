@@ -48,6 +48,26 @@ __device__ __forceinline__ uint32_t expand_field16(const uint8_t *__restrict__ p
     return (uint32_t)read_field(pix, pix_bytes, rank, d);
 }
 
+// the same for 17 <= d <= 32, from dwords (value streams are 16-byte aligned): d = 32 is the dword itself; a narrower field that ends inside
+// the stream lies inside the two dwords at its bit position.  Its last bit is below 8 * pix_bytes, so the first dword starts below pix_bytes
+// and the second one ends before pix_bytes + 8 - inside the frame's slot, which is the longest stream rounded up to 16 bytes plus 16 more,
+// zeroed behind the stream (rc_reader.hip: pv_stride, out_bytes; as k_stats_unpack).
+__device__ __forceinline__ uint32_t expand_field_wide(const uint8_t *__restrict__ pix, uint64_t pix_bytes, uint64_t rank, uint32_t d)
+{
+    if (d == 32 && 4 * rank + 4 <= pix_bytes) return reinterpret_cast<const uint32_t *>(pix)[rank];
+    if (d < 32 && rank * d + d <= 8 * pix_bytes) {
+        const uint64_t bit = rank * d;
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(pix) + (bit >> 5);
+        return (uint32_t)((((uint64_t)p[0] | ((uint64_t)p[1] << 32)) >> (bit & 31u)) & ((1u << d) - 1u));
+    }
+    return (uint32_t)read_field(pix, pix_bytes, rank, d);
+}
+// any 1 <= d <= 32
+__device__ __forceinline__ uint32_t expand_field32(const uint8_t *__restrict__ pix, uint64_t pix_bytes, uint64_t rank, uint32_t d)
+{
+    return d <= 16 ? expand_field16(pix, pix_bytes, rank, d, (1u << d) - 1u) : expand_field_wide(pix, pix_bytes, rank, d);
+}
+
 void launch_expand_count(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, uint32_t *blk_cnt, uint32_t *blk_off,
                          uint64_t *nnz_dev, hipStream_t s);
 void launch_expand_emit(const uint8_t *bitmap_pad8, uint64_t nb8, uint64_t N, uint32_t nx, const uint32_t *blk_off,

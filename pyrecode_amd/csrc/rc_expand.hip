@@ -179,16 +179,9 @@ __global__ __launch_bounds__(WG) void k_expand_emit_b(const uint8_t *__restrict_
             while (col >= nx) { col -= nx; ++row; }
             const uint64_t rank = wg_rank + r;
             uint64_t val;
-            // Fields of 17..32 bits that lie inside the stream, from dwords (value streams are 16-byte aligned): d = 32 is the dword itself;
-            // a narrower field lies inside the two dwords at its bit position.  Its last bit is below 8 * pix_bytes, so the first dword
-            // starts below pix_bytes and the second one ends before pix_bytes + 8 - inside the frame's slot, which is the longest stream
-            // rounded up to 16 bytes plus 16 more, zeroed behind the stream (rc_reader.hip: pv_stride, out_bytes; as k_stats_unpack).
-            if (WIDE && level == 1 && d == 32 && 4 * rank + 4 <= pix_bytes) val = reinterpret_cast<const uint32_t *>(pix)[rank];
-            else if (WIDE && level == 1 && d > 16 && d < 32 && rank * d + d <= 8 * pix_bytes) {
-                const uint64_t bit = rank * d;
-                const uint32_t *p = reinterpret_cast<const uint32_t *>(pix) + (bit >> 5);
-                val = (((uint64_t)p[0] | ((uint64_t)p[1] << 32)) >> (bit & 31u)) & ((1u << d) - 1u);
-            } else
+            // fields of 17..32 bits from dwords (rc_expand.h: expand_field_wide)
+            if (WIDE && level == 1 && d > 16 && d <= 32) val = expand_field_wide(pix, pix_bytes, rank, d);
+            else
                 val = level != 1 ? 1ull : ((d == 16 && 2 * rank + 2 <= pix_bytes) ? (uint64_t)reinterpret_cast<const uint16_t *>(pix)[rank]   // (value streams are 16-byte aligned)
                                                                                     : read_field(pix, pix_bytes, rank, d));
             if (staged) {

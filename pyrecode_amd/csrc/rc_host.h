@@ -302,6 +302,7 @@ struct ReadRes {
     uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be
     uint32_t late_value_bytes = 0;                         // good (device inflate), its COO value width (0: none) and whether it is COO at all
     bool late_coo = false;
+    uint64_t late_dense = 0;                               // rc_expand_frames_dense_submit: bytes of the staged cells (0: not a dense batch), always copied late
     bool late_events = false;                              // rc_count_frames_submit: the four event arrays, always copied late (a refused batch writes nothing)
     std::vector<uint32_t> pv_bytes;
 };

@@ -4,6 +4,7 @@
 // Replaces ReCoDeReader._get_frame_sparse (pyrecode/recode_reader.py:379-471) for n frames at once.
 #include "rc_host.h"
 #include "rc_count.h"
+#include "rc_dense.h"
 #include "rc_inflate.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
@@ -140,14 +141,18 @@ static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, ui
 // EVENT prefix).  A level-2 file's statistics stream is stepped over, as for the sum.
 // cnt and sum together (rc_sum_add_counted / _submit): no event array either - the counting kernels end in k_cnt_place, which adds one
 // count per event to the handle's cells, a grid cnt->upsample times finer than the frame (nx, ny are the FRAME's; triplets NULL, cap 0).
+// dense (rc_expand_frames_dense / _submit): no entries either - behind the count, k_expand_dense_b (rc_dense.hip) writes a region of every frame as
+// an array of cells (`triplets` = the output, cap = its cells, at least n * w * h of cell_bytes bytes: the entry points have checked it).
 struct CountReq { uint32_t method, area_threshold, upsample; };
+struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
-                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr)
+                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr,
+                      const DenseReq *dense = nullptr)
 {
     const uint64_t esz = cnt ? 20 : l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
-    if (!data || !sizes || (!nnz_prefix && !submit_only) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
+    if (!data || !sizes || (!nnz_prefix && !submit_only && !dense) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
         return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
     if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
     if (level == 1 && (bit_depth == 0 || bit_depth > 64)) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
@@ -519,7 +524,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         if (submit_only) {
             HIP_TRY(hipEventRecord(u.done, s));
             u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
-            u.late_events = true; u.late_coo = false; u.late_value_bytes = 0;
+            u.late_events = true; u.late_coo = false; u.late_value_bytes = 0; u.late_dense = 0;
             u.pending = true;
             u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
             u.pv_bytes.assign(pv_bytes, pv_bytes + n);
@@ -536,6 +541,49 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         if (total > cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_count_frames: events holds fewer entries than the frames have events");
         if (staged && total) {
             HIP_TRY(copy_events(reinterpret_cast<uint8_t *>(triplets), u.d_triplets.p, cap, total, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        return RC_OK;
+    }
+    if (dense) {
+        // The cells for device memory are written where the caller wants them; for host memory they are staged and copied once the batch is
+        // known to be good (a submitted batch: by rc_expand_frames_wait) - a refused batch writes nothing.
+        const uint64_t out_bytes_dense = (uint64_t)n * dense->region.w * dense->region.h * dense->cell_bytes;
+        void *cells = triplets;
+        const bool staged = !is_device_ptr(triplets);
+        if (staged) {
+            hipPointerAttribute_t a;
+            if (submit_only && (hipPointerGetAttributes(&a, triplets) != hipSuccess || a.type != hipMemoryTypeHost)) {
+                (void)hipGetLastError();
+                return bail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: out must be device or page-locked host memory");
+            }
+            if ((r = u.d_triplets.ensure(U.dmem, out_bytes_dense + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+            cells = u.d_triplets.p;
+        }
+        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
+        launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, dense->region, dense->cell_bytes,
+                                  cells, d_err, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
+        if (submit_only) {
+            HIP_TRY(hipEventRecord(u.done, s));
+            u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
+            u.late_dense = out_bytes_dense;
+            u.late_events = false; u.late_coo = false; u.late_value_bytes = 0;
+            u.pending = true;
+            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = ~0ull;
+            u.pv_bytes.assign(pv_bytes, pv_bytes + n);
+            return RC_OK;
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        const int err = (int)(uint32_t)h_res[n + 1];
+        if (nnz_prefix) memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
+        if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
+        if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
+        if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
+        if (staged) {
+            HIP_TRY(hipMemcpyAsync(triplets, cells, out_bytes_dense, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
         return RC_OK;
@@ -575,6 +623,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         u.late_value_bytes = l2out ? 0 : coo;
         u.late_coo = coo != 0;
         u.late_events = false;
+        u.late_dense = 0;
         u.pending = true;
         u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
         u.pv_bytes.assign(pv_bytes, pv_bytes + n);
@@ -711,7 +760,11 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
     if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
     if (nnz_prefix[n] > u.cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
     if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
-    if (u.late_dst && nnz_prefix[n]) {
+    if (u.late_dst && u.late_dense) {
+        // a dense batch's cells, staged in d_triplets: all of them, whatever the set pixels number
+        HIP_TRY(hipMemcpyAsync(u.late_dst, u.d_triplets.p, u.late_dense, hipMemcpyDeviceToHost, u.stream));
+        HIP_TRY(hipStreamSynchronize(u.stream));
+    } else if (u.late_dst && nnz_prefix[n]) {
         // the output staged in d_triplets keeps the caller's layout (triplet rows, or the COO arrays cap entries apart)
         const uint64_t total = nnz_prefix[n];
         const uint8_t *src = u.d_triplets.p;
@@ -726,6 +779,47 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
         HIP_TRY(hipStreamSynchronize(u.stream));
     }
     return RC_OK;
+}
+
+// ---- dense frame batches: a region of every frame as an array of cells (rc_dense.hip) -------------------------------------------------
+// what both forms check before the device is asked for: from the arguments alone
+static int dense_admit(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t n, const DenseReq &q, const void *out, uint64_t out_cells)
+{
+    const rc::DenseRegion &g = q.region;
+    if (!out || n == 0 || nx == 0 || ny == 0) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: NULL / zero argument");
+    if (nx > 65535u || ny > 65535u) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: nx, ny in 1..65535");
+    if (g.step_x == 0 || g.step_y == 0 || g.w == 0 || g.h == 0) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: w, h, step_x and step_y must be positive");
+    if ((uint64_t)g.x0 + (uint64_t)(g.w - 1) * g.step_x >= nx || (uint64_t)g.y0 + (uint64_t)(g.h - 1) * g.step_y >= ny)
+        return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: the region leaves the frame");
+    if (q.cell_bytes != 1 && q.cell_bytes != 2 && q.cell_bytes != 4) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: cell_bytes 1, 2 or 4");
+    if (level == 1 && bit_depth > 32) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames_dense: bit_depth above 32 (the cells are uint32 at most)");
+    if (level == 1 && bit_depth > 8 * q.cell_bytes) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: a cell of cell_bytes bytes does not hold bit_depth bits");
+    if ((uintptr_t)out % q.cell_bytes) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense: out must be aligned to its cells");
+    if (out_cells < (uint64_t)n * g.w * g.h) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_dense: out holds fewer than n * w * h cells");
+    return RC_OK;
+}
+
+RC_EXPORT int rc_expand_frames_dense(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                     const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t step_x, uint32_t step_y,
+                                     uint32_t cell_bytes, void *out, uint64_t out_cells, uint64_t *nnz_prefix)
+{
+    const DenseReq req{{x0, y0, w, h, step_x, step_y}, cell_bytes};
+    const int r = dense_admit(nx, ny, bit_depth, level, n, req, out, out_cells);
+    if (r != RC_OK) return r;
+    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(out), out_cells, 0, false,
+                      nullptr, 0, nullptr, nullptr, &req);
+}
+
+RC_EXPORT int rc_expand_frames_dense_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                            const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                            uint32_t step_x, uint32_t step_y, uint32_t cell_bytes, void *out, uint64_t out_cells)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: slot 0 or 1");
+    const DenseReq req{{x0, y0, w, h, step_x, step_y}, cell_bytes};
+    const int r = dense_admit(nx, ny, bit_depth, level, n, req, out, out_cells);
+    if (r != RC_OK) return r;
+    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(out), out_cells, 0, false, nullptr, 0,
+                      nullptr, nullptr, &req);
 }
 
 // ---- electron counting: one event per connected component of a frame's set pixels (rc_count.hip) -------------------------------------

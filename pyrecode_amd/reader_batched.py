@@ -75,6 +75,34 @@ def count_method(method):
     return COUNT_METHODS[method]
 
 
+def plan_sub_volume(key, shape):
+    """What numpy's stack[key] selects, per axis, for a key of slices and integers (one per axis of `shape`), restated for a reader that
+    walks forwards: a list of (start, count, step, flip, drop) - the `count` indices start, start + step, ... with step > 0, ascending;
+    flip: numpy delivers them in the opposite order (a negative step); drop: the axis was indexed with an integer and is not in the
+    result.  stack[key] == take(those indices)[::-1 where flip] with the dropped axes indexed at 0.  None bounds, negative indices and
+    bounds beyond the axis follow numpy (slice.indices); an integer out of range raises IndexError."""
+    import operator
+    if not isinstance(key, tuple) or len(key) != len(shape):
+        raise IndexError('one slice or integer per axis')
+    plan = []
+    for k, size in zip(key, shape):
+        size = int(size)
+        if isinstance(k, slice):
+            r = range(*k.indices(size))
+            if len(r) == 0:
+                plan.append((0, 0, 1, False, False))
+            elif r.step > 0:
+                plan.append((r.start, len(r), r.step, False, False))
+            else:
+                plan.append((r[-1], len(r), -r.step, True, False))
+        else:
+            i = operator.index(k)
+            if not -size <= i < size:
+                raise IndexError('index %d is out of bounds for an axis of size %d' % (i, size))
+            plan.append((i % size, 1, 1, False, True))
+    return plan
+
+
 def _event_views(buf, cap, total):
     """(rows int32, cols int32, area uint32, weight uint64): the first `total` events of rc_count_frames' output of capacity `cap`"""
     return (buf[8 * cap:12 * cap].view(np.int32)[:total], buf[12 * cap:16 * cap].view(np.int32)[:total],
@@ -371,32 +399,35 @@ class BatchedAccess:
     def _route_for(self, family, device_blosc=False, device_zlib=False):
         return _route(self._header, self._foreign_file, device_blosc, device_zlib, family)
 
-    def _batch_sizes(self, a, k):
-        """(sizes uint32[k][3] as rc_expand_frames & co. take them, bytes of the k frames' data) of frames a .. a+k-1"""
+    def _batch_sizes(self, a, k, frames=None):
+        """(sizes uint32[k][3] as rc_expand_frames & co. take them, bytes of the k frames' data) of frames a .. a+k-1 - or of the k frames
+        whose indices `frames` lists"""
         level = int(self._header['reduction_level'])
         sizes = np.zeros((k, 3), np.uint32)
-        for j in range(k):
-            md = self._frame_metadata[a + j]
+        ids = range(a, a + k) if frames is None else [int(z) for z in frames]
+        for j, z in enumerate(ids):
+            md = self._frame_metadata[z]
             sz_map, sz_val = self._stream_sizes(md)
             sizes[j, 0] = sz_map
             if level == 1:
                 sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_pixvals'])
             elif level == 2:
                 sizes[j, 1], sizes[j, 2] = sz_val, int(md['bytes_in_packed_summary_stats'])     # (the summed views' device call steps over them)
-        return sizes, int(self._seek_table[a:a + k, 0].sum())
+        return sizes, int(self._seek_table[list(ids), 0].sum())
 
-    def _frames_one_by_one(self, z0, n):
-        """_get_frame_sparse's result for each of frames z0 .. z0+n-1: the frame-at-a-time path under the batched calls (the stock decoder
-        is the judge, and names the frame that is to blame).  Afterwards a part file's position - get_next_frame's cursor - is where it
-        was, and a merged file's frame counter is behind the batch."""
+    def _frames_one_by_one(self, z0, n, frames=None):
+        """_get_frame_sparse's result for each of frames z0 .. z0+n-1 (or of those `frames` lists, ascending): the frame-at-a-time path
+        under the batched calls (the stock decoder is the judge, and names the frame that is to blame).  Afterwards a part file's
+        position - get_next_frame's cursor - is where it was, and a merged file's frame counter is behind the batch."""
         keep = self._fp.tell()
-        for i in range(n):
-            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0)
-            yield self._get_frame_sparse(self._frame_metadata[z0 + i])
+        ids = range(z0, z0 + n) if frames is None else [int(z) for z in frames]
+        for z in ids:
+            self._fp.seek(self._frame_data_start_position + int(self._seek_table[z, 1]), 0)
+            yield self._get_frame_sparse(self._frame_metadata[z])
         if self._is_intermediate:
             self._fp.seek(keep, 0)
         else:
-            self._note_batch_end(z0 + n)
+            self._note_batch_end(ids[-1] + 1 if len(ids) else z0)
 
     def _expand_now(self, mode, scheme, data, sizes, n, dst):
         """One synchronous device call for n frames (rc_expand_frames & co. into `dst`, a _BatchOut), their streams back to back in `data`
@@ -967,16 +998,16 @@ class BatchedAccess:
             self._user_iters -= 1
 
     # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
-    def _stored_pieces_per_frame(self, a, k):
-        """frames a .. a+k-1 through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge, and names the frame that
-        is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the file's own bit depth:
+    def _stored_pieces_per_frame(self, a, k, frames=None):
+        """frames a .. a+k-1 (or those `frames` lists) through the frame-at-a-time reader (_get_frame_sparse: the stock decoder is the judge,
+        and names the frame that is to blame), restated as stored frames - the binary map, and at level 1 the values packed again at the file's own bit depth:
         (geometry of a mode-0 batch, its bytes, its sizes).  A dense mask, a sort and a pack per frame on the host: the slow route's price."""
         h = self._header
         nx, ny, level, d = int(h['nx']), int(h['ny']), int(h['reduction_level']), int(h['target_bit_depth'])
         nb = (nx * ny + 7) // 8
         sizes, parts = np.zeros((k, 3), np.uint32), []
         shifts = np.arange(d, dtype=np.uint32)
-        for i, m in enumerate(self._frames_one_by_one(a, k)):
+        for i, m in enumerate(self._frames_one_by_one(a, k, frames)):
             m = m[0] if isinstance(m, tuple) else m
             dense, vals = np.zeros(ny * nx, bool), np.zeros(0, np.uint32)
             if m is not None and m.nnz:
@@ -1286,6 +1317,218 @@ class BatchedAccess:
         self._sum_check_file()
         self._count_check_file()
         yield from self._iter_sums(frames_per_view, z0, n, batch, _CountedAdder(method, area_threshold, upsample))
+
+    # ---- dense frame batches (rc_expand_frames_dense): a region of every frame as an array, written on the device --------------------------
+    _DENSE_BYTES = 256 << 20      # the dense output of a batch the streaming calls size themselves (8 frames of 4096 x 4096 uint16)
+
+    def _dense_check_file(self):
+        """the cell type of this file's dense frames: its numpy dtype, which must be an unsigned integer of 1, 2 or 4 bytes"""
+        h = self._header
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        dt = np.dtype(self._numpy_dtype)
+        if level not in (1, 2, 3):
+            raise NotImplementedError('dense frames: reduction level %d' % level)
+        if dt.kind != 'u' or dt.itemsize not in (1, 2, 4):
+            raise NotImplementedError('dense frames: target dtype %s (the cells are unsigned integers of 1, 2 or 4 bytes)' % dt)
+        if level == 1 and (d > 32 or d > 8 * dt.itemsize):
+            raise NotImplementedError('dense frames: files of more than 32 bits, or of more bits than their dtype holds (target_bit_depth %d, %s)' % (d, dt))
+        return dt
+
+    def _dense_region(self, roi):
+        """roi = None (the whole frame) or (slice_y, slice_x) -> (x0, y0, w, h, step_x, step_y) as rc_expand_frames_dense takes it; the
+        slices follow numpy's rules, and must select something, walking forwards"""
+        ny, nx = int(self._header['ny']), int(self._header['nx'])
+        if roi is None:
+            return 0, 0, nx, ny, 1, 1
+        if not (isinstance(roi, tuple) and len(roi) == 2 and all(isinstance(s, slice) for s in roi)):
+            raise ValueError('roi must be (slice_y, slice_x)')
+        (y0, h, sy, fy, _), (x0, w, sx, fx, _) = plan_sub_volume(roi, (ny, nx))
+        if fy or fx or h == 0 or w == 0:
+            raise ValueError('roi: an empty selection or a negative step (get_sub_volume takes those)')
+        return x0, y0, w, h, sx, sy
+
+    def _dense_batch(self, region, dt):
+        """the frames of the largest batch whose dense output stays within _DENSE_BYTES - and at least one"""
+        return max(1, self._DENSE_BYTES // (region[2] * region[3] * dt.itemsize))
+
+    def _read_frames_into(self, blob, frames):
+        """the data of the frames `frames` lists (ascending) -> blob, back to back: a run of consecutive frames as _read_batch_into reads it,
+        anything else gathered piece by piece, the way _read_batch_into does for part files"""
+        k, a = len(frames), int(frames[0])
+        if int(frames[-1]) - a + 1 == k:
+            return self._read_batch_into(blob, a, k)
+        fd, at = self._fp.fileno(), 0
+        for z in frames:
+            size, pos, got = int(self._seek_table[int(z), 0]), self._frame_data_start_position + int(self._seek_table[int(z), 1]), 0
+            while got < size:
+                m = os.preadv(fd, [memoryview(blob[at + got:at + size])], pos + got)
+                if m <= 0:
+                    raise ValueError('file shorter than its seek table says')
+                got += m
+            at += size
+        if not self._is_intermediate:
+            self._fp.seek(pos + size, 0)      # (where reading a run leaves a merged file: behind the last frame read)
+
+    def _dense_call(self, geom, data, sizes, k, region, dt, dst, cells, slot=None):
+        """rc_expand_frames_dense (slot None) or _submit, status returned; dst: an address, host or device"""
+        L = _lib.lib()
+        args = tuple(geom) + (_lib.ptr(data), _lib.ptr(sizes), k) + tuple(region) + (dt.itemsize, dst, cells)
+        return L.rc_expand_frames_dense(*args, None) if slot is None else L.rc_expand_frames_dense_submit(slot, *args)
+
+    def _dense_fall_back(self, frames, blob, sizes, region, dt, dst, cells, offered):
+        """A batch the device decoders refused (offered) or were never offered: the stock decoders on the thread pool, then the stored pieces
+        through the same device call; what is left goes through the frame-at-a-time reader, restated as stored frames (_sum_stream's routes)."""
+        h = self._header
+        k = len(frames)
+        got = self._host_decode_batch(blob, sizes, k, 2) if _stock_decoded(h) else None
+        if got is not None:
+            geom0 = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), 0, int(h['compression_scheme']))
+            _lib.check(self._dense_call(geom0, got[0], got[1], k, region, dt, dst, cells), 'rc_expand_frames_dense')
+            self.last_batch_path = 'host-decode + device-expand'
+            if offered:
+                self._foreign_file = True        # not offered to the device decoders again
+            return
+        geom0, pieces, sizes0 = self._stored_pieces_per_frame(int(frames[0]), k, frames)
+        _lib.check(self._dense_call(geom0, pieces, sizes0, k, region, dt, dst, cells), 'rc_expand_frames_dense')
+        self.last_batch_path = 'per-frame'
+
+    def _dense_geom(self, dev):
+        h = self._header
+        return (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), int(h['rc_operation_mode']), dev)
+
+    def _dense_stream(self, groups, region, dt):
+        """The engine of iter_frames_dense and get_sub_volume: groups = [frame indices, ascending] - one batch each - through
+        rc_expand_frames_dense_submit / rc_expand_frames_wait on the two slots, so the next batch is read from the file and queued before this
+        one is waited for.  Yields (index of the group, array[k, h, w]): a VIEW of the slot's page-locked output, valid until the generator
+        advances.  Routes and fall-backs are _sum_stream's."""
+        w, hh, isz = region[2], region[3], dt.itemsize
+        # (a job's first frame is chosen so that first + count is behind its last frame: where _two_slots leaves a merged file's counter)
+        jobs = [_Job(int(g[-1]) + 1 - len(g), len(g), SimpleNamespace(frames=g, index=i)) for i, g in enumerate(groups)]
+        bufs = self._bufs.stream
+
+        def start(job):
+            """read the job's bytes into its slot's page-locked blob and offer them to the device"""
+            p, k = job.payload, job.count
+            p.sizes, nbytes = self._batch_sizes(0, k, p.frames)
+            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
+            p.blob = bufs[job.slot].array[:nbytes]
+            self._read_frames_into(p.blob, p.frames)
+            p.cells = k * w * hh
+            bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], p.cells * isz)
+            p.dev, p.status = self._route_for('sum')[1], None
+            if p.dev is None:
+                return
+            call = (self._dense_geom(p.dev), p.blob, p.sizes, k, region, dt, bufs[2 + job.slot]._p, p.cells)
+            p.status = self._dense_call(*call, slot=job.slot)
+            if _slot_taken(p.status):
+                p.status = self._dense_call(*call)       # another reader's iterator holds the slot: the synchronous call has resources of its own
+                return
+            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(p.status, 'rc_expand_frames_dense_submit')
+            job.queued = p.status == _lib.RC_OK
+
+        def finish(job):
+            p, k = job.payload, job.count
+            st = p.status
+            if job.queued:
+                st, _ = _wait(job)
+            dst = bufs[2 + job.slot]
+            if p.dev is not None and st == _lib.RC_OK:
+                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_expand_frames_wait')
+            else:
+                self._dense_fall_back(p.frames, p.blob, p.sizes, region, dt, dst._p, p.cells, p.dev is not None)
+            return p.index, dst.array[:p.cells * isz].view(dt).reshape(k, hh, w)
+
+        self._ra = None
+        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
+        self._user_iters += 1
+        try:
+            yield from self._two_slots(jobs, start, finish)
+        finally:
+            self._user_iters -= 1
+
+    def get_frames_dense(self, z0, n, roi=None, out=None):
+        """Frames z0 .. z0+n-1 of a merged file (records of a part file) as an array[n, h, w] of the file's dtype in ONE device call
+        (rc_expand_frames_dense): what np.stack of get_frame(z)['data'].toarray() gives - a memset and a scatter per frame on the host
+        (utils/viewer.py:65-68) - written by the device, zeros included; nothing per set pixel crosses the link.
+        roi: None (whole frames) or (slice_y, slice_x), numpy's rules, positive steps: only that region is written and copied.
+        out: None (an array of its own), a C-contiguous numpy array of shape (n, h, w) and the file's dtype, or an object with data_ptr(),
+        shape, element_size() and is_contiguous() - a torch tensor on the GPU -, which the device writes in place; `out` is returned.
+        For WHOLE frames wanted in host memory the link carries 2 bytes per pixel here against 10 per set pixel on the COO route
+        (get_frames_coo): below one set pixel in five that route moves less - this one saves the host's memset and scatter
+        (DESIGN.md 7f has the rates measured side by side).
+        Routes (last_batch_path) and fall-backs as for sum_frames.  A dtype that is not an unsigned integer of 1, 2 or 4 bytes, and files
+        of more than 32 bits, are not taken (NotImplementedError)."""
+        dt = self._dense_check_file()
+        n = self._frame_range(z0, n)
+        region = self._dense_region(roi)
+        shape = (n, region[3], region[2])
+        if out is None:
+            out = np.empty(shape, dt)
+        if isinstance(out, np.ndarray):
+            if out.dtype != dt or out.shape != shape or not out.flags['C_CONTIGUOUS']:
+                raise ValueError('get_frames_dense: out must be a C-contiguous %s array of shape %s' % (dt, shape))
+            dst = _lib.ptr(out)
+        else:
+            if tuple(out.shape) != shape or out.element_size() != dt.itemsize or not out.is_contiguous():
+                raise ValueError('get_frames_dense: out must be contiguous, of shape %s and %d bytes an element' % (shape, dt.itemsize))
+            dst = int(out.data_ptr())
+        frames = np.arange(z0, z0 + n)
+        cells = n * shape[1] * shape[2]
+        sizes, total = self._batch_sizes(z0, n)
+        self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total + 64)
+        blob = self._bufs.pin_blob.array[:total]
+        self._read_batch_into(blob, z0, n)
+        dev = self._route_for('sum')[1]
+        st = None
+        if dev is not None:
+            st = self._dense_call(self._dense_geom(dev), blob, sizes, n, region, dt, dst, cells)
+            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_expand_frames_dense')
+        if st == _lib.RC_OK:
+            self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+        else:
+            self._dense_fall_back(frames, blob, sizes, region, dt, dst, cells, dev is not None)
+        self._note_batch_end(z0 + n)
+        return out
+
+    def iter_frames_dense(self, z0=0, n=None, batch=None, roi=None):
+        """get_frames_dense for a whole file, streamed: yields (first frame index, array[k, h, w]) per batch of up to `batch` frames, two
+        batches in flight (rc_expand_frames_dense_submit / rc_expand_frames_wait).  The array is a VIEW of page-locked memory, valid until
+        the generator is advanced (copy it to keep it), like the batches of iter_frames_triplets.  batch=None: the largest batch whose dense
+        output is at most 256 MiB, and at least one frame - 8 frames of 4096 x 4096 uint16."""
+        dt = self._dense_check_file()
+        region = self._dense_region(roi)
+        batch = self._dense_batch(region, dt) if batch is None else batch
+        n = self._frame_range(z0, n, batch)
+        groups = [np.arange(a, min(a + batch, z0 + n)) for a in range(z0, z0 + n, batch)]
+        for i, arr in self._dense_stream(groups, region, dt):
+            yield int(groups[i][0]), arr
+
+    def get_sub_volume(self, slice_z, slice_y, slice_x):
+        """What numpy's stack[slice_z, slice_y, slice_x] returns - values, shape and dtype -, stack[z] being the toarray() of frame z's COO
+        matrix as get_frame returns it (records of a part file: record z): the method the reference's source readers implement
+        (em_reader.py:111-116) and its ReCoDeReader leaves a stub (recode_reader.py:185-186).  Slices and integers, None bounds, negative
+        indices and negative steps follow numpy's rules (plan_sub_volume); as in the reference's readers a slice_z.stop beyond nz raises
+        IndexError.  Only the selected frames are read - a z step other than 1 gathers their blobs piece by piece -, only the selected
+        region of each is written by the device (rc_expand_frames_dense) and copied; batches are sized as in iter_frames_dense."""
+        dt = self._dense_check_file()
+        shape = (self._batch_frames(), int(self._header['ny']), int(self._header['nx']))
+        if isinstance(slice_z, slice) and slice_z.stop is not None and slice_z.stop > shape[0]:
+            raise IndexError('slice_z.stop (%d) is beyond the number of frames (%d)' % (slice_z.stop, shape[0]))
+        (z0, cz, sz, fz, dz), (y0, cy, sy, fy, dy), (x0, cx, sx, fx, dx) = plan_sub_volume((slice_z, slice_y, slice_x), shape)
+        vol = np.empty((cz, cy, cx), dt)
+        if vol.size:
+            region = (x0, y0, cx, cy, sx, sy)
+            frames = z0 + sz * np.arange(cz)
+            batch = self._dense_batch(region, dt)
+            groups = [frames[a:a + batch] for a in range(0, cz, batch)]
+            for i, arr in self._dense_stream(groups, region, dt):
+                vol[i * batch:i * batch + arr.shape[0]] = arr
+        vol = vol[::-1 if fz else 1, ::-1 if fy else 1, ::-1 if fx else 1]
+        return vol[0 if dz else slice(None), 0 if dy else slice(None), 0 if dx else slice(None)]
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of

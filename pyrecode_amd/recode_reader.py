@@ -139,8 +139,7 @@ class ReCoDeReader(BatchedAccess):
     def get_dtype(self):
         return self._header['target_dtype']
 
-    def get_sub_volume(self, slice_z, slice_y, slice_x):
-        raise NotImplementedError
+    # (get_sub_volume(slice_z, slice_y, slice_x): reader_batched.BatchedAccess - dense frames written on the device)
 
     @property
     def sz_frame_metadata(self):

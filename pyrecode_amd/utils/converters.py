@@ -1,7 +1,9 @@
 """Converters between reduction levels (reference: pyrecode/utils/converters.py).  l1_to_l4_converter counts electrons - every 8-connected
 puddle of a level-1 frame's set pixels becomes one event at its centroid - with the labelling and the per-component sums on the device
 (rc_count_frames); the reference labels with scipy and sums in numba, a frame at a time on the host.
-recalibrate_l1 is not offered: it adds a calibration difference to EVERY pixel, unset ones included, so it works on dense frames."""
+recalibrate_l1 is not offered: it adds a calibration difference to EVERY pixel, unset ones included, so it works on dense frames -
+which the reader can deliver now (ReCoDeReader.get_frames_dense), but re-thresholding and re-encoding them is a
+feature of its own."""
 import copy
 from datetime import datetime
 
