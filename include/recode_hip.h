@@ -473,6 +473,49 @@ int rc_expand_frames_dense_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint3
                                   uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0,
                                   uint32_t w, uint32_t h, uint32_t step_x, uint32_t step_y, uint32_t cell_bytes, void *out,
                                   uint64_t out_cells);
+/* ---- frame traces: a few exact integers per frame, reduced on the device -----------------------------------------
+ * What a time-resolved or scanned acquisition is first looked at with, and what the reference computes on the host: the dose rate its
+ * l1_to_l4_converter prints per frame (pyrecode/utils/converters.py:108-111: the frame's set pixels over its area), and everything
+ * else per frame - total intensity, centre of mass, the sum under a mask - by a caller's loop around ReCoDeReader.get_frame
+ * (pyrecode/recode_reader.py:379-471) and numpy.  A batch is decoded and counted exactly as by rc_expand_frames, and in place of the
+ * emit kernel the kernels of rc_trace.hip write, for frame f and its set pixels (row, col) of stored value v (level 1: the
+ * bit_depth-bit field; levels 2 and 3: 1, a level-2 frame's statistics stream is stepped over),
+ *   out[f][0] = the number of set pixels      out[f][2] = sum v * row
+ *   out[f][1] = sum v                          out[f][3] = sum v * col        out[f][4 + m] = sum v * W_m[row][col],  m < k
+ * int64[n][4 + k], row-major, exact.  A frame without a set pixel gives a row of zeros; EVERY cell is written exactly once: out needs
+ * no memset.
+ *   rc_trace_create   nx, ny: the frames' shape, 1..65535; k <= 16 planes of int32[ny][nx] in C order, host or device memory (NULL
+ *                     when k == 0), copied into the handle in the layout its kernel reads (pixel-major) - the caller's may go away.
+ *                     Device planes are read on the library's own stream, which is NOT ordered behind the caller's: they lie on the
+ *                     handle's GPU and whatever writes them has finished (hipStreamSynchronize / hipDeviceSynchronize) before the call.
+ *                     NULL with *status set on failure: RC_ERR_BAD_ARG (k > 16, a shape of 0 or above 65535, planes NULL with k > 0),
+ *                     RC_ERR_DEVICE without a GPU.  The handle lives on the caller's current GPU (RC_DEVICE); its weights are read-only
+ *                     after create, so batches on both slots may use one handle.  One thread uses a handle at a time.
+ *   rc_trace_columns       4 + k
+ *   rc_trace_weight_bound  max |W_m| as uint32 (INT32_MIN counts as 2^31); 0 for m >= k
+ * No silent wrap: with a = the largest weight of any column (1, ny - 1, nx - 1, the planes' bounds), vmax = 2^bit_depth - 1 at level 1
+ * and 1 otherwise, and P_f = the set pixels frame f can hold (nx * ny; at level 1 no more than floor(8 * sizes[3 f + 2] / bit_depth)),
+ * a batch with a * vmax * P_f > 2^63 - 1 for any frame is refused with RC_ERR_OUT_TOO_SMALL before any device work.
+ *   out           int64-aligned, device or host memory: device memory is written by the kernel itself, host memory is staged on the
+ *                 device and copied once the batch is known to be good
+ *   out_cells     cells out has room for; fewer than n * (4 + k) is RC_ERR_OUT_TOO_SMALL
+ *   nnz_prefix    uint64[n+1] out (host), may be NULL: what rc_expand_frames gives
+ * Level 1 with bit_depth > 16 is RC_ERR_UNSUPPORTED, as for the summed views; stored frames (op_mode 0) whose binary map is not
+ * ceil(nx * ny / 8) bytes, and a handle of another device, are RC_ERR_BAD_ARG.  Everything known from the arguments alone is reported
+ * before any device work, in both forms.  op_mode / scheme, data (host or device), sizes and the device decoders' subset as for
+ * rc_expand_frames.  A batch that is refused - the no-wrap rule, a decoder's RC_ERR_CORRUPT or RC_ERR_UNSUPPORTED, a level-1 value stream
+ * shorter than its set pixels need (RC_ERR_CORRUPT) - writes NOTHING to out.
+ * rc_trace_frames_submit queues the batch on slot 0 or 1 (out: device memory, or page-locked host memory, which gets ONE asynchronous
+ * copy after the verdict; anything else is RC_ERR_BAD_ARG); rc_expand_frames_wait(slot, nnz_prefix) gives its verdict and the prefix. */
+typedef struct rc_trace rc_trace;
+rc_trace *rc_trace_create(uint32_t nx, uint32_t ny, uint32_t k, const int32_t *planes, int *status);
+int rc_trace_destroy(rc_trace *t);
+uint32_t rc_trace_columns(const rc_trace *t);
+uint32_t rc_trace_weight_bound(const rc_trace *t, uint32_t m);
+int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                    const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix);
+int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                           const uint8_t *data, const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

@@ -87,6 +87,12 @@ SIGNATURES = {
     "rc_sum_add_counted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 8 + [_u8p, _u32p] + [C.c_uint32] * 3),
     "rc_sum_fetch": (C.c_int, [C.c_void_p, _u32p, C.c_int]),
     "rc_sum_bound": (C.c_uint64, [C.c_void_p]),
+    "rc_trace_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
+    "rc_trace_destroy": (C.c_int, [C.c_void_p]),
+    "rc_trace_columns": (C.c_uint32, [C.c_void_p]),
+    "rc_trace_weight_bound": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "rc_trace_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
+    "rc_trace_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
     "rc_host_decode_streams": (C.c_int, [C.c_uint32, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32]),
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -298,6 +304,117 @@ class FrameSum:
         pin, self._pin = getattr(self, "_pin", None), None
         if pin is not None:
             pin.close()
+
+    __del__ = close
+
+
+class FrameTrace:
+    """Frame traces on the device: rc_trace_create .. rc_trace_destroy (include/recode_hip.h) - per frame of a batch of stored frames the
+    number of set pixels, the sum of their values, the sums weighted by row and by column, and the sums under k weight planes the handle
+    keeps a copy of: int64[n, 4 + k], exact.  weights: None (the four moments alone), or a numpy array / a torch tensor on the GPU of shape
+    (ny, nx) or (k, ny, nx), k <= 16, of an integer dtype whose values fit int32; anything else raises ValueError.  A tensor must be on the device the library runs on - the
+    current device, or RC_DEVICE -; its device is synchronised before the handle copies it, so a tensor that kernels of the caller are still
+    writing is read when they are done.  `geom` is the tuple the
+    batched readers pass to rc_expand_frames: (nx, ny, bit_depth, reduction_level, op_mode, scheme); its nx, ny must be the handle's.  One
+    thread uses a handle at a time; the weights are read-only, so batches on both slots may share it."""
+
+    MAX_PLANES = 16
+
+    def __init__(self, nx, ny, weights=None):
+        self.nx, self.ny = int(nx), int(ny)
+        planes, self.k = self._int32_planes(weights)       # (`planes` is kept alive until rc_trace_create has copied it)
+        st = C.c_int(0)
+        addr = None if planes is None else planes.data_ptr() if hasattr(planes, "data_ptr") else ptr(planes)
+        self._h = lib().rc_trace_create(self.nx, self.ny, self.k, addr, C.byref(st))
+        if not self._h:
+            check(st.value, "rc_trace_create")
+
+    def _int32_planes(self, weights):
+        """(the planes as C-contiguous int32[k, ny, nx] - numpy, or torch on the GPU -, k)"""
+        if weights is None:
+            return None, 0
+        on_gpu = hasattr(weights, "data_ptr") and not isinstance(weights, np.ndarray)
+        if on_gpu and not weights.is_cuda:
+            weights, on_gpu = weights.numpy(), False
+        if not on_gpu and not isinstance(weights, np.ndarray):
+            raise ValueError("FrameTrace: weights must be a numpy array or a torch tensor")
+        shape = tuple(int(v) for v in weights.shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3 or shape[1:] != (self.ny, self.nx) or not 1 <= shape[0] <= self.MAX_PLANES:
+            raise ValueError("FrameTrace: weights of shape %s - (ny, nx) or (k, ny, nx) with ny, nx = %d, %d and 1 <= k <= %d"
+                             % (tuple(weights.shape), self.ny, self.nx, self.MAX_PLANES))
+        lo, hi = -(1 << 31), (1 << 31) - 1
+        if on_gpu:
+            import torch
+            if weights.dtype.is_floating_point or weights.dtype.is_complex or weights.dtype == torch.bool:
+                raise ValueError("FrameTrace: weights of dtype %s (an integer dtype that fits int32)" % weights.dtype)
+            # The library runs on the caller's current device (RC_DEVICE overrides it) and on streams of its own: the tensor must live on that
+            # device, and everything queued on it - the kernels that produced the weights, the int32 copy below - must have finished before
+            # rc_trace_create reads it (the library's streams are not ordered behind torch's).
+            lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
+            if weights.device.index != lib_device:
+                raise ValueError("FrameTrace: weights on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (weights.device, lib_device))
+            if weights.dtype not in (torch.int8, torch.int16, torch.int32, torch.uint8) and weights.numel():
+                # (unsigned 32- and 64-bit values are judged through the signed view of the same width: what does not fit int32 is negative
+                # there, or above 2^31 - 1; torch reduces signed dtypes only)
+                signed = {getattr(torch, "uint16", None): torch.int32, getattr(torch, "uint32", None): torch.int32, getattr(torch, "uint64", None): torch.int64}
+                seen = weights if weights.dtype not in signed else weights.to(torch.int32) if weights.element_size() == 2 else weights.view(signed[weights.dtype])
+                floor = lo if weights.dtype not in signed else 0
+                if not (floor <= int(seen.min()) and int(seen.max()) <= hi):
+                    raise ValueError("FrameTrace: weights do not fit int32")
+            planes = weights.reshape(shape).to(torch.int32).contiguous()
+            torch.cuda.synchronize(weights.device)
+            return planes, shape[0]
+        if weights.dtype.kind not in "iu":
+            raise ValueError("FrameTrace: weights of dtype %s (an integer dtype that fits int32)" % weights.dtype)
+        if weights.size and not (lo <= int(weights.min()) and int(weights.max()) <= hi):
+            raise ValueError("FrameTrace: weights do not fit int32")
+        return np.ascontiguousarray(weights.reshape(shape), dtype=np.int32), shape[0]
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def columns(self):
+        return 4 + self.k
+
+    def weight_bounds(self):
+        """max |W_m| of every plane, as the handle holds them for the no-wrap rule (INT32_MIN counts as 2^31)"""
+        return [int(lib().rc_trace_weight_bound(self._h, m)) for m in range(self.k)]
+
+    def _codec(self, geom):
+        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("FrameTrace: frames of %d x %d traced with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
+        return tuple(int(v) for v in geom[2:6])
+
+    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
+        """rc_trace_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
+        return lib().rc_trace_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
+
+    def frames(self, geom, data, sizes, n):
+        """Trace n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them): (int64[n, 4 + k],
+        the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
+        out, prefix = np.empty((n, self.columns), np.int64), np.zeros(n + 1, np.uint64)
+        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_trace_frames")
+        return out, prefix
+
+    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
+        """rc_trace_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
+        returned, which gives the verdict and the prefix)"""
+        return lib().rc_trace_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.rc_trace_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     __del__ = close
 

@@ -6,6 +6,7 @@
 #include "rc_count.h"
 #include "rc_dense.h"
 #include "rc_inflate.h"
+#include "rc_trace.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
 namespace {
@@ -143,16 +144,20 @@ static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, ui
 // count per event to the handle's cells, a grid cnt->upsample times finer than the frame (nx, ny are the FRAME's; triplets NULL, cap 0).
 // dense (rc_expand_frames_dense / _submit): no entries either - behind the count, k_expand_dense_b (rc_dense.hip) writes a region of every frame as
 // an array of cells (`triplets` = the output, cap = its cells, at least n * w * h of cell_bytes bytes: the entry points have checked it).
+// trace (rc_trace_frames / _submit): no entries either - behind the count, the kernels of rc_trace.hip write 4 + k int64 sums per frame
+// (`triplets` = the output, cap = its cells, at least n * (4 + k): the entry points have checked it).  It shares the dense request's
+// handling of the output: written in place in device memory, staged and released after the verdict for host memory.
 struct CountReq { uint32_t method, area_threshold, upsample; };
 struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
+struct TraceReq { const int32_t *weights; uint32_t k; };   // (rc_trace_frames: the handle's interleaved weights and their planes)
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
                       bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr,
-                      const DenseReq *dense = nullptr)
+                      const DenseReq *dense = nullptr, const TraceReq *trace = nullptr)
 {
     const uint64_t esz = cnt ? 20 : l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
-    if (!data || !sizes || (!nnz_prefix && !submit_only && !dense) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
+    if (!data || !sizes || (!nnz_prefix && !submit_only && !dense && !trace) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
         return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
     if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
     if (level == 1 && (bit_depth == 0 || bit_depth > 64)) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
@@ -545,24 +550,31 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         }
         return RC_OK;
     }
-    if (dense) {
+    if (dense || trace) {
         // The cells for device memory are written where the caller wants them; for host memory they are staged and copied once the batch is
         // known to be good (a submitted batch: by rc_expand_frames_wait) - a refused batch writes nothing.
-        const uint64_t out_bytes_dense = (uint64_t)n * dense->region.w * dense->region.h * dense->cell_bytes;
+        const uint64_t out_bytes_dense = trace ? (uint64_t)n * (rc::TRACE_MOMENTS + trace->k) * 8 : (uint64_t)n * dense->region.w * dense->region.h * dense->cell_bytes;
         void *cells = triplets;
         const bool staged = !is_device_ptr(triplets);
         if (staged) {
             hipPointerAttribute_t a;
             if (submit_only && (hipPointerGetAttributes(&a, triplets) != hipSuccess || a.type != hipMemoryTypeHost)) {
                 (void)hipGetLastError();
-                return bail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: out must be device or page-locked host memory");
+                return bail(RC_ERR_BAD_ARG, trace ? "rc_trace_frames_submit: out must be device or page-locked host memory"
+                                                        : "rc_expand_frames_dense_submit: out must be device or page-locked host memory");
             }
             if ((r = u.d_triplets.ensure(U.dmem, out_bytes_dense + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
             cells = u.d_triplets.p;
         }
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
-        launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, dense->region, dense->cell_bytes,
-                                  cells, d_err, s);
+        if (trace) {
+            // the per-(frame, block) partial sums live in the counting workspace: no counting request shares a batch with a trace
+            if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, trace->k) + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+            launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, trace->weights, trace->k,
+                                      u.d_count.as<int64_t>(), static_cast<int64_t *>(cells), d_err, s);
+        } else
+            launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, dense->region, dense->cell_bytes,
+                                      cells, d_err, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
@@ -1014,4 +1026,132 @@ RC_EXPORT int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, u
     r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req);
     if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
     return r;
+}
+
+// ---- frame traces: per frame the set pixels, the sum, its first moments and the sums under the handle's weight planes (rc_trace.hip) ----
+// The handle owns the weights: an interleaved copy, int32[ny * nx][kp] (kp = k rounded up to a multiple of 4; the padding planes are zero),
+// read-only after create - batches on both slots and the synchronous call may use it at once -, and every plane's maxabs for the no-wrap rule.
+struct rc_trace {
+    int device = -1;
+    uint32_t nx = 0, ny = 0, k = 0;
+    int32_t *weights = nullptr;
+    uint32_t bound[rc::TRACE_MAX_PLANES] = {};
+};
+
+RC_EXPORT rc_trace *rc_trace_create(uint32_t nx, uint32_t ny, uint32_t k, const int32_t *planes, int *status)
+{
+    using namespace rc;
+    auto done = [&](int code) { if (status) *status = code; return (rc_trace *)nullptr; };
+    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: nx, ny in 1..65535"));
+    if (k > TRACE_MAX_PLANES) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: at most 16 weight planes"));
+    if (k && !planes) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: planes is NULL with k > 0"));
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return done(r);
+    rc_trace *t = new (std::nothrow) rc_trace;
+    if (!t) return done(fail(RC_ERR_WORKSPACE, "rc_trace_create: out of host memory"));
+    t->device = g_util.device; t->nx = nx; t->ny = ny; t->k = k;
+    if (k == 0) { if (status) *status = RC_OK; return t; }
+    const uint64_t N = (uint64_t)nx * ny;
+    const uint32_t kp = trace_padded_planes(k);
+    const bool on_device = is_device_ptr(planes);
+    hipStream_t s = g_util.stream;
+    int32_t *stage = nullptr;          // one plane of a host caller's, on its way into the interleaved copy
+    uint32_t *d_bound = nullptr;       // maxabs of a device caller's planes
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->weights), N * kp * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(t->weights, 0, N * kp * 4, s);
+    if (e == hipSuccess && !on_device) e = hipMalloc(reinterpret_cast<void **>(&stage), N * 4);
+    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_bound), TRACE_MAX_PLANES * 4);
+    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_bound, 0, TRACE_MAX_PLANES * 4, s);
+    for (uint32_t m = 0; m < k && e == hipSuccess; ++m) {
+        const int32_t *plane = planes + (uint64_t)m * N;
+        if (on_device) launch_trace_maxabs(plane, N, d_bound + m, s);
+        else {
+            uint32_t a = 0;
+            for (uint64_t p = 0; p < N; ++p) a = std::max(a, trace_abs(plane[p]));
+            t->bound[m] = a;
+            e = hipMemcpyAsync(stage, plane, N * 4, hipMemcpyHostToDevice, s);      // (`stage` is reused per plane: the stream orders copy and kernel)
+            plane = stage;
+        }
+        if (e == hipSuccess) launch_trace_interleave(plane, N, m, kp, t->weights, s);
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess && on_device) e = hipMemcpyAsync(t->bound, d_bound, k * 4, hipMemcpyDeviceToHost, s);
+    // (also after an error: copies and kernels queued before it may still read `stage`, `d_bound` and the caller's planes)
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e_sync;
+    if (stage) (void)hipFree(stage);
+    if (d_bound) (void)hipFree(d_bound);
+    if (e != hipSuccess) {
+        r = hip_fail(e, "rc_trace_create");
+        if (t->weights) (void)hipFree(t->weights);
+        delete t;
+        return done(r);
+    }
+    if (status) *status = RC_OK;
+    return t;
+}
+
+RC_EXPORT int rc_trace_destroy(rc_trace *t)
+{
+    if (!t) return RC_OK;
+    RC_ON_DEVICE(t->device);
+    // (a batch still queued on a slot reads the weights: both slots' streams and the synchronous call's are waited for)
+    (void)hipDeviceSynchronize();
+    if (t->weights) (void)hipFree(t->weights);
+    delete t;
+    return RC_OK;
+}
+
+RC_EXPORT uint32_t rc_trace_columns(const rc_trace *t) { return t ? rc::TRACE_MOMENTS + t->k : 0; }
+RC_EXPORT uint32_t rc_trace_weight_bound(const rc_trace *t, uint32_t m) { return t && m < t->k ? t->bound[m] : 0; }
+
+// what both forms check before the device is asked for: from the arguments alone
+static int trace_admit(const rc_trace *t, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
+                       const int64_t *out, uint64_t out_cells)
+{
+    using namespace rc;
+    if (!t || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: NULL / zero argument");
+    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
+    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_trace_frames: bit_depth above 16 (as for the summed views)");
+    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: out must be aligned to its int64 cells");
+    if (out_cells < (uint64_t)n * (TRACE_MOMENTS + t->k)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_trace_frames: out holds fewer than n * (4 + k) cells");
+    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
+    const uint64_t nb = ((uint64_t)t->nx * t->ny + 7) / 8;
+    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
+        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: the frames' geometry differs from the handle's");
+    if (!trace_batch_fits(t->nx, t->ny, level, bit_depth, t->k, t->bound, sizes, n))
+        return fail(RC_ERR_OUT_TOO_SMALL, "rc_trace_frames: a column could pass 2^63 - 1 (largest weight * largest value * set pixels a frame can hold)");
+    return RC_OK;
+}
+static int trace_on_its_device(const rc_trace *t)
+{
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return r;
+    return g_util.device == t->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_trace_frames: the handle belongs to another device");
+}
+
+RC_EXPORT int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
+                              uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
+{
+    int r = trace_admit(t, bit_depth, level, op_mode, data, sizes, n, out, out_cells);
+    if (r == RC_OK) r = trace_on_its_device(t);
+    if (r != RC_OK) return r;
+    const TraceReq req{t->weights, t->k};
+    return expand_run(RC_READ_SLOTS, false, t->nx, t->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, reinterpret_cast<uint64_t *>(out), out_cells,
+                      0, false, nullptr, 0, nullptr, nullptr, nullptr, &req);
+}
+
+RC_EXPORT int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                     const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_trace_frames_submit: slot 0 or 1");
+    int r = trace_admit(t, bit_depth, level, op_mode, data, sizes, n, out, out_cells);
+    if (r == RC_OK) r = trace_on_its_device(t);
+    if (r != RC_OK) return r;
+    const TraceReq req{t->weights, t->k};
+    return expand_run(slot, true, t->nx, t->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, reinterpret_cast<uint64_t *>(out), out_cells, 0, false,
+                      nullptr, 0, nullptr, nullptr, nullptr, &req);
 }

@@ -103,6 +103,16 @@ def plan_sub_volume(key, shape):
     return plan
 
 
+def centre_of_mass(traces):
+    """(row, col) as float64 arrays from a dict of get_frame_traces / iter_frame_traces: sum_row / sum and sum_col / sum per frame - the
+    intensity centre of mass in pixel coordinates -, NaN for a frame whose sum is 0"""
+    s = np.asarray(traces['sum'], np.float64)
+    safe = np.where(s != 0, s, 1.0)
+    row = np.where(s != 0, np.asarray(traces['sum_row'], np.float64) / safe, np.nan)
+    col = np.where(s != 0, np.asarray(traces['sum_col'], np.float64) / safe, np.nan)
+    return row, col
+
+
 def _event_views(buf, cap, total):
     """(rows int32, cols int32, area uint32, weight uint64): the first `total` events of rc_count_frames' output of capacity `cap`"""
     return (buf[8 * cap:12 * cap].view(np.int32)[:total], buf[12 * cap:16 * cap].view(np.int32)[:total],
@@ -1529,6 +1539,131 @@ class BatchedAccess:
                 vol[i * batch:i * batch + arr.shape[0]] = arr
         vol = vol[::-1 if fz else 1, ::-1 if fy else 1, ::-1 if fx else 1]
         return vol[0 if dz else slice(None), 0 if dy else slice(None), 0 if dx else slice(None)]
+
+    # ---- frame traces (rc_trace_frames): a few exact integers per frame, reduced on the device --------------------------------------------
+    def _trace_check_file(self):
+        h = self._header
+        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+        if level not in (1, 2, 3):
+            raise NotImplementedError('frame traces: reduction level %d' % level)
+        if level == 1 and d > 16:
+            raise NotImplementedError('frame traces: files of more than 16 bits (target_bit_depth %d): the sums are exact in 64 bits for '
+                                      '16-bit values' % d)
+
+    def _trace_handle(self, weights):
+        """(the _lib.FrameTrace to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
+        nx, ny = int(self._header['nx']), int(self._header['ny'])
+        if isinstance(weights, _lib.FrameTrace):
+            if (weights.nx, weights.ny) != (nx, ny):
+                raise ValueError('frame traces: a FrameTrace of %d x %d for frames of %d x %d' % (weights.nx, weights.ny, nx, ny))
+            return weights, False
+        return _lib.FrameTrace(nx, ny, weights), True
+
+    def _trace_dict(self, first, k, cells):
+        """a batch's int64[k, 4 + planes] as the dict get_frame_traces returns (copies of their own)"""
+        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
+        return {'count': cells[:, 0].copy(), 'sum': cells[:, 1].copy(), 'sum_row': cells[:, 2].copy(), 'sum_col': cells[:, 3].copy(),
+                'weighted': cells[:, 4:].copy(), 'frame_ids': ids}
+
+    def _trace_stream(self, z0, n, batch, ft):
+        """The engine of get_frame_traces and iter_frame_traces: the batches go through rc_trace_frames_submit / rc_expand_frames_wait on the
+        two slots, so the next batch is read from the file and queued before this one is waited for; 8 * (4 + k) bytes per frame cross the
+        link.  Yields (first frame, dict).  Routes and fall-backs are the summed views' (sum_frames)."""
+        h = self._header
+        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
+        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
+        cols = ft.columns
+        jobs = _jobs(z0, n, batch)
+        bufs = self._bufs.stream
+
+        def start(job):
+            """read the job's bytes into its slot's page-locked blob and offer them to the device; payload: what finish needs"""
+            k = job.count
+            p = job.payload = SimpleNamespace()
+            p.sizes, nbytes = self._batch_sizes(job.first, k)
+            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
+            p.blob = bufs[job.slot].array[:nbytes]
+            self._read_batch_into(p.blob, job.first, k)
+            bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], 8 * k * cols)
+            p.dev, p.status = self._route_for('sum')[1], None
+            if p.dev is None:
+                return
+            call = ((nx, ny, d, level, mode, p.dev), p.blob, p.sizes, k, bufs[2 + job.slot]._p, k * cols)
+            p.status = ft.submit_status(job.slot, *call)
+            if _slot_taken(p.status):
+                p.status = ft.frames_status(*call)       # another reader's iterator holds the slot: the synchronous call has resources of its own
+                return
+            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(p.status, 'rc_trace_frames_submit')
+            job.queued = p.status == _lib.RC_OK
+
+        def finish(job):
+            p, k = job.payload, job.count
+            st = p.status
+            if job.queued:
+                st, _ = _wait(job)
+            dst = bufs[2 + job.slot]
+            if p.dev is not None and st == _lib.RC_OK:
+                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                _lib.check(st, 'rc_expand_frames_wait')
+            else:
+                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
+                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
+                if got is not None:
+                    _lib.check(ft.frames_status((nx, ny, d, level, 0, scheme), *got, k, dst._p, k * cols), 'rc_trace_frames')
+                    self.last_batch_path = 'host-decode + device-expand'
+                    if p.dev is not None:
+                        self._foreign_file = True        # not offered to the device decoders again
+                else:
+                    geom0, pieces, sizes0 = self._stored_pieces_per_frame(job.first, k)
+                    _lib.check(ft.frames_status(geom0, pieces, sizes0, k, dst._p, k * cols), 'rc_trace_frames')
+                    self.last_batch_path = 'per-frame'
+            return job.first, self._trace_dict(job.first, k, dst.array[:8 * k * cols].view(np.int64).reshape(k, cols))
+
+        self._ra = None
+        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
+        self._user_iters += 1
+        try:
+            yield from self._two_slots(jobs, start, finish)
+        finally:
+            self._user_iters -= 1
+
+    def get_frame_traces(self, z0, n, weights=None):
+        """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) a few exact integers, reduced ON THE DEVICE in one call
+        (rc_trace_frames): what the reference prints as a dose rate per frame (utils/converters.py:108-111) and what a caller otherwise
+        computes from every frame's COO matrix on the host.  Returns a dict of int64 arrays: 'count' [n] - the set pixels -, 'sum' [n] - the
+        sum of their values (levels 2 and 3: every value is 1) -, 'sum_row' and 'sum_col' [n] - the sums of value * row and value * column
+        (centre_of_mass turns them into coordinates) -, 'weighted' [n, k] - the sums of value * weights[m][row][col] -, and 'frame_ids' [n]
+        - the frames' indices, a part file's frame ids.
+        weights: None, an integer array or GPU tensor of shape (ny, nx) or (k, ny, nx), k <= 16, whose values fit int32 - masks of a virtual
+        detector, an ROI -, or a _lib.FrameTrace the caller made, so that the part files of a run share one copy of the weights.  A batch
+        in which a column could pass 2^63 - 1 raises ValueError.  Routes (last_batch_path) and fall-backs as for sum_frames; files of more
+        than 16 bits are not taken (NotImplementedError)."""
+        n = self._frame_range(z0, n)
+        self._trace_check_file()
+        ft, own = self._trace_handle(weights)
+        stream = self._trace_stream(z0, n, n, ft)      # (one batch of n frames)
+        try:
+            return next(stream)[1]
+        finally:
+            stream.close()
+            if own:
+                ft.close()
+
+    def iter_frame_traces(self, z0=0, n=None, batch=64, weights=None):
+        """get_frame_traces for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two batches in
+        flight (rc_trace_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
+        n = self._frame_range(z0, n, batch)
+        self._trace_check_file()
+        ft, own = self._trace_handle(weights)
+        stream = self._trace_stream(z0, n, batch, ft)
+        try:
+            yield from stream
+        finally:
+            stream.close()
+            if own:
+                ft.close()
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
