@@ -4,6 +4,7 @@ stock decoder takes, and the read-ahead that serves the reference's own frame-at
 (recode_reader.py) inherits BatchedAccess; the methods here use its file handle, header, metadata table and COO helpers.
 """
 import os
+from contextlib import contextmanager
 from types import SimpleNamespace
 
 import numpy as np
@@ -138,15 +139,43 @@ def count_frames_now(geom, data, sizes, k, method, area_threshold):
     return st, prefix, _event_views(buf, cap, int(prefix[k])) if st == _lib.RC_OK else None
 
 
-class _PlainAdder:
-    """What _sum_stream drives into a _lib.FrameSum: the frames' values (rc_sum_add_frames / _submit).  geom is a batch's tuple for
-    rc_expand_frames, frame shape first."""
-    what = 'rc_sum_add_frames'
+def _area_threshold(area_threshold):
+    thr = int(area_threshold)
+    if not 0 <= thr < 1 << 32:
+        raise ValueError('area_threshold must fit 32 bits')
+    return thr
+
+
+class _Kind:
+    """What the ladder of the 'sum' route family (BatchedAccess._offer / _settle) is told about the kind of result a batch becomes; one
+    small subclass per kind.  geom is a batch's tuple for rc_expand_frames - (nx, ny, bit depth, level, op_mode, scheme) -, and every
+    rung of the ladder makes the same call under another one: the file's own, the stored pieces' (.., 0, scheme) of a host-decoded batch,
+    _stored_pieces_per_frame's.  What a kind keeps between the calls for a job is in job.payload, next to the ladder's own fields."""
+    what = None                           # the library call, as _lib.check's messages name it (queued: what + '_submit')
+    verdict = 'rc_expand_frames_wait'     # ... and as they name a streamed batch's verdict
 
     @staticmethod
     def queues(level):
-        """whether batches of this level go through the two slots"""
+        """whether batches of this level go through the two slots (False: the synchronous call, which counts first)"""
         return True
+
+    def room(self, job, geom, sizes, k):
+        """prepares the job's output for a batch of k frames under geom: called once before every rung's call(s)"""
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        """the device call, status returned: queued on `slot`, or (None) synchronous"""
+        raise NotImplementedError
+
+    def item(self, job):
+        """what the stream yields for a finished job (None: nothing)"""
+
+
+class _PlainAdder(_Kind):
+    """A batch's frames added into a _lib.FrameSum, their values (rc_sum_add_frames / _submit): the job's payload names the handle (fs),
+    its window and whether it is the window's last job.  fold(fs, grow), where set, is called before an add that grows fs's bound by
+    `grow` - the host-decoded and per-frame adds included, so a batch that was queued and then refused grows the bound twice."""
+    what = 'rc_sum_add_frames'
+    fold = None
 
     @staticmethod
     def view_shape(nx, ny):
@@ -156,24 +185,25 @@ class _PlainAdder:
     def grows_by(geom, sizes, n):
         return _lib.FrameSum.grows_by(geom, n)
 
-    @staticmethod
-    def submit_status(fs, slot, geom, data, sizes, n):
-        return fs.submit_status(slot, geom, data, sizes, n)
+    def room(self, job, geom, sizes, k):
+        if self.fold is not None:
+            self.fold(job.payload.fs, self.grows_by(geom, sizes, k))
 
-    @staticmethod
-    def add_status(fs, geom, data, sizes, n):
-        return fs.add_status(geom, data, sizes, n)
+    def call(self, job, geom, data, sizes, k, slot=None):
+        fs = job.payload.fs
+        return fs.add_status(geom, data, sizes, k) if slot is None else fs.submit_status(slot, geom, data, sizes, k)
+
+    def item(self, job):
+        return job.payload.window if job.payload.last else None
 
 
-class _CountedAdder:
+class _CountedAdder(_PlainAdder):
     """The counted add (rc_sum_add_counted / _submit): one count per event of the frames, the view `upsample` times finer than they are.
-    Levels 2 and 3 wait for their set-pixel count inside the call: they go through the synchronous one, as in _count_stream."""
+    Levels 2 and 3 wait for their set-pixel count inside the call: they go through the synchronous one, like the events themselves."""
     what = 'rc_sum_add_counted'
 
     def __init__(self, method, area_threshold, upsample):
-        self.code, self.thr, self.s = count_method(method), int(area_threshold), int(upsample)
-        if not 0 <= self.thr < 1 << 32:
-            raise ValueError('area_threshold must fit 32 bits')
+        self.code, self.thr, self.s = count_method(method), _area_threshold(area_threshold), int(upsample)
         if not 1 <= self.s <= 16:
             raise ValueError('upsample must be in 1..16')
 
@@ -188,20 +218,102 @@ class _CountedAdder:
     def grows_by(geom, sizes, n):
         return _lib.FrameSum.grows_by_counted(geom, sizes, n)
 
-    def submit_status(self, fs, slot, geom, data, sizes, n):
-        return fs.submit_counted_status(slot, geom, data, sizes, n, self.code, self.thr, self.s)
+    def call(self, job, geom, data, sizes, k, slot=None):
+        fs, how = job.payload.fs, (self.code, self.thr, self.s)
+        return fs.add_counted_status(geom, data, sizes, k, *how) if slot is None else fs.submit_counted_status(slot, geom, data, sizes, k, *how)
 
-    def add_status(self, fs, geom, data, sizes, n):
-        return fs.add_counted_status(geom, data, sizes, n, self.code, self.thr, self.s)
+
+class _Events(_Kind):
+    """A batch's events (rc_count_frames / _submit): level 1 bounds them from the sizes and is queued, its output the slot's; levels 2 and
+    3 have no bound short of their pixels and go through the synchronous call, which counts first (count_frames_now)."""
+    what = verdict = 'rc_count_frames'
+
+    def __init__(self, method, area_threshold, outs):
+        self.code, self.thr, self.outs = count_method(method), _area_threshold(area_threshold), outs
+
+    @staticmethod
+    def queues(level):
+        return level == 1
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        p = job.payload
+        p.result = None
+        if slot is None:
+            st, p.prefix, p.result = count_frames_now(geom, data, sizes, k, self.code, self.thr)
+            return st
+        p.cap = _l1_cap(sizes, geom[2])
+        self.outs[2 + slot] = _pinned(self.outs[2 + slot], 20 * p.cap)
+        return _lib.lib().rc_count_frames_submit(slot, *geom, _lib.ptr(data), _lib.ptr(sizes), k, self.code, self.thr, self.outs[2 + slot]._p, p.cap)
+
+    def item(self, job):
+        p = job.payload
+        if p.result is None:          # (the queued call delivered: copies of the slot's output)
+            p.result = tuple(a.copy() for a in _event_views(self.outs[2 + job.slot].array, p.cap, int(p.prefix[job.count])))
+        return (job.first, p.prefix) + p.result
+
+
+class _Dense(_Kind):
+    """A region of a batch's frames as cells of dt (rc_expand_frames_dense / _submit), written to the slot's page-locked output (outs:
+    the reader's stream buffers) - sized before every rung, because the fall-backs write there too - or to `dst`, an address in host or
+    device memory, which the synchronous form is given."""
+    what = 'rc_expand_frames_dense'
+
+    def __init__(self, region, dt, outs=None, dst=None):
+        self.region, self.dt, self.outs, self.dst = tuple(region), dt, outs, dst
+
+    def _cells(self, k):
+        return k * self.region[2] * self.region[3]
+
+    def room(self, job, geom, sizes, k):
+        if self.outs is not None:
+            self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], self._cells(k) * self.dt.itemsize)
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        L = _lib.lib()
+        dst = self.dst if self.outs is None else self.outs[2 + job.slot]._p
+        args = tuple(geom) + (_lib.ptr(data), _lib.ptr(sizes), k) + self.region + (self.dt.itemsize, dst, self._cells(k))
+        return L.rc_expand_frames_dense(*args, None) if slot is None else L.rc_expand_frames_dense_submit(slot, *args)
+
+    def item(self, job):
+        if self.outs is None:         # (the caller's own memory has been written)
+            return None
+        k, (w, h) = job.count, self.region[2:4]
+        return job.payload.index, self.outs[2 + job.slot].array[:self._cells(k) * self.dt.itemsize].view(self.dt).reshape(k, h, w)
+
+
+class _Traces(_Kind):
+    """A batch's traces (rc_trace_frames / _submit on the _lib.FrameTrace ft): int64[k, ft.columns] in the slot's page-locked output,
+    handed out as as_dict(first, k, cells) makes them."""
+    what = 'rc_trace_frames'
+
+    def __init__(self, ft, outs, as_dict):
+        self.ft, self.outs, self.as_dict = ft, outs, as_dict
+
+    def room(self, job, geom, sizes, k):
+        self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * k * self.ft.columns)
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        out = (self.outs[2 + job.slot]._p, k * self.ft.columns)
+        return self.ft.frames_status(geom, data, sizes, k, *out) if slot is None else self.ft.submit_status(slot, geom, data, sizes, k, *out)
+
+    def item(self, job):
+        k, cols = job.count, self.ft.columns
+        return job.first, self.as_dict(job.first, k, self.outs[2 + job.slot].array[:8 * k * cols].view(np.int64).reshape(k, cols))
+
+
+def _device_path(dev):
+    """last_batch_path of a batch the device decoders took under scheme `dev`"""
+    return 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
 
 
 class _Job:
-    """One batch of a streaming pipeline: frames first .. first + count - 1, the device slot (0 or 1) it goes through, whether it is queued
-    there (submitted and not yet waited for), and what its family keeps between start and finish."""
-    __slots__ = ('first', 'count', 'slot', 'queued', 'payload')
+    """One batch of a streaming pipeline: frames first .. first + count - 1 - or the `count` frames that `frames` lists, ascending -, the
+    device slot (0 or 1) it goes through, whether it is queued there (submitted and not yet waited for), and what its family keeps
+    between start and finish."""
+    __slots__ = ('first', 'count', 'slot', 'queued', 'payload', 'frames')
 
-    def __init__(self, first, count, payload=None):
-        self.first, self.count, self.slot, self.queued, self.payload = first, count, 0, False, payload
+    def __init__(self, first, count, payload=None, frames=None):
+        self.first, self.count, self.slot, self.queued, self.payload, self.frames = first, count, 0, False, payload, frames
 
 
 def _jobs(z0, n, batch):
@@ -378,24 +490,30 @@ class BatchedAccess:
         lo = self._frame_data_start_position + int(self._seek_table[z0, 1])
         if not self._is_intermediate:
             return self._read_into(blob, lo, move_fp)
-        fd = self._fp.fileno()
-        sizes = self._seek_table[z0:z0 + n, 0].astype(np.int64)
-        ats = np.concatenate([[0], np.cumsum(sizes)])
-
-        def some(lo, hi):
-            for i in range(lo, hi):
-                size, at = int(sizes[i]), int(ats[i])
-                pos, got = self._frame_data_start_position + int(self._seek_table[z0 + i, 1]), 0
-                while got < size:
-                    k = os.preadv(fd, [memoryview(blob[at + got:at + size])], pos + got)
-                    if k <= 0:
-                        raise ValueError('file shorter than its records say')
-                    got += k
-        nthr = 4 if int(ats[-1]) >= (8 << 20) and n >= 4 else 1      # (as _read_into: a read from the page cache is a memcpy)
+        some, total = self._piecewise(blob, range(z0, z0 + n), 'file shorter than its records say')
+        nthr = 4 if total >= (8 << 20) and n >= 4 else 1      # (as _read_into: a read from the page cache is a memcpy)
         if nthr == 1:
             return some(0, n)
         cuts = [n * t // nthr for t in range(nthr + 1)]
         list(self._bufs.pool('read', 4).map(lambda t: some(cuts[t], cuts[t + 1]), range(nthr)))
+
+    def _piecewise(self, blob, frames, short):
+        """(some, bytes in all): some(lo, hi) reads the data of frames[lo:hi] to their places in `blob`, where the frames that `frames`
+        lists lie back to back - one positional read per frame, and more where one comes back short; `short`: what to say of a file
+        that ends before a frame does"""
+        fd, table, start = self._fp.fileno(), self._seek_table, self._frame_data_start_position
+        ats = np.concatenate([[0], np.cumsum(table[list(frames), 0].astype(np.int64))])
+
+        def some(lo, hi):
+            for i in range(lo, hi):
+                at, end = int(ats[i]), int(ats[i + 1])
+                pos = start + int(table[int(frames[i]), 1]) - at
+                while at < end:
+                    k = os.preadv(fd, [memoryview(blob[at:end])], pos + at)
+                    if k <= 0:
+                        raise ValueError(short)
+                    at += k
+        return some, int(ats[-1])
 
     def _frame_range(self, z0, n, batch=None):
         """the number of frames a batched call covers (n, or None: from z0 to the end), checked against the file.  The synchronous calls
@@ -487,6 +605,94 @@ class BatchedAccess:
                     _drain(queued)
                 except Exception:         # (a generator finalised while the interpreter shuts down)
                     pass
+
+    @contextmanager
+    def _takes_over_from_readahead(self):
+        """What every streaming generator a caller drives is wrapped in.  The read-ahead under get_frame / get_next_frame keeps an iterator
+        of its own alive on the same page-locked blobs and slots, with one batch queued on the device: it is ended first (its queued batch
+        waited for, the window it serves forgotten), and it stays off while the generator lives (_user_iters)."""
+        self._ra = None
+        self._close_ra_iter()
+        self._user_iters += 1
+        try:
+            yield
+        finally:
+            self._user_iters -= 1
+
+    # ---- the ladder of the 'sum' route family: a batch is offered to the device decoders and falls back rung by rung ----------------------
+    def _batch_geom(self, mode, scheme):
+        h = self._header
+        return int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), mode, scheme
+
+    def _offer(self, kind, job, sync=False):
+        """The ladder's first half, _two_slots' start: the job's file bytes are read into page-locked memory - the slot's blob, or (sync)
+        the synchronous calls' - and, where the route names a device scheme, offered to the device decoders as `kind` (a _Kind) calls them:
+        queued on the job's slot, or through the synchronous call when the kind does not queue this level, when another reader holds
+        the slot, or in the synchronous form.  Of a queued call only RC_OK (job.queued), RC_ERR_UNSUPPORTED and RC_ERR_CORRUPT pass; the
+        synchronous call's status is _settle's to judge.  The job's payload keeps sizes, blob, dev (the scheme offered under, None: not
+        offered) and status."""
+        if job.payload is None:
+            job.payload = SimpleNamespace()
+        p, k, bufs = job.payload, job.count, self._bufs
+        p.sizes, nbytes = self._batch_sizes(job.first, k, job.frames)
+        if sync:
+            bufs.pin_blob = _pinned(bufs.pin_blob, nbytes + 64)
+            p.blob = bufs.pin_blob.array[:nbytes]
+        else:
+            bufs.stream[job.slot] = _pinned(bufs.stream[job.slot], nbytes + 64)
+            p.blob = bufs.stream[job.slot].array[:nbytes]
+        if job.frames is None:
+            self._read_batch_into(p.blob, job.first, k)
+        else:
+            self._read_frames_into(p.blob, job.frames)
+        p.dev, p.status = self._route_for('sum')[1], None
+        if p.dev is None:
+            return
+        geom = self._batch_geom(int(self._header['rc_operation_mode']), p.dev)
+        call = (job, geom, p.blob, p.sizes, k)
+        kind.room(job, geom, p.sizes, k)
+        if not sync and kind.queues(geom[3]):
+            p.status = kind.call(*call, job.slot)
+            if not _slot_taken(p.status):
+                if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+                    _lib.check(p.status, kind.what + '_submit')
+                job.queued = p.status == _lib.RC_OK
+                return
+        # a level that waits for its count inside the call, or another reader's iterator holds the slot: the synchronous call has
+        # resources of its own
+        p.status = kind.call(*call)
+
+    def _settle(self, kind, job, sync=False):
+        """The ladder's second half, _two_slots' finish: waits for a queued job's verdict, and takes the batch down the rungs the device
+        decoders left - the stock decoders on the thread pool and the same call on the stored pieces, then the frame-at-a-time reader's
+        frames restated as stored ones (_stored_pieces_per_frame).  Sets last_batch_path; marks the file foreign when a batch that was
+        offered came out of the stock decoders instead.  Returns kind.item(job)."""
+        p, k = job.payload, job.count
+        st, offered = p.status, p.dev is not None
+        if job.queued:
+            st, p.prefix = _wait(job)
+        if offered and st == _lib.RC_OK:
+            self.last_batch_path = _device_path(p.dev)
+        elif offered and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
+            _lib.check(st, kind.what if sync else kind.verdict)
+        else:
+            # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
+            got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(self._header) else None
+            if got is not None:
+                (data, sizes), geom, path = got, self._batch_geom(0, int(self._header['compression_scheme'])), 'host-decode + device-expand'
+            else:
+                (geom, data, sizes), path = self._stored_pieces_per_frame(job.first, k, job.frames), 'per-frame'
+            kind.room(job, geom, sizes, k)
+            _lib.check(kind.call(job, geom, data, sizes, k), kind.what)
+            self.last_batch_path = path
+            if offered and got is not None:
+                self._foreign_file = True        # not offered to the device decoders again
+        return kind.item(job)
+
+    def _ladder(self, kind, jobs):
+        """the streaming form: `jobs` through _offer / _settle on the two slots, the items of `kind` yielded"""
+        with self._takes_over_from_readahead():
+            yield from self._two_slots(jobs, lambda job: self._offer(kind, job), lambda job: self._settle(kind, job))
 
     _RA_FRAMES = 32          # frames fetched ahead once the calls turn out to be sequential
     _RA_BYTES = 512 << 20    # ... as long as their triplets fit into this much page-locked memory
@@ -621,7 +827,7 @@ class BatchedAccess:
                 st, prefix, res = self._expand_now(int(h['rc_operation_mode']), dev, blob, sizes, n, dst)
                 if st == _lib.RC_OK:
                     self._note_batch_end(z0 + n)
-                    self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
+                    self.last_batch_path = _device_path(dev)
                     return prefix, res
                 # Outside the device decoders' subset - or a stream they could not make sense of (a foreign encoder's independent 64 KiB
                 # LZ4 blocks look like that): the paths below decode with the stock library, which is also the judge of whether
@@ -793,16 +999,10 @@ class BatchedAccess:
                 pass
 
     def iter_frames_triplets(self, z0=0, n=None, batch=64, coo=False, device_blosc=False, device_zlib=False):
-        """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc, device_zlib: as in get_frames_triplets).  The read-ahead under get_frame / get_next_frame keeps
-        an iterator of its own alive on the same page-locked buffers, with one batch queued on the device: it is ended first (its queued
-        batch waited for, the window it serves forgotten), and it stays off while this generator lives."""
-        self._ra = None
-        self._close_ra_iter()
-        self._user_iters += 1
-        try:
+        """The caller's own streaming iterator (documented at _iter_frames_impl; device_blosc, device_zlib: as in get_frames_triplets):
+        the read-ahead's, which runs _iter_frames_impl too, is ended first and stays off while this generator lives."""
+        with self._takes_over_from_readahead():
             yield from self._iter_frames_impl(z0, n, batch, coo, device_blosc, device_zlib)
-        finally:
-            self._user_iters -= 1
 
     def _iter_frames_impl(self, z0=0, n=None, batch=64, coo=False, device_blosc=False, device_zlib=False):
         """Streams frames z0 .. z0+n-1 of a merged file (records z0 .. of a part file: the reference's own read test sums a part file's
@@ -861,7 +1061,7 @@ class BatchedAccess:
             if st == _lib.RC_ERR_CORRUPT or (st == _lib.RC_ERR_UNSUPPORTED and zdev):      # the stock decoder is the judge
                 return one_call(job)
             _lib.check(st, 'rc_expand_frames_wait')
-            self.last_batch_path = 'device-inflate' if zdev else 'device'
+            self.last_batch_path = _device_path(dev)
             return job.first, prefix, outs[job.slot].result(int(prefix[job.count]))
 
         def stop(job):
@@ -954,8 +1154,6 @@ class BatchedAccess:
             for job in jobs:
                 yield one_call(job)
             return
-        self._ra = None
-        self._close_ra_iter()
         L = _lib.lib()
         geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['rc_operation_mode']), int(h['compression_scheme']))
         bufs, sbufs = self._bufs.stream, self._bufs.l2
@@ -1001,11 +1199,8 @@ class BatchedAccess:
             self.last_batch_path = 'device'
             return (job.first, prefix, rc[:tot].copy(), rc[cap:cap + tot].copy(), sp,
                     sbufs[job.slot].array[:2 * ns].view(np.uint16).astype(self._numpy_dtype))
-        self._user_iters += 1
-        try:
+        with self._takes_over_from_readahead():
             yield from self._two_slots(jobs, start, finish)
-        finally:
-            self._user_iters -= 1
 
     # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
     def _stored_pieces_per_frame(self, a, k, frames=None):
@@ -1033,84 +1228,15 @@ class BatchedAccess:
                 sizes[i, 1] = sizes[i, 2] = packed.size
         return (nx, ny, d, 1 if level == 1 else 3, 0, 0), np.ascontiguousarray(np.concatenate(parts)), sizes
 
-    def _sum_per_frame(self, fs, room, a, k, adder=_PlainAdder):
-        """sum_frames' last route: frames a .. a+k-1 as _stored_pieces_per_frame restates them - so the handle's bound grows as for any
-        other batch - and added like one: a caller's handle (`into`) receives them too."""
-        geom, pieces, sizes = self._stored_pieces_per_frame(a, k)
-        room(fs, adder.grows_by(geom, sizes, k))
-        _lib.check(adder.add_status(fs, geom, pieces, sizes, k), adder.what)
-        self.last_batch_path = 'per-frame'
-
-    def _sum_stream(self, windows, batch, room, adder=_PlainAdder):
+    def _sum_stream(self, windows, batch, adder):
         """The engine of sum_frames and iter_frame_sums: windows = [(first frame, frames > 0, FrameSum)], one after the other; their batches
-        go through rc_sum_add_frames_submit / rc_expand_frames_wait on the two slots as ONE sequence, so the next batch - the next window's
-        first one, into its own handle, included - is read from the file and queued before this one is waited for.  Yields a window's
-        index once every batch of it has been added.  Every device call is made on the caller's thread.  room(fs, grow) is called before
-        an add that grows fs's bound by `grow`.  adder: what is added - the frames' values (_PlainAdder) or their events (_CountedAdder).
-        Routes and fall-backs: see sum_frames."""
-        h = self._header
-        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        # a job's payload: its window, whether it is the window's last; from start on: sizes, blob, the device scheme (None: not offered),
-        # and the status so far
-        jobs = [_Job(b, min(batch, a + k - b), SimpleNamespace(window=w, last=b + batch >= a + k))
-                for w, (a, k, _) in enumerate(windows) for b in range(a, a + k, batch)]
-        bufs = self._bufs.stream
-
-        def start(job):
-            """read the job's bytes into its slot's page-locked blob and offer them to the device"""
-            p, k = job.payload, job.count
-            fs = windows[p.window][2]
-            p.sizes, nbytes = self._batch_sizes(job.first, k)
-            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
-            p.blob = bufs[job.slot].array[:nbytes]
-            self._read_batch_into(p.blob, job.first, k)
-            p.dev, p.status = self._route_for('sum')[1], None
-            if p.dev is None:
-                return
-            geom = (nx, ny, d, level, mode, p.dev)
-            room(fs, adder.grows_by(geom, p.sizes, k))
-            if adder.queues(level):
-                p.status = adder.submit_status(fs, job.slot, geom, p.blob, p.sizes, k)
-            if not adder.queues(level) or _slot_taken(p.status):
-                # (a level that waits for its count inside the call, or another reader's iterator holds the slot) the synchronous call
-                # has resources of its own
-                p.status = adder.add_status(fs, geom, p.blob, p.sizes, k)
-                return
-            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(p.status, adder.what + '_submit')
-            job.queued = p.status == _lib.RC_OK
-
-        def finish(job):
-            p, k = job.payload, job.count
-            fs, st = windows[p.window][2], p.status
-            if job.queued:
-                st, _ = _wait(job)
-            if p.dev is not None and st == _lib.RC_OK:
-                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_expand_frames_wait')
-            else:
-                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
-                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
-                if got is not None:
-                    geom0 = (nx, ny, d, level, 0, scheme)
-                    room(fs, adder.grows_by(geom0, got[1], k))
-                    _lib.check(adder.add_status(fs, geom0, *got, k), adder.what)
-                    self.last_batch_path = 'host-decode + device-expand'
-                    if p.dev is not None:
-                        self._foreign_file = True        # not offered to the device decoders again
-                else:
-                    self._sum_per_frame(fs, room, job.first, k, adder)
-            return p.window if p.last else None
-
-        self._ra = None
-        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
-        self._user_iters += 1
-        try:
-            yield from self._two_slots(jobs, start, finish)
-        finally:
-            self._user_iters -= 1
+        go down the ladder (_ladder: rc_sum_add_frames_submit / rc_expand_frames_wait on the two slots) as ONE sequence, so the next batch -
+        the next window's first one, into its own handle, included - is read from the file and queued before this one is waited for.
+        Yields a window's index once every batch of it has been added.  Every device call is made on the caller's thread.  adder: what is
+        added - the frames' values (_PlainAdder) or their events (_CountedAdder).  Routes and fall-backs: see sum_frames."""
+        jobs = [_Job(b, min(batch, a + k - b), SimpleNamespace(fs=fs, window=w, last=b + batch >= a + k))
+                for w, (a, k, fs) in enumerate(windows) for b in range(a, a + k, batch)]
+        return self._ladder(adder, jobs)
 
     def sum_frames(self, z0=0, n=None, batch=64, into=None):
         """The sum of frames z0 .. z0+n-1 of a merged file (records of a part file) as uint64[ny, nx] - what the reference's viewer and its
@@ -1124,12 +1250,12 @@ class BatchedAccess:
         handle's bound() is an UPPER bound: a batch the device queued and then refused (the first one or two batches of a stock encoder's
         file, which are then decoded on the host and added again) has grown it twice, so a caller's handle can be refused up to two
         batches' share early.
-        Routes, per batch (last_batch_path): the device decoders ('device', 'device-inflate'); for streams they refuse and for host-only
-        schemes the stock decoders on the thread pool, then one add of the stored pieces ('host-decode + device-expand'); what is left
-        goes through the frame-at-a-time reader ('per-frame').  Files of more than 16 bits are not taken (NotImplementedError)."""
+        Routes, per batch (last_batch_path): the device decoders ("device", "device-inflate"); for streams they refuse and for host-only
+        schemes the stock decoders on the thread pool, then one add of the stored pieces ("host-decode + device-expand"); what is left
+        goes through the frame-at-a-time reader ("per-frame").  Files of more than 16 bits are not taken (NotImplementedError)."""
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
-        return self._sum_into(z0, n, batch, into, _PlainAdder)
+        return self._sum_into(z0, n, batch, into, _PlainAdder())
 
     def _sum_into(self, z0, n, batch, into, adder):
         """sum_frames and sum_frames_counted behind their argument checks"""
@@ -1137,13 +1263,14 @@ class BatchedAccess:
         fs = into if into is not None else _lib.FrameSum(vx, vy)
         total = None if into is not None else np.zeros((vy, vx), np.uint64)
 
-        def room(view, grow):
+        def fold(view, grow):
             """this call's own view is folded before `grow` could overflow it (rc_sum_fetch waits for every queued add itself)"""
-            if total is not None and view.bound() + grow > view.LIMIT:
+            if view.bound() + grow > view.LIMIT:
                 np.add(total, view.fetch_view(reset=True), out=total)
+        adder.fold = fold if total is not None else None
         try:
             if n:
-                for _ in self._sum_stream([(z0, n, fs)], batch, room, adder):
+                for _ in self._sum_stream([(z0, n, fs)], batch, adder):
                     pass
             if total is None:
                 return n
@@ -1171,14 +1298,14 @@ class BatchedAccess:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
-        yield from self._iter_sums(frames_per_view, z0, n, batch, _PlainAdder)
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _PlainAdder())
 
     def _iter_sums(self, frames_per_view, z0, n, batch, adder):
         """iter_frame_sums and iter_frame_sums_counted behind their argument checks"""
         vx, vy = adder.view_shape(int(self._header['nx']), int(self._header['ny']))
         views = [_lib.FrameSum(vx, vy), _lib.FrameSum(vx, vy)]
         windows = [(a, min(frames_per_view, z0 + n - a), views[i & 1]) for i, a in enumerate(range(z0, z0 + n, frames_per_view))]
-        stream = self._sum_stream(windows, batch, lambda view, grow: None, adder)
+        stream = self._sum_stream(windows, batch, adder)
         try:
             for w in stream:
                 a, k, view = windows[w]
@@ -1199,79 +1326,10 @@ class BatchedAccess:
                                       '16-bit values' % d)
 
     def _count_stream(self, z0, n, batch, area_threshold, method):
-        """The engine of get_frames_counted and iter_frames_counted: the batches go through rc_count_frames_submit / rc_expand_frames_wait
-        on the two slots, so the next batch is read from the file and queued before this one is waited for.  Levels 2 and 3 have no bound
-        on a batch's events short of its pixels: they go through the synchronous call, which counts first.  Routes and fall-backs are the
-        summed views' (sum_frames)."""
-        h = self._header
-        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        code, thr = count_method(method), int(area_threshold)
-        if not 0 <= thr < 1 << 32:
-            raise ValueError('area_threshold must fit 32 bits')
-        L = _lib.lib()
-        jobs = _jobs(z0, n, batch)
-        bufs = self._bufs.stream
-
-        def start(job):
-            """read the job's bytes into its slot's page-locked blob and offer them to the device; payload: what finish needs"""
-            k = job.count
-            p = job.payload = SimpleNamespace(result=None, cap=0)
-            p.sizes, nbytes = self._batch_sizes(job.first, k)
-            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
-            p.blob = bufs[job.slot].array[:nbytes]
-            self._read_batch_into(p.blob, job.first, k)
-            p.dev, p.status = self._route_for('sum')[1], None
-            if p.dev is None:
-                return
-            geom = (nx, ny, d, level, mode, p.dev)
-            if level == 1:
-                p.cap = _l1_cap(p.sizes, d)
-                bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], 20 * p.cap)
-                p.status = L.rc_count_frames_submit(job.slot, *geom, _lib.ptr(p.blob), _lib.ptr(p.sizes), k, code, thr, bufs[2 + job.slot]._p, p.cap)
-                if p.status == _lib.RC_OK:
-                    job.queued = True
-                    return
-                if not _slot_taken(p.status):
-                    if p.status not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                        _lib.check(p.status, 'rc_count_frames_submit')
-                    return
-            # another reader's iterator holds the slot, or a level without a bound: the synchronous call has resources of its own
-            p.status, p.prefix, p.result = count_frames_now(geom, p.blob, p.sizes, k, code, thr)
-
-        def finish(job):
-            p, k = job.payload, job.count
-            st = p.status
-            if job.queued:
-                st, p.prefix = _wait(job)
-                if st == _lib.RC_OK:
-                    p.result = tuple(a.copy() for a in _event_views(bufs[2 + job.slot].array, p.cap, int(p.prefix[k])))
-            if p.dev is not None and st == _lib.RC_OK:
-                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_count_frames')
-            else:
-                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
-                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
-                if got is not None:
-                    st, p.prefix, p.result = count_frames_now((nx, ny, d, level, 0, scheme), *got, k, code, thr)
-                    self.last_batch_path = 'host-decode + device-expand'
-                    if p.dev is not None:
-                        self._foreign_file = True        # not offered to the device decoders again
-                else:
-                    geom0, pieces, sizes0 = self._stored_pieces_per_frame(job.first, k)
-                    st, p.prefix, p.result = count_frames_now(geom0, pieces, sizes0, k, code, thr)
-                    self.last_batch_path = 'per-frame'
-                _lib.check(st, 'rc_count_frames')
-            return (job.first, p.prefix) + p.result
-
-        self._ra = None
-        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
-        self._user_iters += 1
-        try:
-            yield from self._two_slots(jobs, start, finish)
-        finally:
-            self._user_iters -= 1
+        """The engine of get_frames_counted and iter_frames_counted: the batches go down the ladder as events (_Events:
+        rc_count_frames_submit / rc_expand_frames_wait on the two slots), so the next batch is read from the file and queued before this
+        one is waited for.  Routes and fall-backs are the summed views' (sum_frames)."""
+        yield from self._ladder(_Events(method, area_threshold, self._bufs.stream), _jobs(z0, n, batch))
 
     def get_frames_counted(self, z0, n, area_threshold=0, method='weighted_average'):
         """Electron counting of frames z0 .. z0+n-1 of a merged file (records of a part file) in ONE device call (rc_count_frames): what the
@@ -1367,97 +1425,18 @@ class BatchedAccess:
         k, a = len(frames), int(frames[0])
         if int(frames[-1]) - a + 1 == k:
             return self._read_batch_into(blob, a, k)
-        fd, at = self._fp.fileno(), 0
-        for z in frames:
-            size, pos, got = int(self._seek_table[int(z), 0]), self._frame_data_start_position + int(self._seek_table[int(z), 1]), 0
-            while got < size:
-                m = os.preadv(fd, [memoryview(blob[at + got:at + size])], pos + got)
-                if m <= 0:
-                    raise ValueError('file shorter than its seek table says')
-                got += m
-            at += size
-        if not self._is_intermediate:
-            self._fp.seek(pos + size, 0)      # (where reading a run leaves a merged file: behind the last frame read)
-
-    def _dense_call(self, geom, data, sizes, k, region, dt, dst, cells, slot=None):
-        """rc_expand_frames_dense (slot None) or _submit, status returned; dst: an address, host or device"""
-        L = _lib.lib()
-        args = tuple(geom) + (_lib.ptr(data), _lib.ptr(sizes), k) + tuple(region) + (dt.itemsize, dst, cells)
-        return L.rc_expand_frames_dense(*args, None) if slot is None else L.rc_expand_frames_dense_submit(slot, *args)
-
-    def _dense_fall_back(self, frames, blob, sizes, region, dt, dst, cells, offered):
-        """A batch the device decoders refused (offered) or were never offered: the stock decoders on the thread pool, then the stored pieces
-        through the same device call; what is left goes through the frame-at-a-time reader, restated as stored frames (_sum_stream's routes)."""
-        h = self._header
-        k = len(frames)
-        got = self._host_decode_batch(blob, sizes, k, 2) if _stock_decoded(h) else None
-        if got is not None:
-            geom0 = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), 0, int(h['compression_scheme']))
-            _lib.check(self._dense_call(geom0, got[0], got[1], k, region, dt, dst, cells), 'rc_expand_frames_dense')
-            self.last_batch_path = 'host-decode + device-expand'
-            if offered:
-                self._foreign_file = True        # not offered to the device decoders again
-            return
-        geom0, pieces, sizes0 = self._stored_pieces_per_frame(int(frames[0]), k, frames)
-        _lib.check(self._dense_call(geom0, pieces, sizes0, k, region, dt, dst, cells), 'rc_expand_frames_dense')
-        self.last_batch_path = 'per-frame'
-
-    def _dense_geom(self, dev):
-        h = self._header
-        return (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), int(h['rc_operation_mode']), dev)
+        self._piecewise(blob, frames, 'file shorter than its seek table says')[0](0, k)
+        if not self._is_intermediate:         # (where reading a run leaves a merged file: behind the last frame read)
+            self._fp.seek(self._frame_data_start_position + int(self._seek_table[int(frames[-1])].sum()), 0)
 
     def _dense_stream(self, groups, region, dt):
-        """The engine of iter_frames_dense and get_sub_volume: groups = [frame indices, ascending] - one batch each - through
-        rc_expand_frames_dense_submit / rc_expand_frames_wait on the two slots, so the next batch is read from the file and queued before this
-        one is waited for.  Yields (index of the group, array[k, h, w]): a VIEW of the slot's page-locked output, valid until the generator
-        advances.  Routes and fall-backs are _sum_stream's."""
-        w, hh, isz = region[2], region[3], dt.itemsize
+        """The engine of iter_frames_dense and get_sub_volume: groups = [frame indices, ascending] - one batch each - down the ladder as
+        dense cells (_Dense: rc_expand_frames_dense_submit / rc_expand_frames_wait on the two slots), so the next batch is read from the
+        file and queued before this one is waited for.  Yields (index of the group, array[k, h, w]): a VIEW of the slot's page-locked
+        output, valid until the generator advances.  Routes and fall-backs are the summed views' (sum_frames)."""
         # (a job's first frame is chosen so that first + count is behind its last frame: where _two_slots leaves a merged file's counter)
-        jobs = [_Job(int(g[-1]) + 1 - len(g), len(g), SimpleNamespace(frames=g, index=i)) for i, g in enumerate(groups)]
-        bufs = self._bufs.stream
-
-        def start(job):
-            """read the job's bytes into its slot's page-locked blob and offer them to the device"""
-            p, k = job.payload, job.count
-            p.sizes, nbytes = self._batch_sizes(0, k, p.frames)
-            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
-            p.blob = bufs[job.slot].array[:nbytes]
-            self._read_frames_into(p.blob, p.frames)
-            p.cells = k * w * hh
-            bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], p.cells * isz)
-            p.dev, p.status = self._route_for('sum')[1], None
-            if p.dev is None:
-                return
-            call = (self._dense_geom(p.dev), p.blob, p.sizes, k, region, dt, bufs[2 + job.slot]._p, p.cells)
-            p.status = self._dense_call(*call, slot=job.slot)
-            if _slot_taken(p.status):
-                p.status = self._dense_call(*call)       # another reader's iterator holds the slot: the synchronous call has resources of its own
-                return
-            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(p.status, 'rc_expand_frames_dense_submit')
-            job.queued = p.status == _lib.RC_OK
-
-        def finish(job):
-            p, k = job.payload, job.count
-            st = p.status
-            if job.queued:
-                st, _ = _wait(job)
-            dst = bufs[2 + job.slot]
-            if p.dev is not None and st == _lib.RC_OK:
-                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_expand_frames_wait')
-            else:
-                self._dense_fall_back(p.frames, p.blob, p.sizes, region, dt, dst._p, p.cells, p.dev is not None)
-            return p.index, dst.array[:p.cells * isz].view(dt).reshape(k, hh, w)
-
-        self._ra = None
-        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
-        self._user_iters += 1
-        try:
-            yield from self._two_slots(jobs, start, finish)
-        finally:
-            self._user_iters -= 1
+        jobs = [_Job(int(g[-1]) + 1 - len(g), len(g), SimpleNamespace(index=i), g) for i, g in enumerate(groups)]
+        return self._ladder(_Dense(region, dt, self._bufs.stream), jobs)
 
     def get_frames_dense(self, z0, n, roi=None, out=None):
         """Frames z0 .. z0+n-1 of a merged file (records of a part file) as an array[n, h, w] of the file's dtype in ONE device call
@@ -1485,22 +1464,9 @@ class BatchedAccess:
             if tuple(out.shape) != shape or out.element_size() != dt.itemsize or not out.is_contiguous():
                 raise ValueError('get_frames_dense: out must be contiguous, of shape %s and %d bytes an element' % (shape, dt.itemsize))
             dst = int(out.data_ptr())
-        frames = np.arange(z0, z0 + n)
-        cells = n * shape[1] * shape[2]
-        sizes, total = self._batch_sizes(z0, n)
-        self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total + 64)
-        blob = self._bufs.pin_blob.array[:total]
-        self._read_batch_into(blob, z0, n)
-        dev = self._route_for('sum')[1]
-        st = None
-        if dev is not None:
-            st = self._dense_call(self._dense_geom(dev), blob, sizes, n, region, dt, dst, cells)
-            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_expand_frames_dense')
-        if st == _lib.RC_OK:
-            self.last_batch_path = 'device-inflate' if dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-        else:
-            self._dense_fall_back(frames, blob, sizes, region, dt, dst, cells, dev is not None)
+        kind, job = _Dense(region, dt, dst=dst), _Job(z0, n)
+        self._offer(kind, job, sync=True)        # (the ladder in its synchronous form: nothing is queued, `out` is written in place)
+        self._settle(kind, job, sync=True)
         self._note_batch_end(z0 + n)
         return out
 
@@ -1566,68 +1532,10 @@ class BatchedAccess:
                 'weighted': cells[:, 4:].copy(), 'frame_ids': ids}
 
     def _trace_stream(self, z0, n, batch, ft):
-        """The engine of get_frame_traces and iter_frame_traces: the batches go through rc_trace_frames_submit / rc_expand_frames_wait on the
-        two slots, so the next batch is read from the file and queued before this one is waited for; 8 * (4 + k) bytes per frame cross the
-        link.  Yields (first frame, dict).  Routes and fall-backs are the summed views' (sum_frames)."""
-        h = self._header
-        nx, ny, d = int(h['nx']), int(h['ny']), int(h['target_bit_depth'])
-        level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
-        cols = ft.columns
-        jobs = _jobs(z0, n, batch)
-        bufs = self._bufs.stream
-
-        def start(job):
-            """read the job's bytes into its slot's page-locked blob and offer them to the device; payload: what finish needs"""
-            k = job.count
-            p = job.payload = SimpleNamespace()
-            p.sizes, nbytes = self._batch_sizes(job.first, k)
-            bufs[job.slot] = _pinned(bufs[job.slot], nbytes + 64)
-            p.blob = bufs[job.slot].array[:nbytes]
-            self._read_batch_into(p.blob, job.first, k)
-            bufs[2 + job.slot] = _pinned(bufs[2 + job.slot], 8 * k * cols)
-            p.dev, p.status = self._route_for('sum')[1], None
-            if p.dev is None:
-                return
-            call = ((nx, ny, d, level, mode, p.dev), p.blob, p.sizes, k, bufs[2 + job.slot]._p, k * cols)
-            p.status = ft.submit_status(job.slot, *call)
-            if _slot_taken(p.status):
-                p.status = ft.frames_status(*call)       # another reader's iterator holds the slot: the synchronous call has resources of its own
-                return
-            if p.status not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(p.status, 'rc_trace_frames_submit')
-            job.queued = p.status == _lib.RC_OK
-
-        def finish(job):
-            p, k = job.payload, job.count
-            st = p.status
-            if job.queued:
-                st, _ = _wait(job)
-            dst = bufs[2 + job.slot]
-            if p.dev is not None and st == _lib.RC_OK:
-                self.last_batch_path = 'device-inflate' if p.dev == _lib.RC_SCHEME_ZLIB_DEVICE else 'device'
-            elif p.dev is not None and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                _lib.check(st, 'rc_expand_frames_wait')
-            else:
-                # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
-                got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(h) else None
-                if got is not None:
-                    _lib.check(ft.frames_status((nx, ny, d, level, 0, scheme), *got, k, dst._p, k * cols), 'rc_trace_frames')
-                    self.last_batch_path = 'host-decode + device-expand'
-                    if p.dev is not None:
-                        self._foreign_file = True        # not offered to the device decoders again
-                else:
-                    geom0, pieces, sizes0 = self._stored_pieces_per_frame(job.first, k)
-                    _lib.check(ft.frames_status(geom0, pieces, sizes0, k, dst._p, k * cols), 'rc_trace_frames')
-                    self.last_batch_path = 'per-frame'
-            return job.first, self._trace_dict(job.first, k, dst.array[:8 * k * cols].view(np.int64).reshape(k, cols))
-
-        self._ra = None
-        self._close_ra_iter()            # (the read-ahead's iterator uses the same page-locked blobs and slots)
-        self._user_iters += 1
-        try:
-            yield from self._two_slots(jobs, start, finish)
-        finally:
-            self._user_iters -= 1
+        """The engine of get_frame_traces and iter_frame_traces: the batches go down the ladder as traces (_Traces: rc_trace_frames_submit /
+        rc_expand_frames_wait on the two slots), so the next batch is read from the file and queued before this one is waited for;
+        8 * (4 + k) bytes per frame cross the link.  Yields (first frame, dict).  Routes and fall-backs are the summed views' (sum_frames)."""
+        return self._ladder(_Traces(ft, self._bufs.stream, self._trace_dict), _jobs(z0, n, batch))
 
     def get_frame_traces(self, z0, n, weights=None):
         """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) a few exact integers, reduced ON THE DEVICE in one call

@@ -453,6 +453,52 @@ def test_traces_on_this_librarys_files(hip, stack, tmp_path, level, scheme, dz, 
     rd.close()
 
 
+def test_two_readers_share_the_slots_on_the_sum_familys_ladder(hip, tmp_path, monkeypatch):
+    """The two streaming slots belong to the process: two readers of one small LZ4 file (6 frames of 48 x 64, 12 bits, level 1) advanced in
+    turn - dense batches of two frames on one, traces on the other - find each other's batches on the slots, and the batch that finds its
+    slot taken goes through the synchronous call of the same ladder: every batch equals a third reader's get_frames_dense /
+    get_frame_traces, and every one was decoded on the device.  Then two sum_frames into ONE handle while an iterator of the first reader
+    still holds a slot: twice a single reader's sum.  Six frames in batches of two is the smallest run in which both slots are held
+    when the other reader arrives."""
+    from pyrecode_amd import reader_batched as rb
+    rng = np.random.default_rng(33)
+    ny, nx, nz = 48, 64, 6
+    dark = rng.integers(80, 121, (ny, nx)).astype(np.uint16)
+    frames = np.where(rng.random((nz, ny, nx)) < 0.05, dark + rng.integers(1, 3900, (nz, ny, nx)), dark // 2).astype(np.uint16)
+    path = _write(tmp_path, dark, frames, 1, 2)
+    a, b, ref = _open(path), _open(path), _open(path)
+    planes = _masks(rng, ny, nx)
+    taken, asked = [], rb._slot_taken
+    monkeypatch.setattr(rb, "_slot_taken", lambda st: (taken.append(asked(st)), taken[-1])[1])      # (a count of the submits that found a slot held)
+    dense_it, trace_it = a.iter_frames_dense(batch=2), b.iter_frame_traces(batch=2, weights=planes)
+    dense, traces = [], []
+    for _ in range(3):
+        z, arr = next(dense_it)
+        dense.append((z, arr.copy()))
+        assert a.last_batch_path == "device"
+        traces.append(next(trace_it))
+        assert b.last_batch_path == "device"
+    assert next(dense_it, None) is None and next(trace_it, None) is None and [z for z, _ in dense] == [z for z, _ in traces] == [0, 2, 4]
+    assert any(taken), "no batch found its slot taken: the synchronous rung was not walked"
+    for (z, arr), (_, t) in zip(dense, traces):
+        want = ref.get_frames_dense(z, 2)
+        assert ref.last_batch_path == "device" and arr.dtype == want.dtype and np.array_equal(arr, want) and want.any()
+        _same(t, ref.get_frame_traces(z, 2, planes), range(z, z + 2))
+    # the summed views: both readers add into one handle while a dense iterator of a third still holds slot 1
+    want = ref.sum_frames(batch=2)
+    del taken[:]
+    held = ref.iter_frames_dense(batch=2)
+    next(held)
+    fs = hip.FrameSum(nx, ny)
+    for rd in (a, b):
+        assert rd.sum_frames(batch=2, into=fs) == nz and rd.last_batch_path == "device"
+    held.close()
+    assert any(taken) and np.array_equal(fs.fetch().astype(np.uint64), 2 * want) and want.any()
+    fs.close()
+    for rd in (a, b, ref):
+        rd.close()
+
+
 def test_trace_kernel_footprint():
     """k_expand_trace_b's descriptors in the built library (read the way test_gpu_frame_sums.py::test_sum_kernel_footprint reads its kernel's;
     no GPU needed, but the file's other tests do): both instantiations - with and without weights -, no scratch, and at most 81 920 B of static

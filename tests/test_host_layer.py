@@ -497,6 +497,157 @@ def test_drain_waits_only_for_a_queued_job(monkeypatch):
     assert waited == [4]
 
 
+def _recording_ladder(monkeypatch, dev, queued=0, wait=0, sync=0, queues=True, stock=True, host_decodes=True, slot_taken=False):
+    """The ladder of the 'sum' route family (BatchedAccess._offer / _settle) with a recording fake kind and a reader of fakes, over three
+    jobs of two frames: (the reader, the kind, the jobs, the log).  dev: the scheme the route offers under (None: never offered); queued,
+    wait, sync: the statuses the queued call, the verdict and the synchronous call under the FILE's geometry answer (the stored pieces'
+    calls, op_mode 0, always succeed); slot_taken: the queued call answers as when another reader holds the slot.  The file: 8 x 4,
+    12 bits, level 1, op_mode 1, scheme 2 - so (1, dev) marks a call on the file's bytes, (0, 2) one on host-decoded pieces and (0, 0)
+    one on _stored_pieces_per_frame's."""
+    from types import SimpleNamespace
+    from pyrecode_amd import _lib, reader_batched as rb
+    log = []
+    pieces, sizes0 = np.zeros(4, np.uint8), np.zeros((2, 3), np.uint32)
+
+    class Bare(rb.BatchedAccess):
+        _header = dict(nx=8, ny=4, target_bit_depth=12, reduction_level=1, rc_operation_mode=1, compression_scheme=2)
+        _foreign_file, last_batch_path, _ra, _user_iters = False, None, None, 0
+
+        def __init__(self):
+            self._bufs = SimpleNamespace(stream=[None] * 4, pin_blob=None)
+
+        def _close_ra_iter(self):
+            pass
+
+        def _note_batch_end(self, z):
+            pass
+
+        def _route_for(self, family, device_blosc=False, device_zlib=False):
+            assert family == 'sum'
+            return ('device', dev) if dev is not None else ('host-decode' if stock else 'per-frame', None)
+
+        def _batch_sizes(self, a, k, frames=None):
+            return np.zeros((k, 3), np.uint32), 16
+
+        def _read_batch_into(self, blob, z0, n, move_fp=True):
+            log.append(("read", (z0 - 10) // 2, blob.size))
+
+        def _host_decode_batch(self, blob, sizes, n, slot):
+            log.append(("host-decode", slot))
+            return (pieces, sizes0) if host_decodes else None
+
+        def _stored_pieces_per_frame(self, a, k, frames=None):
+            log.append(("frame by frame", a, k))
+            return (8, 4, 12, 1, 0, 0), pieces, sizes0
+    jobs = rb._jobs(10, 6, 2)
+
+    class Kind(rb._Kind):
+        what = "fake_call"
+        args = {}
+
+        def queues(self, level):
+            return queues
+
+        def room(self, job, geom, sizes, k):
+            log.append(("room", jobs.index(job)) + tuple(geom[4:]))
+
+        def call(self, job, geom, data, sizes, k, slot=None):
+            log.append(("call", jobs.index(job), "sync" if slot is None else "slot %d" % slot) + tuple(geom[4:]))
+            self.args.setdefault(jobs.index(job), []).append((geom, data.ctypes.data, sizes.ctypes.data, k))
+            assert tuple(geom[:4]) == (8, 4, 12, 1) and k == job.count == 2
+            return 0 if geom[4] == 0 else sync if slot is None else _lib.RC_ERR_BAD_ARG if slot_taken else queued
+
+        def item(self, job):
+            return "item %d" % jobs.index(job)
+
+    def wait_(job):
+        log.append(("wait", jobs.index(job)))
+        job.queued = False
+        return wait, np.zeros(job.count + 1, np.uint64)
+    monkeypatch.setattr(rb, "_pinned", lambda buf, nbytes: buf if buf is not None else SimpleNamespace(array=np.zeros(nbytes, np.uint8)))
+    monkeypatch.setattr(rb, "_wait", wait_)
+    monkeypatch.setattr(rb, "_stock_decoded", lambda h: stock)
+    monkeypatch.setattr(_lib, "last_error", lambda: "slot 0 holds a submitted batch" if slot_taken else "")
+    return Bare(), Kind(), jobs, log
+
+
+def test_the_ladder_of_the_sum_family_rung_by_rung(monkeypatch):
+    """One ladder for every kind of result of the 'sum' route family: which calls the kind receives - queued or synchronous, under which
+    geometry's (op_mode, scheme) -, last_batch_path and _foreign_file for every rung, in the streaming form (_ladder on _two_slots) and in
+    the synchronous one (what get_frames_dense uses)."""
+    from pyrecode_amd import _lib
+    UNS, BAD, DEVICE = _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT, _lib.RC_ERR_DEVICE
+    items = ["item 0", "item 1", "item 2"]
+
+    def calls(log, j=None):
+        return [e for e in log if e[0] in ("call", "host-decode", "frame by frame") and (j is None or e[1] == j or e[0] != "call")]
+    # queued, and the wait says OK: 'device'; the file bytes are read, then the output is sized, then the batch is offered, and job j + 1
+    # is offered before job j is waited for
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file, r._user_iters) == ("device", False, 0)
+    start = lambda j: [("read", j, 16), ("room", j, 1, 2), ("call", j, "slot %d" % (j & 1), 1, 2)]
+    assert log == start(0) + start(1) + [("wait", 0)] + start(2) + [("wait", 1), ("wait", 2)] and not any(j.queued for j in jobs)
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=_lib.RC_SCHEME_ZLIB_DEVICE)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("device-inflate", False)
+    # queued, the wait says UNSUPPORTED, the host decode delivers: the same call on the stored pieces, and the file is marked
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, wait=UNS)
+    gen = r._ladder(kind, jobs)
+    assert next(gen) == "item 0" and r._user_iters == 1
+    assert (r.last_batch_path, r._foreign_file) == ("host-decode + device-expand", True)
+    assert [e for e in log if e[1:2] == (0,) or e[0] == "host-decode"] == [
+        ("read", 0, 16), ("room", 0, 1, 2), ("call", 0, "slot 0", 1, 2), ("wait", 0), ("host-decode", 2), ("room", 0, 0, 2), ("call", 0, "sync", 0, 2)]
+    assert list(gen) == items[1:] and r._user_iters == 0 and not any(e[0] == "frame by frame" for e in log)
+    # the submit says CORRUPT, no stock decoder for the file: frame by frame, nothing waited for, the file is not marked
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, queued=BAD, stock=False)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("per-frame", False)
+    assert [e for e in log if e[1:2] == (1,) or e[0] == "frame by frame" and e[1] == 12] == [
+        ("read", 1, 16), ("room", 1, 1, 2), ("call", 1, "slot 1", 1, 2), ("frame by frame", 12, 2), ("room", 1, 0, 0), ("call", 1, "sync", 0, 0)]
+    assert not any(e[0] in ("wait", "host-decode") for e in log) and not any(j.queued for j in jobs)
+    # ... and a stock decoder that gives up leads to the same rung
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, wait=BAD, host_decodes=False)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("per-frame", False)
+    assert calls(log, 2)[-3:] == [("host-decode", 2), ("frame by frame", 14, 2), ("call", 2, "sync", 0, 0)]
+    # never offered, the host decode delivers: no call under the file's geometry, the file is not marked
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=None)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("host-decode + device-expand", False)
+    assert [e for e in log if e[0] != "read"] == [e for j in range(3) for e in (("host-decode", 2), ("room", j, 0, 2), ("call", j, "sync", 0, 2))]
+    # another reader holds the slot: one queued attempt, then the synchronous call with the same arguments, whose status is the verdict
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, slot_taken=True)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("device", False)
+    assert [e for e in log if e[0] != "read"] == [e for j in range(3) for e in (("room", j, 1, 2), ("call", j, "slot %d" % (j & 1), 1, 2), ("call", j, "sync", 1, 2))]
+    assert all(len(a) == 2 and a[0] == a[1] for a in kind.args.values()) and not any(j.queued for j in jobs)
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, slot_taken=True, sync=UNS)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("host-decode + device-expand", True)
+    # a kind that does not queue this level: no queued attempt at all
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, queues=False)
+    assert list(r._ladder(kind, jobs)) == items and r.last_batch_path == "device"
+    assert [e for e in log if e[0] == "call"] == [("call", j, "sync", 1, 2) for j in range(3)] and not any(e[0] == "wait" for e in log)
+    # a status outside OK / UNSUPPORTED / CORRUPT - of the submit, of the verdict, of the synchronous offer - raises, and no decoder is asked
+    for kw in (dict(queued=DEVICE), dict(wait=DEVICE), dict(sync=DEVICE, queues=False), dict(sync=DEVICE, slot_taken=True)):
+        r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, **kw)
+        with pytest.raises(_lib.RecodeHipError, match="fake_call_submit" if "queued" in kw else "rc_expand_frames_wait"):
+            list(r._ladder(kind, jobs))
+        assert r.last_batch_path is None and not r._foreign_file and r._user_iters == 0, kw
+        assert not any(e[0] in ("host-decode", "frame by frame") for e in log) and not any(j.queued for j in jobs), kw
+    # the synchronous form walks the same rungs, on the synchronous calls' blob and with no queued attempt
+    for kw, path, foreign, want in (
+            (dict(dev=2), "device", False, [("call", 0, "sync", 1, 2)]),
+            (dict(dev=_lib.RC_SCHEME_ZLIB_DEVICE), "device-inflate", False, [("call", 0, "sync", 1, _lib.RC_SCHEME_ZLIB_DEVICE)]),
+            (dict(dev=2, sync=UNS), "host-decode + device-expand", True, [("call", 0, "sync", 1, 2), ("host-decode", 2), ("call", 0, "sync", 0, 2)]),
+            (dict(dev=2, sync=BAD, stock=False), "per-frame", False, [("call", 0, "sync", 1, 2), ("frame by frame", 10, 2), ("call", 0, "sync", 0, 0)]),
+            (dict(dev=None), "host-decode + device-expand", False, [("host-decode", 2), ("call", 0, "sync", 0, 2)]),
+            (dict(dev=None, stock=False), "per-frame", False, [("frame by frame", 10, 2), ("call", 0, "sync", 0, 0)])):
+        r, kind, jobs, log = _recording_ladder(monkeypatch, **kw)
+        r._offer(kind, jobs[0], sync=True)
+        assert r._settle(kind, jobs[0], sync=True) == "item 0" and (r.last_batch_path, r._foreign_file) == (path, foreign), kw
+        assert calls(log) == want and r._bufs.pin_blob is not None and r._bufs.stream == [None] * 4 and not jobs[0].queued, kw
+    r, kind, jobs, log = _recording_ladder(monkeypatch, dev=2, sync=DEVICE)
+    r._offer(kind, jobs[0], sync=True)
+    with pytest.raises(_lib.RecodeHipError, match="fake_call: "):
+        r._settle(kind, jobs[0], sync=True)
+    assert calls(log) == [("call", 0, "sync", 1, 2)] and r.last_batch_path is None
+
+
 # (family, reduction level, operation mode, _foreign_file, then one string per (device_blosc, device_zlib) = (F, F), (F, T), (T, F), (T, T)
 # with one letter per compression scheme 0, 1, 2, 4, 5, 8): D = 'device' under the file's scheme, Z = 'device' under RC_SCHEME_ZLIB_DEVICE,
 # H = 'host-decode', P = 'per-frame'
