@@ -443,6 +443,29 @@ int rc_sum_add_counted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, u
 int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth,
                               uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                               uint32_t n, uint32_t method, uint32_t area_threshold);
+/* ---- aligned views: per-frame shifts applied while the device sums frames ------------------------------------
+ * A dose-fractionated movie is not summed as it lies: the specimen drifts, and every frame is translated by its measured drift before it is
+ * added.  The four calls below are the four adds above with one more argument:
+ *   shifts  int32[2 * n] in HOST memory: dy0, dx0, dy1, dx1, ... - frame f's translation.  What the unshifted call adds to cell (r, c) of the
+ *           view, the shifted call adds to (r + dy_f, c + dx_f); a contribution whose target lies outside the view is DROPPED - not wrapped,
+ *           not clamped, not an error.  Any int32 pair is legal (the cell is computed in 64 bits); a frame shifted wholly out adds nothing.
+ *           The array is copied before the call returns, the _submit forms included.  NULL: RC_ERR_BAD_ARG.
+ * Plain sums: cells are sensor pixels, shifts whole pixels (fractional shifts of plain sums are not offered: the cells would stop being
+ * exact integers).  Counted sums: cells are the fine grid's and shifts are in FINE cells (1 / upsample pixel) - the event is placed as by
+ * rc_sum_add_counted and then translated, which makes an integer shift a drift correction at 1 / upsample-pixel resolution.
+ * Unchanged by shifts: nnz_prefix / nev_prefix (the decoded set pixels or kept events per frame, placed or not), the growth of
+ * rc_sum_bound() (dropping only lowers a sum), every refusal and status code of the unshifted calls, and "a rejected batch adds NOTHING".
+ * All-zero shifts give, cell for cell, what the unshifted call gives; one handle takes shifted and unshifted adds. */
+int rc_sum_add_frames_shifted(rc_sum *s, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                              const uint32_t *sizes, uint32_t n, const int32_t *shifts, uint64_t *nnz_prefix);
+int rc_sum_add_frames_shifted_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                                     const uint8_t *data, const uint32_t *sizes, uint32_t n, const int32_t *shifts);
+int rc_sum_add_counted_shifted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t reduction_level,
+                               uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
+                               uint32_t area_threshold, const int32_t *shifts, uint64_t *nev_prefix);
+int rc_sum_add_counted_shifted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth,
+                                      uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
+                                      uint32_t n, uint32_t method, uint32_t area_threshold, const int32_t *shifts);
 /* ---- dense frame batches: a region of every frame as an array, written on the device ----------------------------
  * What ReCoDeReader.get_sub_volume would return in the reference, where it is a stub (pyrecode/recode_reader.py:185-186), and what its
  * callers do instead with every frame on the host - frame.toarray(), a memset and a scatter (pyrecode/utils/viewer.py:65-68): a batch is

@@ -24,6 +24,7 @@ RC_SCHEME_ZLIB_DEVICE = 0x100   # compression_scheme 0 records from the device's
 
 # every symbol include/recode_hip.h declares: (restype, argtypes)
 _u8p, _u16p, _u32p, _u64p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p  # raw addresses: host or device
+_i32p = C.c_void_p
 SIGNATURES = {
     "rc_abi_version": (C.c_int, []),
     "rc_strerror": (C.c_char_p, [C.c_int]),
@@ -85,6 +86,10 @@ SIGNATURES = {
     "rc_sum_add_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32]),
     "rc_sum_add_counted": (C.c_int, [C.c_void_p] + [C.c_uint32] * 7 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_u64p]),
     "rc_sum_add_counted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 8 + [_u8p, _u32p] + [C.c_uint32] * 3),
+    "rc_sum_add_frames_shifted": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, _i32p, _u64p]),
+    "rc_sum_add_frames_shifted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, _i32p]),
+    "rc_sum_add_counted_shifted": (C.c_int, [C.c_void_p] + [C.c_uint32] * 7 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_i32p, _u64p]),
+    "rc_sum_add_counted_shifted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 8 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_i32p]),
     "rc_sum_fetch": (C.c_int, [C.c_void_p, _u32p, C.c_int]),
     "rc_sum_bound": (C.c_uint64, [C.c_void_p]),
     "rc_trace_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
@@ -173,6 +178,19 @@ def ptr(a):
     return int(a)
 
 
+def shift_rows(shifts, n=None, what="shifts"):
+    """Per-frame shifts as the aligned adds take them: an integer array-like of shape (n, 2), (dy, dx) per frame -> C-contiguous int32[n, 2].
+    A float (or any non-integer) dtype, another shape and a value outside int32 are ValueError: nothing is rounded or wrapped silently."""
+    a = np.asarray(shifts)
+    if a.dtype.kind not in "iu":
+        raise ValueError("%s: an integer array of (dy, dx) rows, not dtype %s (round the shifts yourself)" % (what, a.dtype))
+    if a.ndim != 2 or a.shape[1] != 2 or (n is not None and a.shape[0] != int(n)):
+        raise ValueError("%s: shape %s, wanted (%s, 2)" % (what, a.shape, "n" if n is None else int(n)))
+    if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) > (1 << 31) - 1):
+        raise ValueError("%s: a value outside int32" % what)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 PIPE_SLOTS = 3
 
 
@@ -241,6 +259,41 @@ class FrameSum:
     def submit(self, slot, geom, data, sizes, n):
         """Queue the batch on slot 0 or 1 (data stays valid until rc_expand_frames_wait(slot) has returned, which gives the verdict)."""
         check(self.submit_status(slot, geom, data, sizes, n), "rc_sum_add_frames_submit")
+
+    # ---- aligned views (rc_sum_add_frames_shifted): frame f lands shifts[f] = (dy, dx) cells away, what leaves the view is dropped -----------
+    def add_shifted_status(self, geom, data, sizes, n, shifts, prefix=None):
+        """rc_sum_add_frames_shifted, status returned; shifts: int32[n, 2] (shift_rows)"""
+        return lib().rc_sum_add_frames_shifted(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(shift_rows(shifts, n)), ptr(prefix))
+
+    def add_shifted(self, geom, data, sizes, n, shifts):
+        """add() with frame f translated by shifts[f] = (dy, dx) whole pixels; the prefix counts the frames' set pixels, placed or not"""
+        prefix = np.zeros(n + 1, np.uint64)
+        check(self.add_shifted_status(geom, data, sizes, n, shifts, prefix), "rc_sum_add_frames_shifted")
+        return prefix
+
+    def submit_shifted_status(self, slot, geom, data, sizes, n, shifts):
+        """rc_sum_add_frames_shifted_submit (the library copies the shifts before it returns)"""
+        return lib().rc_sum_add_frames_shifted_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(shift_rows(shifts, n)))
+
+    def submit_shifted(self, slot, geom, data, sizes, n, shifts):
+        check(self.submit_shifted_status(slot, geom, data, sizes, n, shifts), "rc_sum_add_frames_shifted_submit")
+
+    def add_counted_shifted_status(self, geom, data, sizes, n, shifts, method=0, area_threshold=0, upsample=1, prefix=None):
+        """rc_sum_add_counted_shifted, status returned; shifts in FINE cells (1 / upsample pixel)"""
+        return lib().rc_sum_add_counted_shifted(self._h, *self._codec_counted(geom, upsample), ptr(data), ptr(sizes), n, int(method), int(area_threshold),
+                                                ptr(shift_rows(shifts, n)), ptr(prefix))
+
+    def add_counted_shifted(self, geom, data, sizes, n, shifts, method=0, area_threshold=0, upsample=1):
+        """add_counted() with frame f's counts translated by shifts[f] = (dy, dx) fine cells; the prefix counts the kept events, placed or not"""
+        prefix = np.zeros(n + 1, np.uint64)
+        check(self.add_counted_shifted_status(geom, data, sizes, n, shifts, method, area_threshold, upsample, prefix), "rc_sum_add_counted_shifted")
+        return prefix
+
+    def submit_counted_shifted_status(self, slot, geom, data, sizes, n, shifts, method=0, area_threshold=0, upsample=1):
+        """rc_sum_add_counted_shifted_submit on slot 0 or 1"""
+        nx, ny, s, *codec = self._codec_counted(geom, upsample)
+        return lib().rc_sum_add_counted_shifted_submit(self._h, slot, nx, ny, s, *codec, ptr(data), ptr(sizes), n, int(method), int(area_threshold),
+                                                       ptr(shift_rows(shifts, n)))
 
     # ---- counted views (rc_sum_add_counted): one count per event of the frames, on a grid `upsample` times finer than theirs --------------
     def _codec_counted(self, geom, upsample):

@@ -110,9 +110,11 @@ void launch_count_events(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, ui
 // added to view[frow * (upsample * nx) + fcol] (cnt_finish_fine; view_cells = (upsample * nx) * (upsample * ny) uint32 cells, zero
 // or more counts in them already).  No event is written anywhere; the frames' event prefix lies at cnt_ev_base as above.  order: the
 // adding kernel waits for this event and records it again (the handle's adds, whichever stream they come from, are one sequence).
+// shifts (device memory, int32[2 * n], NULL: none): frame f's counts land (shifts[2 * f], shifts[2 * f + 1]) = (dy, dx) cells of the view away,
+// those that leave it are dropped (rc_sum_add_counted_shifted).
 void launch_count_place(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                         const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level,
                         uint32_t method, uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, uint32_t *view, uint64_t view_cells,
-                        uint32_t upsample, hipEvent_t order, int *err, hipStream_t s);
+                        uint32_t upsample, hipEvent_t order, int *err, hipStream_t s, const int32_t *shifts = nullptr);
 }  // namespace rc
 #endif

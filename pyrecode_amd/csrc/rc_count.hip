@@ -51,6 +51,7 @@ struct CntArgs {
     uint32_t *view;                // counted views: the caller's cells, a grid `up` times finer than the frame (NULL: events)
     uint64_t view_cells;
     uint32_t up;
+    const int32_t *shifts;         // aligned views: frame f's (dy, dx) in cells of the view at [2 * f], [2 * f + 1] (NULL: none)
     int *err;
 };
 
@@ -331,7 +332,8 @@ __global__ __launch_bounds__(WG) void k_cnt_emit(CntArgs A)
 // (cnt_finish_fine) and counted into its cell with one 32-bit no-return atomic - the cells belong to the caller's handle, other batches
 // and earlier calls have added to them, and several components of a frame may share one (a ring around a dot).  The block's number of
 // events goes to ev_cnt for the frames' event prefix.  A centroid lies inside its frame, so a cell inside the view (cnt_place); an
-// index that did not would be dropped, not written.
+// index that did not would be dropped, not written.  With shifts (rc_sum_add_counted_shifted) the cell is translated by the frame's (dy, dx)
+// fine cells, in 64 bits - any int32 pair is legal -, and a count that leaves the view is dropped; the block's number of events is not.
 template <uint32_t M>
 __global__ __launch_bounds__(WG) void k_cnt_place(CntArgs A)
 {
@@ -353,6 +355,11 @@ __global__ __launch_bounds__(WG) void k_cnt_place(CntArgs A)
         const uint32_t id = id0 + (uint32_t)__builtin_popcountll(w & ((1ull << b) - 1ull));
         uint32_t frow, fcol;
         cnt_finish_fine(M, cnt_sums<M>(A, id), A.nx, A.up, &frow, &fcol);
+        if (A.shifts) {
+            const int64_t row = (int64_t)frow + A.shifts[2 * f], col = (int64_t)fcol + A.shifts[2 * f + 1];
+            if (row >= 0 && col >= 0 && col < (int64_t)fnx && row < (int64_t)(A.view_cells / fnx)) (void)atomicAdd(A.view + (uint64_t)row * fnx + (uint64_t)col, 1u);
+            continue;
+        }
         const uint64_t cell = frow * fnx + fcol;
         if (fcol < fnx && cell < A.view_cells) (void)atomicAdd(A.view + cell, 1u);
     }
@@ -405,7 +412,7 @@ namespace {
 void cnt_run(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
              const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level, uint32_t method,
              uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, void *events, uint64_t cap, uint32_t *view, uint64_t view_cells,
-             uint32_t upsample, hipEvent_t order, int *err, hipStream_t s)
+             uint32_t upsample, const int32_t *shifts, hipEvent_t order, int *err, hipStream_t s)
 {
     const CntLayout L = cnt_layout(nb8, n, id_cap, method);
     uint64_t *ev_nnz = reinterpret_cast<uint64_t *>(workspace), *ev_base = cnt_ev_base(workspace, n);
@@ -425,6 +432,7 @@ void cnt_run(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, ui
     A.ev_off = ev_off; A.ev_base = ev_base;
     A.cap = cap; A.events = events;
     A.view = view; A.view_cells = view_cells; A.up = upsample;
+    A.shifts = shifts;
     A.err = err;
     (void)hipMemsetAsync(workspace + L.o_sums, 0, L.o_evoff - L.o_sums, s);
     if (method == CNT_WEIGHTED) cnt_launch<CNT_WEIGHTED>(A, nb8, ev_nnz, ev_base, ev_off, order, s);
@@ -439,16 +447,16 @@ void launch_count_events(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, ui
                          hipStream_t s)
 {
     cnt_run(bm, bm_stride, nb8, N, nx, n, blk_off, frame_base, pv, pv_stride, pv_bytes, d, level, method, area_threshold, workspace, id_cap, events, cap,
-            nullptr, 0, 1, nullptr, err, s);
+            nullptr, 0, 1, nullptr, nullptr, err, s);
 }
 
 void launch_count_place(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                         const uint64_t *frame_base, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level,
                         uint32_t method, uint32_t area_threshold, uint8_t *workspace, uint64_t id_cap, uint32_t *view, uint64_t view_cells,
-                        uint32_t upsample, hipEvent_t order, int *err, hipStream_t s)
+                        uint32_t upsample, hipEvent_t order, int *err, hipStream_t s, const int32_t *shifts)
 {
     cnt_run(bm, bm_stride, nb8, N, nx, n, blk_off, frame_base, pv, pv_stride, pv_bytes, d, level, method, area_threshold, workspace, id_cap, nullptr, 0,
-            view, view_cells, upsample, order, err, s);
+            view, view_cells, upsample, shifts, order, err, s);
 }
 
 }  // namespace rc

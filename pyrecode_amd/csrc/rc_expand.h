@@ -1,6 +1,7 @@
 // rc_expand.h - launchers of rc_expand.hip
 #pragma once
 #include "rc_device.h"
+#include "rc_shift.h"
 
 namespace rc {
 // ---- what the kernels of rc_expand.hip and rc_count.hip read a decoded frame with ----------------------------------------------------
@@ -86,6 +87,11 @@ void launch_expand_batch_emit(const uint8_t *bm, uint64_t bm_stride, uint64_t nb
 // launch_expand_batch_count on the same stream (blk_off, and *err as the gate: nothing is added once it is set)
 void launch_expand_batch_sum(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t n, const uint32_t *blk_off, const uint8_t *pv,
                              uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level, uint32_t *acc, const int *err, hipStream_t s);
+// the same with frame f added (shifts[2 * f], shifts[2 * f + 1]) = (dy, dx) pixels away, what leaves the ny x nx view dropped (k_sum_shift; shifts:
+// device memory, frame_nnz: the count pass's per-frame totals)
+void launch_expand_batch_sum_shifted(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t ny, uint32_t n,
+                                     const uint32_t *blk_off, const uint64_t *frame_nnz, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes,
+                                     uint32_t d, uint32_t level, const int32_t *shifts, uint32_t *acc, const int *err, hipStream_t s);
 // rc_zstd_dec.hip: block decoders of the batched reader
 void launch_block_decode(int codec, int row, const uint8_t *data, const void *frame_lists, uint32_t nframes, uint32_t max_blocks_per_frame,
                          const void *tables, const void *predef, uint8_t *out, const uint64_t *out_base, int *err, hipStream_t s,

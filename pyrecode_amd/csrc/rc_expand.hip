@@ -315,6 +315,104 @@ void launch_expand_batch_sum(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8
                        per_group, acc, err);
 }
 
+// ---- aligned sums (rc_sum_add_frames_shifted): frame f is added (dy_f, dx_f) away from where it was recorded -----------------------------
+// k_expand_sum_b's structure - the LDS cells and their layout, the flush, the frame groups -, but the workgroup owns a block of 16 384 OUTPUT
+// pixels and GATHERS: output word i of frame f is the 64 source bits from bit 64 * i - s_f on (rc_shift.h), two neighbouring source words
+// funnel-shifted by an amount that is the same for the whole workgroup, with the bits whose column came from the neighbouring row masked
+// off.  Thread t stays the only writer of its word's cells, and frames with different shifts meet in LDS: no global atomic more than the
+// unshifted sum issues.
+// A set bit's value is the field at its SOURCE rank.  The workgroup's WG source words start at word a0 and straddle at most two of the
+// count pass's blocks; one scan over popcount(word a0 + t) ranks them relative to a0, and the absolute rank of a0 comes from the first block
+// boundary at or behind it - blk_off there (0 before the frame, the frame's total behind it) minus the scan's value at the thread that
+// holds the boundary word.  A masked-off bit still consumes a rank: the rank inside the window is a popcount of the UNMASKED window below
+// the bit.  Levels 2 and 3 add 1 per set bit and need neither scan nor barrier.
+struct ShiftWin {
+    uint64_t w0, w1;     // source words a0 + t and the one behind it
+    int64_t q;           // a0 - blockIdx.x * WG
+    uint32_t sh;
+    int32_t dx;
+    bool in;             // anything of the frame survives (uniform)
+};
+__device__ __forceinline__ ShiftWin shift_fetch(const uint8_t *__restrict__ fbm, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t ny, uint64_t i,
+                                                const int32_t *__restrict__ shifts, uint32_t f)
+{
+    ShiftWin W;
+    const int32_t dy = shifts[2 * f];
+    W.dx = shifts[2 * f + 1];
+    W.w0 = W.w1 = 0; W.q = 0; W.sh = 0;
+    W.in = shift_in_view(dy, W.dx, nx, ny);
+    if (!W.in) return W;
+    shift_funnel(shift_offset(dy, W.dx, nx), &W.q, &W.sh);
+    const int64_t a = (int64_t)i + W.q;                              // (signed: a window may start before the frame)
+    if (a >= 0) W.w0 = expand_word(fbm, nb8, N, (uint64_t)a);
+    if (W.sh && a + 1 >= 0) W.w1 = expand_word(fbm, nb8, N, (uint64_t)(a + 1));
+    return W;
+}
+__global__ __launch_bounds__(WG) void k_sum_shift(const uint8_t *__restrict__ bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t ny,
+                                                    uint32_t nblk, const uint32_t *__restrict__ blk_off, const uint64_t *__restrict__ frame_nnz,
+                                                    const uint8_t *__restrict__ pv, uint64_t pv_stride, const uint32_t *__restrict__ pv_bytes, uint32_t d,
+                                                    uint32_t level, uint32_t n, uint32_t per_group, const int32_t *__restrict__ shifts,
+                                                    uint32_t *__restrict__ acc, const int *__restrict__ err)
+{
+    __shared__ uint32_t sm[WAVES + 1];
+    __shared__ uint32_t s_anchor;
+    __shared__ uint32_t cell[64 * SUM_ROW];
+    if (*err) return;   // (workgroup-uniform, as in k_expand_sum_b)
+    const uint32_t t = threadIdx.x;
+    for (uint32_t b = 0; b < 64; ++b) cell[b * SUM_ROW + t] = 0;     // (its own cells: no barrier before the loop)
+    const uint32_t f0 = blockIdx.y * per_group, f1 = min(n, f0 + per_group);
+    const uint64_t i = (uint64_t)blockIdx.x * WG + t;               // OUTPUT word
+    const uint32_t c0 = (uint32_t)((i * 64) % nx);                   // column of its first pixel: the one division
+    const uint32_t dmask = level == 1 ? (1u << d) - 1u : 0u;
+    ShiftWin next = f0 < f1 ? shift_fetch(bm + f0 * bm_stride, nb8, N, nx, ny, i, shifts, f0) : ShiftWin{};
+    for (uint32_t f = f0; f < f1; ++f) {
+        const ShiftWin W = next;
+        if (f + 1 < f1) next = shift_fetch(bm + (f + 1) * bm_stride, nb8, N, nx, ny, i, shifts, f + 1);   // (in flight across this frame's barriers)
+        if (!W.in) continue;                                         // (uniform)
+        const uint64_t win = shift_window(W.w0, W.w1, W.sh);
+        uint64_t keep = win & shift_col_mask(c0, nx, W.dx);
+        if (level != 1) {
+            for (; keep; keep &= keep - 1) cell[(uint32_t)__builtin_ctzll(keep) * SUM_ROW + t] += 1u;
+            continue;
+        }
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan((uint32_t)__builtin_popcountll(W.w0), sm, &tot);
+        // the first block boundary at or behind a0, and the thread whose word w0 it is
+        const int64_t a0 = (int64_t)blockIdx.x * WG + W.q;
+        const int64_t bc = a0 >= 0 ? (a0 + WG - 1) / WG : -((-a0) / WG);
+        const uint32_t t1 = (uint32_t)(bc * WG - a0);
+        if (t == t1) s_anchor = ex;
+        __syncthreads();             // (the next frame writes s_anchor behind its scan's barriers)
+        if (!keep) continue;
+        const uint32_t at_bc = bc <= 0 ? 0u : bc >= (int64_t)nblk ? (uint32_t)frame_nnz[f] : blk_off[(uint64_t)f * nblk + (uint64_t)bc];
+        const uint32_t rank0 = at_bc - s_anchor + ex + (uint32_t)__builtin_popcountll(W.w0 & ((1ull << W.sh) - 1ull));
+        const uint8_t *pix = pv + f * pv_stride;
+        const uint64_t pix_bytes = pv_bytes[f];
+        for (; keep; keep &= keep - 1) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(keep);
+            const uint64_t rank = (uint64_t)rank0 + (uint32_t)__builtin_popcountll(win & ((1ull << b) - 1ull));
+            cell[b * SUM_ROW + t] += expand_field16(pix, pix_bytes, rank, d, dmask);
+        }
+    }
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * WG * 64;
+    for (uint32_t j = 0; j < 64; ++j) {
+        const uint32_t q = j * WG + t;                               // pixel of the block: word q >> 6 (uniform in a wave), bit = lane
+        const uint32_t v = cell[(q & 63u) * SUM_ROW + (q >> 6)];
+        if (v && p0 + q < N) (void)atomicAdd(acc + p0 + q, v);
+    }
+}
+void launch_expand_batch_sum_shifted(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t ny, uint32_t n,
+                                     const uint32_t *blk_off, const uint64_t *frame_nnz, const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes,
+                                     uint32_t d, uint32_t level, const int32_t *shifts, uint32_t *acc, const int *err, hipStream_t s)
+{
+    const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
+    uint32_t per_group = 1;
+    const uint32_t groups = expand_sum_groups(nb8, n, &per_group);
+    hipLaunchKernelGGL(k_sum_shift, dim3(nblk, groups), dim3(WG), 0, s, bm, bm_stride, nb8, N, nx, ny, nblk, blk_off, frame_nnz, pv, pv_stride, pv_bytes, d,
+                       level, n, per_group, shifts, acc, err);
+}
+
 // ---- level-2 statistics of a batch (rc_expand_frames_l2): frame f's decoded statistics stream at pv + f * pv_stride -> its
 // floor(8 * pv_bytes[f] / d) fields as uint16 at out + st_base[f].  Replaces the reader's host-side unpack (recode_reader.py:473-481 with
 // the intended semantics of c_extensions/reader.h:74-99) for every frame of the batch at once.  One thread per field, 8 <= d <= 16: a

@@ -142,6 +142,9 @@ static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, ui
 // EVENT prefix).  A level-2 file's statistics stream is stepped over, as for the sum.
 // cnt and sum together (rc_sum_add_counted / _submit): no event array either - the counting kernels end in k_cnt_place, which adds one
 // count per event to the handle's cells, a grid cnt->upsample times finer than the frame (nx, ny are the FRAME's; triplets NULL, cap 0).
+// shifts (rc_sum_add_frames_shifted, rc_sum_add_counted_shifted and their _submit forms; with sum only): the caller's int32 (dy, dx) per frame.  They are
+// copied into the slot's page-locked head before anything is queued - the caller may reuse its array once the call has returned - and
+// reach the device with the head's one copy; k_sum_shift (rc_expand.hip) or k_cnt_place then adds frame f that far from where it lies.
 // dense (rc_expand_frames_dense / _submit): no entries either - behind the count, k_expand_dense_b (rc_dense.hip) writes a region of every frame as
 // an array of cells (`triplets` = the output, cap = its cells, at least n * w * h of cell_bytes bytes: the entry points have checked it).
 // trace (rc_trace_frames / _submit): no entries either - behind the count, the kernels of rc_trace.hip write 4 + k int64 sums per frame
@@ -153,7 +156,7 @@ struct TraceReq { const int32_t *weights; uint32_t k; };   // (rc_trace_frames: 
 static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                       const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
                       bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr,
-                      const DenseReq *dense = nullptr, const TraceReq *trace = nullptr)
+                      const DenseReq *dense = nullptr, const TraceReq *trace = nullptr, const int32_t *shifts = nullptr)
 {
     const uint64_t esz = cnt ? 20 : l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
     using namespace rc;
@@ -223,7 +226,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const uint64_t ntab = codec == EMIT_ZSTD ? 2 * (uint64_t)n : 0;
     const uint64_t o_first = ntab * sizeof(ZdTables);
     const uint64_t o_base2 = (o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList) + (uint64_t)n * 4 + 15) & ~15ull;
-    const uint64_t sz_head = o_base2 + (uint64_t)n * 5 * 8;
+    const uint64_t o_shift = o_base2 + (uint64_t)n * 5 * 8;                 // [shifts 2n int32] behind them, for a shifted add only
+    const uint64_t sz_head = o_shift + (shifts ? (uint64_t)n * 8 : 0);
     if ((r = u.d_data.ensure(U.dmem, total_in + 64)) != RC_OK || (r = u.d_streams.ensure(U.dmem, out_bytes)) != RC_OK ||
         (r = u.d_head.ensure(U.dmem, sz_head)) != RC_OK ||
         (r = u.d_counters.ensure(U.dmem, (uint64_t)n * nblk * 8 + (uint64_t)(2 * n + 2) * 8 + 64)) != RC_OK ||
@@ -267,6 +271,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     ZdFrameList *cbm_list = raw_list + RC_READ_THREADS;
     uint32_t *pv_bytes = reinterpret_cast<uint32_t *>(cbm_list + n);
     uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head.p + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n, *st_base = src_base + n;
+    if (shifts) memcpy(u.rd_head.p + o_shift, shifts, (size_t)n * 8);
     // c0, c_n: the frame's range in its thread's compact offset list (c_n blocks = c_n + 1 offsets); c_skips: tree_skip | seq_skip << 8
     struct FrameIndex { uint32_t bm0 = 0, bm_n = 0, pv0 = 0, pv_n = 0, thread = 0, c0 = 0, c_n = 0, c_skips = 0; int status = ZD_OK; const char *what = nullptr; };
     std::vector<FrameIndex> fi(n);
@@ -416,6 +421,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     const ZdFrameList *d_cbm_list = d_raw_list + RC_READ_THREADS;
     uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.d_head.p + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
     uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.d_head.p + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n, *d_st_base = d_src_base + n;
+    const int32_t *d_shifts = shifts ? reinterpret_cast<const int32_t *>(u.d_head.p + o_shift) : nullptr;
     HIP_TRY(hipMemcpyAsync(u.d_head.p, u.rd_head.p, sz_head, hipMemcpyHostToDevice, s));
     const double t_3 = now();
     // the value streams' chunks (few, long serial chains) decode next to the binary maps' blocks (many, short), on a second stream
@@ -519,7 +525,7 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         }
         if (sum)
             launch_count_place(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
-                               cnt->area_threshold, u.d_count.p, id_cap, sum->acc, (uint64_t)sum->nx * sum->ny, cnt->upsample, sum->ev, d_err, s);
+                               cnt->area_threshold, u.d_count.p, id_cap, sum->acc, (uint64_t)sum->nx * sum->ny, cnt->upsample, sum->ev, d_err, s, d_shifts);
         else
             launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
                                 cnt->area_threshold, u.d_count.p, id_cap, events, cap, d_err, s);
@@ -615,7 +621,11 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (sum) {
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
         HIP_TRY(hipStreamWaitEvent(s, sum->ev, 0));
-        launch_expand_batch_sum(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, sum->acc, d_err, s);
+        if (d_shifts)
+            launch_expand_batch_sum_shifted(d_bm, bm_stride, nb8, N, nx, ny, n, d_blk_off, d_fnnz, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, d_shifts,
+                                            sum->acc, d_err, s);
+        else
+            launch_expand_batch_sum(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, sum->acc, d_err, s);
         HIP_TRY(hipEventRecord(sum->ev, s));
     } else if (dev_out) {
         launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, cap, d_err);
@@ -959,6 +969,40 @@ RC_EXPORT int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_de
     return r;
 }
 
+// ---- aligned views: the same adds with frame f translated by (shifts[2 * f], shifts[2 * f + 1]) = (dy, dx) cells of the view ---------------
+// Everything the unshifted calls check is checked as they check it, in their order; the shifts themselves cannot be wrong (any int32 pair
+// is legal), only missing.  The bound grows as for the unshifted add: dropping only lowers a sum.
+RC_EXPORT int rc_sum_add_frames_shifted(rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                        const uint32_t *sizes, uint32_t n, const int32_t *shifts, uint64_t *nnz_prefix)
+{
+    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted: shifts is NULL");
+    uint64_t grow = 0;
+    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
+    if (r == RC_OK) r = sum_on_its_device(s);
+    if (r != RC_OK) return r;
+    std::vector<uint64_t> own;
+    if (!nnz_prefix) { own.resize((size_t)n + 1); nnz_prefix = own.data(); }
+    r = expand_run(RC_READ_SLOTS, false, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, nullptr, 0, 0, false, nullptr, 0, s, nullptr,
+                   nullptr, nullptr, shifts);
+    if (r == RC_OK) s->bound += grow;
+    return r;
+}
+
+RC_EXPORT int rc_sum_add_frames_shifted_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                               const uint8_t *data, const uint32_t *sizes, uint32_t n, const int32_t *shifts)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted_submit: slot 0 or 1");
+    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted_submit: shifts is NULL");
+    uint64_t grow = 0;
+    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
+    if (r == RC_OK) r = sum_on_its_device(s);
+    if (r != RC_OK) return r;
+    r = expand_run(slot, true, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, nullptr, nullptr,
+                   nullptr, shifts);
+    if (r == RC_OK) s->bound += grow;      // (queued: as rc_sum_add_frames_submit)
+    return r;
+}
+
 RC_EXPORT int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset)
 {
     if (!s || !dst) return fail(RC_ERR_BAD_ARG, "rc_sum_fetch: NULL argument");
@@ -1025,6 +1069,40 @@ RC_EXPORT int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, u
     const CountReq req{method, area_threshold, upsample};
     r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req);
     if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
+    return r;
+}
+
+// the counted adds with shifts in FINE cells (1 / upsample pixel): the event is placed as above and then translated
+RC_EXPORT int rc_sum_add_counted_shifted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
+                                         uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold,
+                                         const int32_t *shifts, uint64_t *nev_prefix)
+{
+    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted: shifts is NULL");
+    uint64_t grow = 0;
+    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
+    if (r != RC_OK) return r;
+    std::vector<uint64_t> own;
+    if (!nev_prefix) { own.resize((size_t)n + 1); nev_prefix = own.data(); }
+    const CountReq req{method, area_threshold, upsample};
+    r = expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, nullptr, 0, 0, false, nullptr, 0, s, &req, nullptr,
+                   nullptr, shifts);
+    if (r == RC_OK) s->bound += grow;
+    return r;
+}
+
+RC_EXPORT int rc_sum_add_counted_shifted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level,
+                                                uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
+                                                uint32_t area_threshold, const int32_t *shifts)
+{
+    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted_submit: slot 0 or 1");
+    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted_submit: shifts is NULL");
+    uint64_t grow = 0;
+    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
+    if (r != RC_OK) return r;
+    const CountReq req{method, area_threshold, upsample};
+    r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req, nullptr, nullptr,
+                   shifts);
+    if (r == RC_OK) s->bound += grow;      // (queued: as rc_sum_add_counted_submit)
     return r;
 }
 

@@ -223,6 +223,51 @@ class _CountedAdder(_PlainAdder):
         return fs.add_counted_status(geom, data, sizes, k, *how) if slot is None else fs.submit_counted_status(slot, geom, data, sizes, k, *how)
 
 
+class _ShiftedPlainAdder(_PlainAdder):
+    """_PlainAdder with per-frame shifts (rc_sum_add_frames_shifted / _submit): shifts is int32[n, 2] for frames z0 .. z0 + n - 1 of the call,
+    and every rung of the ladder - the device decoders, the host-decoded batch, the per-frame restatement - makes this call, with the rows of
+    the job's frames."""
+    what = 'rc_sum_add_frames_shifted'
+
+    def __init__(self, z0, shifts):
+        self.z0, self.shifts = int(z0), shifts
+
+    def rows(self, job):
+        a = job.first - self.z0
+        return self.shifts[a:a + job.count]
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        fs, rows = job.payload.fs, self.rows(job)
+        return fs.add_shifted_status(geom, data, sizes, k, rows) if slot is None else fs.submit_shifted_status(slot, geom, data, sizes, k, rows)
+
+
+class _ShiftedCountedAdder(_CountedAdder):
+    """_CountedAdder with per-frame shifts in fine cells (rc_sum_add_counted_shifted / _submit), on every rung like _ShiftedPlainAdder"""
+    what = 'rc_sum_add_counted_shifted'
+    rows = _ShiftedPlainAdder.rows
+
+    def __init__(self, method, area_threshold, upsample, z0, shifts):
+        super().__init__(method, area_threshold, upsample)
+        self.z0, self.shifts = int(z0), shifts
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        fs, rows, how = job.payload.fs, self.rows(job), (self.code, self.thr, self.s)
+        if slot is None:
+            return fs.add_counted_shifted_status(geom, data, sizes, k, rows, *how)
+        return fs.submit_counted_shifted_status(slot, geom, data, sizes, k, rows, *how)
+
+
+def _plain_adder(z0, n, shifts):
+    """the adder of sum_frames / iter_frame_sums: today's without shifts, the shifted one with (shifts checked against the n frames)"""
+    return _PlainAdder() if shifts is None else _ShiftedPlainAdder(z0, _lib.shift_rows(shifts, n))
+
+
+def _counted_adder(method, area_threshold, upsample, z0, n, shifts):
+    if shifts is None:
+        return _CountedAdder(method, area_threshold, upsample)
+    return _ShiftedCountedAdder(method, area_threshold, upsample, z0, _lib.shift_rows(shifts, n))
+
+
 class _Events(_Kind):
     """A batch's events (rc_count_frames / _submit): level 1 bounds them from the sizes and is queued, its output the slot's; levels 2 and
     3 have no bound short of their pixels and go through the synchronous call, which counts first (count_frames_now)."""
@@ -1238,7 +1283,7 @@ class BatchedAccess:
                 for w, (a, k, fs) in enumerate(windows) for b in range(a, a + k, batch)]
         return self._ladder(adder, jobs)
 
-    def sum_frames(self, z0=0, n=None, batch=64, into=None):
+    def sum_frames(self, z0=0, n=None, batch=64, into=None, shifts=None):
         """The sum of frames z0 .. z0+n-1 of a merged file (records of a part file) as uint64[ny, nx] - what the reference's viewer and its
         own read test build one get_next_frame at a time (utils/viewer.py:65-68, tests/recode_v1_read_test.py:9-21) -, added up ON THE
         DEVICE (rc_sum_add_frames_submit / rc_expand_frames_wait, two batches in flight: the next batch's bytes are read from the file while
@@ -1252,10 +1297,13 @@ class BatchedAccess:
         batches' share early.
         Routes, per batch (last_batch_path): the device decoders ("device", "device-inflate"); for streams they refuse and for host-only
         schemes the stock decoders on the thread pool, then one add of the stored pieces ("host-decode + device-expand"); what is left
-        goes through the frame-at-a-time reader ("per-frame").  Files of more than 16 bits are not taken (NotImplementedError)."""
+        goes through the frame-at-a-time reader ("per-frame").  Files of more than 16 bits are not taken (NotImplementedError).
+        shifts: None, or an integer array-like of shape (n, 2) - (dy, dx) whole pixels for frames z0 .. z0 + n - 1: what frame f adds to
+        pixel (r, c) it then adds to (r + dy_f, c + dx_f), and what leaves the view is dropped (rc_sum_add_frames_shifted, on every route).
+        A float dtype, another shape or a value outside int32 is a ValueError."""
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
-        return self._sum_into(z0, n, batch, into, _PlainAdder())
+        return self._sum_into(z0, n, batch, into, _plain_adder(z0, n, shifts))
 
     def _sum_into(self, z0, n, batch, into, adder):
         """sum_frames and sum_frames_counted behind their argument checks"""
@@ -1288,17 +1336,18 @@ class BatchedAccess:
         if level == 1 and d > 16:
             raise NotImplementedError('sum_frames: files of more than 16 bits (target_bit_depth %d): the cells of a summed view are uint32' % d)
 
-    def iter_frame_sums(self, frames_per_view, z0=0, n=None, batch=64):
+    def iter_frame_sums(self, frames_per_view, z0=0, n=None, batch=64, shifts=None):
         """Views of `frames_per_view` consecutive frames each (the last one of what is left): yields (first index, count, uint32[ny, nx]) -
         a loop over sum_frames' engine with two device views that alternate: all windows' batches form one sequence on the two slots, so
         the next window's first batch is read and queued - into the other view - before this window's image is fetched.  One thread does
         it all.  The image is a VIEW of page-locked memory the device copied into, valid until the generator is advanced (copy it to keep
-        it), like the batches of iter_frames_triplets.  A window whose sum could pass 2^32 - 1 raises ValueError."""
+        it), like the batches of iter_frames_triplets.  A window whose sum could pass 2^32 - 1 raises ValueError.
+        shifts: as for sum_frames, one (dy, dx) row per frame of z0 .. z0 + n - 1 - the aligned views of a drifting series."""
         if frames_per_view <= 0 or batch <= 0:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
-        yield from self._iter_sums(frames_per_view, z0, n, batch, _PlainAdder())
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _plain_adder(z0, n, shifts))
 
     def _iter_sums(self, frames_per_view, z0, n, batch, adder):
         """iter_frame_sums and iter_frame_sums_counted behind their argument checks"""
@@ -1360,7 +1409,7 @@ class BatchedAccess:
         yield from self._count_stream(z0, n, batch, area_threshold, method)
 
     # ---- counted views (rc_sum_add_counted): the events of a range of frames summed on the device, on a grid up to 16 times finer ---------
-    def sum_frames_counted(self, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1, into=None):
+    def sum_frames_counted(self, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1, into=None, shifts=None):
         """The counted image of frames z0 .. z0+n-1 as uint64[upsample * ny, upsample * nx]: every event of get_frames_counted (same
         components, method and area_threshold) is ONE count, added on the device to the cell of a grid `upsample` (1..16) times finer
         than the sensor's whose centre lies nearest to the event's exact centroid (ties to the even cell index; pixel centres at
@@ -1370,21 +1419,23 @@ class BatchedAccess:
         4 * upsample^2 * nx * ny bytes on the device and as much page-locked memory on the host (1 GiB for 4096 x 4096 at 4).
         into: a _lib.FrameSum(upsample * nx, upsample * ny) - the counts are added into it and the number of frames is returned.
         Engine, routes, fall-backs, last_batch_path and the fold before a cell could overflow: sum_frames.  Levels 2 and 3 (every value 1)
-        go through the synchronous call.  Files of more than 16 bits are not taken (NotImplementedError)."""
+        go through the synchronous call.  Files of more than 16 bits are not taken (NotImplementedError).
+        shifts: as for sum_frames, in FINE cells (1 / upsample pixel): the event is placed on the fine grid and then translated, so an
+        integer shift is a drift correction at 1 / upsample-pixel resolution (rc_sum_add_counted_shifted)."""
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
         self._count_check_file()
-        return self._sum_into(z0, n, batch, into, _CountedAdder(method, area_threshold, upsample))
+        return self._sum_into(z0, n, batch, into, _counted_adder(method, area_threshold, upsample, z0, n, shifts))
 
-    def iter_frame_sums_counted(self, frames_per_view, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1):
+    def iter_frame_sums_counted(self, frames_per_view, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1, shifts=None):
         """iter_frame_sums with sum_frames_counted's images: yields (first index, count, uint32[upsample * ny, upsample * nx]) per window of
-        `frames_per_view` frames - a VIEW of page-locked memory, valid until the generator is advanced."""
+        `frames_per_view` frames - a VIEW of page-locked memory, valid until the generator is advanced.  shifts: as for sum_frames_counted."""
         if frames_per_view <= 0 or batch <= 0:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
         self._sum_check_file()
         self._count_check_file()
-        yield from self._iter_sums(frames_per_view, z0, n, batch, _CountedAdder(method, area_threshold, upsample))
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _counted_adder(method, area_threshold, upsample, z0, n, shifts))
 
     # ---- dense frame batches (rc_expand_frames_dense): a region of every frame as an array, written on the device --------------------------
     _DENSE_BYTES = 256 << 20      # the dense output of a batch the streaming calls size themselves (8 frames of 4096 x 4096 uint16)

@@ -16,6 +16,11 @@ more than 65 537 frames of 16 bits, or 1 048 832 of 12 - raises ValueError; the 
 counting (not in the reference): ReCoDeViewer(..., counting=dict(area_threshold=0, method='weighted_average', upsample=1)) - any subset of
 the keys - makes every view the COUNTED image of its window (ReCoDeReader.sum_frames_counted): one count per electron event, on a grid
 `upsample` times finer than the sensor's; get_shape() is then (upsample * ny, upsample * nx).
+
+shifts (not in the reference): ReCoDeViewer(..., shifts=table) - an integer array indexed by frame ID, shape (>= largest id + 1, 2), row id =
+(dy, dx) - makes every view an ALIGNED one: each frame is translated by its row before it is added, what leaves the view is dropped
+(ReCoDeReader.sum_frames(shifts=)).  Whole pixels for plain views; with counting= the units are fine cells (1 / upsample pixel).  An id beyond
+the table is a ValueError at the window that needs it.
 """
 import os
 
@@ -44,9 +49,19 @@ def plan_view(part_ids, start, fractionation):
     return ranges, n_frames, (last + 1 if n_frames else stop)
 
 
+def shifts_for_ids(table, ids):
+    """rows of the viewer's shift table for the frame ids of a part's share of a window - a pure function.  ValueError: an id the table
+    does not reach."""
+    ids = np.asarray(ids, np.int64)
+    if ids.size and (int(ids.max()) >= table.shape[0] or int(ids.min()) < 0):
+        raise ValueError('shifts: frame id %d needs a table of at least %d rows, it has %d'
+                         % (int(ids.max()), int(ids.max()) + 1, table.shape[0]))
+    return table[ids]
+
+
 class ReCoDeViewer:
 
-    def __init__(self, folder_path, base_filename, num_parts, fractionation, counting=None):
+    def __init__(self, folder_path, base_filename, num_parts, fractionation, counting=None, shifts=None):
         from .. import _lib
         from ..recode_reader import ReCoDeReader
         self._fractionation = int(fractionation)
@@ -56,6 +71,9 @@ class ReCoDeViewer:
             if unknown:
                 raise ValueError('counting: unknown keys %s' % sorted(unknown))
             self._counting = dict(dict(area_threshold=0, method='weighted_average', upsample=1), **counting)
+        self._shifts = None
+        if shifts is not None:
+            self._shifts = _lib.shift_rows(shifts, None, 'ReCoDeViewer: shifts')
         self._readers = []
         self._frame_start = 0
         self._sum = None
@@ -81,12 +99,15 @@ class ReCoDeViewer:
         if plan is None:
             return None
         ranges, n_frames, next_start = plan
+        # (every part's rows before anything is added: an id the table does not reach leaves the view untouched)
+        shifted = [None if self._shifts is None or hi <= lo else shifts_for_ids(self._shifts, rd.part_frame_ids[lo:hi])
+                   for rd, (lo, hi) in zip(self._readers, ranges)]
         try:
-            for rd, (lo, hi) in zip(self._readers, ranges):
+            for rd, (lo, hi), rows in zip(self._readers, ranges, shifted):
                 if hi > lo and self._counting:
-                    rd.sum_frames_counted(lo, hi - lo, into=self._sum, **self._counting)
+                    rd.sum_frames_counted(lo, hi - lo, into=self._sum, shifts=rows, **self._counting)
                 elif hi > lo:
-                    rd.sum_frames(lo, hi - lo, into=self._sum)
+                    rd.sum_frames(lo, hi - lo, into=self._sum, shifts=rows)
         except Exception:
             self._sum.fetch_view(reset=True)                     # (what earlier parts added is no view: start the window afresh)
             raise
