@@ -28,6 +28,7 @@
 #include "../../include/recode_hip.h"
 #include "rc_expand.h"
 #include "rc_launch.h"
+#include "rc_read_plan.h"
 #include "rc_zstd_block.h"
 #include "rc_zstd_dec.h"
 
@@ -297,14 +298,10 @@ struct ReadRes {
     DevBuf d_count;                                        // electron counting (rc_count.hip): directory, union-find nodes, per-component sums, event counters
     // a submitted batch waiting for its rc_expand_frames_wait
     bool pending = false;
-    uint32_t n = 0, level = 0, bit_depth = 0;
-    uint64_t cap = 0;
-    uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be
-    uint32_t late_value_bytes = 0;                         // good (device inflate), its COO value width (0: none) and whether it is COO at all
-    bool late_coo = false;
-    uint64_t late_dense = 0;                               // rc_expand_frames_dense_submit: bytes of the staged cells (0: not a dense batch), always copied late
-    bool late_events = false;                              // rc_count_frames_submit: the four event arrays, always copied late (a refused batch writes nothing)
-    std::vector<uint32_t> pv_bytes;
+    uint32_t n = 0;
+    rc::ReadKind kind = rc::RK_TRIPLETS;                   // what the batch leaves behind: the verdict's capacity rule and the copy-back plan follow from it
+    uint64_t cap = 0, cell_bytes = 0;                      // (rc_read_plan.h; cell_bytes: a dense or trace output's size)
+    uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be good
 };
 
 struct Util {

@@ -6,6 +6,7 @@
 #include "rc_count.h"
 #include "rc_dense.h"
 #include "rc_inflate.h"
+#include "rc_read_plan.h"
 #include "rc_trace.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
@@ -119,48 +120,107 @@ struct rc_sum {
                                        // a counted add: of the events its frames can hold (counted_admit)
 };
 
-// rc_count_frames' events, staged on the device with the caller's stride: uint64 weight[cap] | int32 rows[cap] | int32 cols[cap] | uint32 area[cap]
-static hipError_t copy_events(uint8_t *dst, const uint8_t *src, uint64_t cap, uint64_t total, hipStream_t s)
-{
-    hipError_t e = hipMemcpyAsync(dst, src, total * 8, hipMemcpyDeviceToHost, s);
-    for (uint64_t k = 0; k < 3 && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(dst + cap * (8 + 4 * k), src + cap * (8 + 4 * k), total * 4, hipMemcpyDeviceToHost, s);
-    return e;
-}
-
-// slot, submit_only: rc_expand_frames = (RC_READ_SLOTS - its own resources -, false); rc_expand_frames_submit = (slot, true): returns once everything is queued.
-// coo (bytes of a value, 0 = not): the output is not uint64 triplets but the three arrays of a COO matrix - int32 rows[cap] | int32 columns[cap] |
-// uint16 (2, rc_expand_frames_coo) or uint32 (4, rc_expand_frames_coo32) values[cap] (k_expand_emit_b<true, ...>): 10 or 12 bytes per set
-// pixel and capacity instead of 24.
-// l2out (rc_expand_frames_l2, level 2 only): rows and columns alone (coo without the value array: 8 bytes per set pixel), and every frame's
-// statistics - the fields of its value stream - as uint16 into stats[stats_cap].  Without it a level-2 frame's statistics stream is
-// stepped over and the frame expands like a level-3 one.
-// sum (rc_sum_add_frames / _submit): no entries at all - behind the count, k_expand_sum_b adds the frames' values to the handle's cells
-// (triplets NULL, cap 0).  The gate is the emit kernel's: a batch a decoder or k_expand_bases rejects adds nothing.
-// cnt (rc_count_frames / _submit): no entry per set pixel either - behind the count the kernels of rc_count.hip label the frames' set
-// pixels and write one event per connected component (`triplets` = the event arrays, cap events, 20 bytes each; nnz_prefix = the frames'
-// EVENT prefix).  A level-2 file's statistics stream is stepped over, as for the sum.
-// cnt and sum together (rc_sum_add_counted / _submit): no event array either - the counting kernels end in k_cnt_place, which adds one
-// count per event to the handle's cells, a grid cnt->upsample times finer than the frame (nx, ny are the FRAME's; triplets NULL, cap 0).
-// shifts (rc_sum_add_frames_shifted, rc_sum_add_counted_shifted and their _submit forms; with sum only): the caller's int32 (dy, dx) per frame.  They are
-// copied into the slot's page-locked head before anything is queued - the caller may reuse its array once the call has returned - and
-// reach the device with the head's one copy; k_sum_shift (rc_expand.hip) or k_cnt_place then adds frame f that far from where it lies.
-// dense (rc_expand_frames_dense / _submit): no entries either - behind the count, k_expand_dense_b (rc_dense.hip) writes a region of every frame as
-// an array of cells (`triplets` = the output, cap = its cells, at least n * w * h of cell_bytes bytes: the entry points have checked it).
-// trace (rc_trace_frames / _submit): no entries either - behind the count, the kernels of rc_trace.hip write 4 + k int64 sums per frame
-// (`triplets` = the output, cap = its cells, at least n * (4 + k): the entry points have checked it).  It shares the dense request's
-// handling of the output: written in place in device memory, staged and released after the verdict for host memory.
+// ---- one request: what an entry point asks of expand_run ---------------------------------------------------------------------------------
 struct CountReq { uint32_t method, area_threshold, upsample; };
 struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
-struct TraceReq { const int32_t *weights; uint32_t k; };   // (rc_trace_frames: the handle's interleaved weights and their planes)
-static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
-                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap, uint32_t coo = 0,
-                      bool l2out = false, uint16_t *stats = nullptr, uint64_t stats_cap = 0, rc_sum *sum = nullptr, const CountReq *cnt = nullptr,
-                      const DenseReq *dense = nullptr, const TraceReq *trace = nullptr, const int32_t *shifts = nullptr)
+struct TraceReq { const int32_t *weights; uint32_t k; };   // (the handle's interleaved weights and their planes)
+// slot, submit: the synchronous forms = (RC_READ_SLOTS - their own resources -, false); the _submit forms = (slot, true): they return once
+// everything is queued.  kind (rc_read_plan.h) says what out / cap are: entries of the kind's size (cap of them; NULL / 0: the prefix alone),
+// the cells of a dense or trace output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
+// stats_cap (RK_L2 alone; otherwise a level-2 file's statistics stream is stepped over): every frame's fields as uint16.  shifts (with sum
+// only): the caller's int32 (dy, dx) per frame, copied into the slot's page-locked head before anything is queued - the caller may reuse its
+// array once the call has returned.  count.upsample: RK_COUNTED_SUM's grid is that many times finer than the frame (nx, ny: the FRAME's).
+struct ReadFrames { uint32_t nx, ny, bit_depth, level, op_mode, scheme; const uint8_t *data; const uint32_t *sizes; uint32_t n; };   // (the ABI's order)
+struct ReadRequest {
+    ReadFrames in;
+    uint32_t slot = RC_READ_SLOTS; bool submit = false;
+    uint64_t *nnz_prefix = nullptr;
+    rc::ReadKind kind = rc::RK_TRIPLETS; void *out = nullptr; uint64_t cap = 0;
+    uint16_t *stats = nullptr; uint64_t stats_cap = 0;
+    rc_sum *sum = nullptr; const int32_t *shifts = nullptr;
+    CountReq count{}; DenseReq dense{}; TraceReq trace{};
+};
+
+// `p` must be memory a queued copy can fill: RC_ERR_BAD_ARG with `msg` for anything but page-locked host memory
+static int need_page_locked(const void *p, const char *msg)
 {
-    const uint64_t esz = cnt ? 20 : l2out ? 8 : coo ? 8 + coo : 24;      // bytes per entry of the output
-    using namespace rc;
-    if (!data || !sizes || (!nnz_prefix && !submit_only && !dense && !trace) || n == 0 || nx == 0 || ny == 0 || (!triplets && cap) || (!stats && stats_cap))
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost) return RC_OK;
+    (void)hipGetLastError();
+    return fail(RC_ERR_BAD_ARG, msg);
+}
+
+// a staged output's segments from `src` (device) to the caller's `dst`, same offsets on both sides
+static int run_copy_plan(const rc::CopyPlan &plan, uint8_t *dst, const uint8_t *src, hipStream_t s)
+{
+    for (uint32_t i = 0; i < plan.nseg; ++i)
+        HIP_TRY(hipMemcpyAsync(dst + plan.seg[i].off, src + plan.seg[i].off, plan.seg[i].bytes, hipMemcpyDeviceToHost, s));
+    return RC_OK;
+}
+
+// The slot's head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n]
+// [pv_bytes n] [base2 2n][pv_base n][src_base n][st_base n] [shifts 2n int32] (a shifted add only) - the same layout in page-locked host
+// memory and on the device: one copy.  It is what the kernels read.
+struct HeadLayout {
+    uint64_t n, ntab, o_lists, o_base2, o_shift, bytes;
+    HeadLayout(uint64_t n_ = 0, bool zstd = false, bool shifted = false) : n(n_), ntab(zstd ? n_ : 0)
+    {
+        o_lists = 2 * ntab * sizeof(rc::ZdTables);
+        o_base2 = (o_lists + (3 * n + RC_READ_THREADS) * sizeof(rc::ZdFrameList) + n * 4 + 15) & ~15ull;
+        o_shift = o_base2 + n * 5 * 8;
+        bytes = o_shift + (shifted ? n * 8 : 0);
+    }
+};
+struct HeadView {
+    rc::ZdTables *bm_tab, *pv_tab;
+    rc::ZdFrameList *bm_list, *pv_list, *raw_list, *cbm_list;
+    uint32_t *pv_bytes; uint64_t *base2, *pv_base, *src_base, *st_base; int32_t *shifts;       // (shifts nullptr: not a shifted add)
+};
+static HeadView head_view(const HeadLayout &L, uint8_t *base)
+{
+    HeadView v;
+    v.bm_tab = reinterpret_cast<rc::ZdTables *>(base); v.pv_tab = v.bm_tab + L.ntab;
+    v.bm_list = reinterpret_cast<rc::ZdFrameList *>(base + L.o_lists); v.pv_list = v.bm_list + L.n; v.raw_list = v.pv_list + L.n;
+    v.cbm_list = v.raw_list + RC_READ_THREADS;
+    v.pv_bytes = reinterpret_cast<uint32_t *>(v.cbm_list + L.n);
+    v.base2 = reinterpret_cast<uint64_t *>(base + L.o_base2); v.pv_base = v.base2 + 2 * L.n; v.src_base = v.pv_base + L.n; v.st_base = v.src_base + L.n;
+    v.shifts = L.bytes > L.o_shift ? reinterpret_cast<int32_t *>(base + L.o_shift) : nullptr;
+    return v;
+}
+
+// What the stages of one call hand to each other, on top of the request's frames and the slot's head as the HOST sees it (dev: the device)
+struct ReadRun : ReadFrames, HeadView {
+    const ReadRequest &q;
+    UtilScope scope;
+    Util *pU = nullptr; ReadRes *pu = nullptr; hipStream_t s = nullptr;
+    uint64_t *h_res = nullptr;                 // page-locked: the prefix (n + 1) and the error word, as the device leaves them
+    rc::ReadKindInfo kind;
+    uint32_t codec, klevel, nblk, nthr = 1;
+    bool vstream, values, l2out;               // the frames carry a value stream (level 1: residuals, level 2: statistics) ... which this call decodes
+    uint64_t N, nb, nb8, bm_stride, pv_stride, total_in = 0, out_bytes;
+    std::vector<uint64_t> foff, st_off;
+    uint64_t stats_total = 0; uint32_t stats_max = 0; bool stats_short = false, stats_staged = false; uint16_t *stats_dev = nullptr;
+    void *out; uint64_t cap;                   // the request's output and capacity - none once stats is short: the call still counts
+    HeadLayout head; HeadView dev;
+    const uint8_t *d_data, *d_bm, *d_pv; uint8_t *d_out; uint32_t *d_blk_cnt, *d_blk_off; uint64_t *d_fnnz, *d_fbase; int *d_err;
+    const uint64_t *d_prefix;                  // where the kernels leave the prefix the caller gets
+    uint64_t n_bm = 0, n_pv = 0, n_raw = 0;
+    uint32_t bm_max = 0, pv_max = 0, raw_max_regen = 0, cbm_max = 0;
+    void *target = nullptr;                    // device memory the kernels write the output to: the caller's, or d_triplets (nullptr: nothing yet)
+    uint8_t *host_dst = nullptr;               // the caller's host memory, when the output is or will be staged in d_triplets
+    uint64_t cell_bytes = 0;                   // bytes of a dense / trace output
+    double t[5] = {};                          // RC_READ_TIMING
+    explicit ReadRun(const ReadRequest &r) : ReadFrames(r.in), HeadView(), q(r) {}
+    int begin(), host_walk(), decode(), route(), results(), finish();      // the stages, in expand_run's order
+};
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- stage 1: the checks, the sizes known without looking at the streams, the slot and its buffers ------------------------------------------
+using namespace rc;      // (the stages below)
+int ReadRun::begin()
+{
+    kind = read_kind_info(q.kind); l2out = kind.stats;
+    if (!data || !sizes || (!q.nnz_prefix && !q.submit && !kind.cells) || n == 0 || nx == 0 || ny == 0 || (!q.out && q.cap) || (!q.stats && q.stats_cap))
         return fail(RC_ERR_BAD_ARG, "NULL / zero argument");
     if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
     if (level == 1 && (bit_depth == 0 || bit_depth > 64)) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
@@ -171,18 +231,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: scheme has no batched device decoder");
     if (op_mode != 0 && scheme == RC_SCHEME_ZLIB_DEVICE && level == 2)
         return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: the device inflate reads reduction levels 1 and 3");
-    const uint32_t codec = op_mode == 0 ? EMIT_RAW : scheme;   // (EMIT_LZ4 / EMIT_ZSTD / EMIT_BLOSC / EMIT_DEFLATE are the scheme codes)
-    const bool vstream = level != 3;              // the frames carry a value stream (level 1: residuals, level 2: statistics) ...
-    const bool values = level == 1 || l2out;      // ... which this call decodes
-    const uint32_t klevel = level == 1 ? 1u : l2out ? 2u : 3u;   // what the expand kernels see: 2 = value 1, COO without the value array
-    const uint64_t N = (uint64_t)nx * ny, nb = (N + 7) / 8, nb8 = (nb + 7) / 8;
-    static const bool timing = getenv("RC_READ_TIMING") != nullptr;   // development: phase times on stderr
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_0 = now();
-    // ---- sizes known without looking at the streams; the copy-in of the compressed bytes starts before the host walks them ----
-    const uint64_t bm_stride = nb8 * 8 + 8;
-    uint64_t pv_stride = 16, total_in = 0;
-    std::vector<uint64_t> foff(n);
+    codec = op_mode == 0 ? EMIT_RAW : scheme;   // (EMIT_LZ4 / EMIT_ZSTD / EMIT_BLOSC / EMIT_DEFLATE are the scheme codes)
+    vstream = level != 3; values = read_kind_values(q.kind, level); klevel = read_kind_klevel(q.kind, level);
+    N = (uint64_t)nx * ny; nb = (N + 7) / 8; nb8 = (nb + 7) / 8;
+    t[0] = now_ms();
+    bm_stride = nb8 * 8 + 8; pv_stride = 16;
+    std::vector<uint64_t>(n).swap(foff);
     for (uint32_t f = 0; f < n; ++f) {
         const uint32_t npk = values ? sizes[3 * f + 2] : 0;
         pv_stride = std::max<uint64_t>(pv_stride, ((uint64_t)npk + 15) & ~15ull);
@@ -191,53 +245,52 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     }
     pv_stride += 16;
     // level-2 statistics: frame f holds floor(8 * sizes[f][2] / bit_depth) of them (exact for fields of a byte or more)
-    uint64_t stats_total = 0;
-    uint32_t stats_max = 0;
-    std::vector<uint64_t> st_off(l2out ? n : 0);
+    std::vector<uint64_t>(l2out ? n : 0).swap(st_off);
     for (uint32_t f = 0; f < n && l2out; ++f) {
         const uint32_t c = (uint32_t)(8ull * sizes[3 * f + 2] / bit_depth);
         st_off[f] = stats_total;
         stats_total += c;
         stats_max = std::max(stats_max, c);
     }
-    const bool stats_short = stats_total > stats_cap;     // the synchronous call still counts (nnz_prefix stays valid), and writes nothing
-    if (stats_short && submit_only) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2_submit: stats holds fewer entries than the frames have statistics");
-    if (stats_short) { triplets = nullptr; cap = 0; }
-    UtilScope util_scope;
-    int r = util_scope.enter();
+    stats_short = stats_total > q.stats_cap;     // the synchronous call still counts (nnz_prefix stays valid), and writes nothing
+    if (stats_short && q.submit) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2_submit: stats holds fewer entries than the frames have statistics");
+    out = stats_short ? nullptr : q.out; cap = stats_short ? 0 : q.cap;
+    int r = scope.enter();
     if (r != RC_OK) return r;
-    Util &U = g_util;
-    ReadRes &u = U.rr[slot];
+    Util &U = *(pU = &g_util); ReadRes &u = *(pu = &U.rr[q.slot]);
     if (u.pending) return fail(RC_ERR_BAD_ARG, "rc_expand_frames: this slot holds a submitted batch - rc_expand_frames_wait first");
     if (!u.stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&u.stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&u.stream2, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&u.ev_a, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&u.ev_b, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
+        for (hipStream_t *p : {&u.stream, &u.stream2}) HIP_TRY(hipStreamCreateWithFlags(p, hipStreamNonBlocking));
+        for (hipEvent_t *p : {&u.ev_a, &u.ev_b, &u.done}) HIP_TRY(hipEventCreateWithFlags(p, hipEventDisableTiming));
     }
     if ((r = u.h_res.ensure(U.hmem, ((uint64_t)n + 2) * 8)) != RC_OK) return r;
-    uint64_t *h_res = u.h_res.as<uint64_t>();
-    hipStream_t s = u.stream;
-    const uint32_t nblk = (uint32_t)((nb8 + WG - 1) / WG);
-    const uint64_t out_bytes = (uint64_t)n * (bm_stride + (values ? pv_stride : 0)) + 64;
-    // head: [ZdTables bitmap x n][ZdTables values x n] (zstd) [block lists: bitmap x n, values x n, stored x threads, compact bitmap x n][pv_bytes n] [base2 2n][pv_base n][src_base n][st_base n], the
-    // same layout in page-locked host memory and on the device: one copy
-    const uint64_t ntab = codec == EMIT_ZSTD ? 2 * (uint64_t)n : 0;
-    const uint64_t o_first = ntab * sizeof(ZdTables);
-    const uint64_t o_base2 = (o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList) + (uint64_t)n * 4 + 15) & ~15ull;
-    const uint64_t o_shift = o_base2 + (uint64_t)n * 5 * 8;                 // [shifts 2n int32] behind them, for a shifted add only
-    const uint64_t sz_head = o_shift + (shifts ? (uint64_t)n * 8 : 0);
+    h_res = u.h_res.as<uint64_t>(); s = u.stream;
+    nblk = (uint32_t)((nb8 + WG - 1) / WG);
+    out_bytes = (uint64_t)n * (bm_stride + (values ? pv_stride : 0)) + 64;
+    head = HeadLayout(n, codec == EMIT_ZSTD, q.shifts != nullptr);
     if ((r = u.d_data.ensure(U.dmem, total_in + 64)) != RC_OK || (r = u.d_streams.ensure(U.dmem, out_bytes)) != RC_OK ||
-        (r = u.d_head.ensure(U.dmem, sz_head)) != RC_OK ||
+        (r = u.d_head.ensure(U.dmem, head.bytes)) != RC_OK ||
         (r = u.d_counters.ensure(U.dmem, (uint64_t)n * nblk * 8 + (uint64_t)(2 * n + 2) * 8 + 64)) != RC_OK ||
-        (r = u.rd_head.ensure(U.hmem, sz_head)) != RC_OK || (r = zstd_predefined_tables(U)) != RC_OK)
+        (r = u.rd_head.ensure(U.hmem, head.bytes)) != RC_OK || (r = zstd_predefined_tables(U)) != RC_OK)
         return r;
+    static_cast<HeadView &>(*this) = head_view(head, u.rd_head.p);
+    dev = head_view(head, u.d_head.p);
+    d_out = u.d_streams.p; d_bm = d_out; d_pv = d_out + (uint64_t)n * bm_stride;
+    d_blk_cnt = u.d_counters.as<uint32_t>(); d_blk_off = d_blk_cnt + (uint64_t)n * nblk;
+    d_fnnz = reinterpret_cast<uint64_t *>(d_blk_off + (uint64_t)n * nblk); d_fbase = d_fnnz + n;
+    d_prefix = d_fbase; d_err = reinterpret_cast<int *>(d_fbase + n + 1);
+    return RC_OK;
+}
+
+// ---- stage 2: the copy-in is queued, then the host walks the frames and builds block tables and decoding tables (a few threads, each
+// claiming frames one at a time).  The copy-in reads the caller's memory: from here on expand_run does not return without waiting for it.
+int ReadRun::host_walk()
+{
+    Util &U = *pU; ReadRes &u = *pu;
     // The compressed bytes: device memory is used where it lies; host memory is copied in, and the copy runs while the host walks the
     // streams.  (Letting the decoders read page-locked host memory in place - their staging loads as the transfer - was slower: the
     // transfer then sits inside the decoders' critical path, 1.3 ms against 0.7 ms behind a copy that hides under the host walk.)
-    const uint8_t *d_data = u.d_data.p;
-    uint8_t *d_out = u.d_streams.p;
+    d_data = u.d_data.p;
     bool copy_in = true;
     {
         // in place only if the decoders' 16-byte staging loads (and the bit readers' dword loads) can neither be misaligned nor leave
@@ -246,14 +299,12 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         const bool usable = ((uintptr_t)data & 15u) == 0 && (end & 4095u) != 0 && (end & 4095u) <= 4096u - 16u;
         if (usable && is_device_ptr(data)) { d_data = data; copy_in = false; }
     }
-    uint32_t *d_blk_cnt = u.d_counters.as<uint32_t>(), *d_blk_off = d_blk_cnt + (uint64_t)n * nblk;
-    uint64_t *d_fnnz = reinterpret_cast<uint64_t *>(d_blk_off + (uint64_t)n * nblk), *d_fbase = d_fnnz + n;
-    int *d_err = reinterpret_cast<int *>(d_fbase + n + 1);
     // The header walk below runs on the host.  Bytes that lie in device memory are fetched once into page-locked memory for it (the
     // host CAN read device memory through the PCIe aperture, a few hundred MB/s: 187 ms for 34 MB); the decoders read them where they are.
     const uint8_t *walk = data;
     if (is_device_ptr(data)) {
-        if ((r = u.h_blob.ensure(U.hmem, total_in + 64, total_in / 4)) != RC_OK) return r;
+        int r = u.h_blob.ensure(U.hmem, total_in + 64, total_in / 4);
+        if (r != RC_OK) return r;
         HIP_TRY(hipMemcpyAsync(u.h_blob.p, data, total_in, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         walk = u.h_blob.p;
@@ -261,23 +312,15 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     if (copy_in) HIP_TRY(hipMemcpyAsync(u.d_data.p, data, total_in, hipMemcpyDefault, s));
     HIP_TRY(hipMemsetAsync(d_out, 0, out_bytes, s));   // bitmap padding and value-stream tails read as zero
     HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
-    // ---- host: walk the frames, build block tables and decoding tables (a few threads, each a contiguous range of frames) ----
-    // (the copy-in reads the caller's memory: no return from here on without waiting for it)
-    auto bail = [&](int code, const char *msg) { (void)hipStreamSynchronize(s); return fail(code, msg); };
-    ZdTables *bm_tab = u.rd_head.as<ZdTables>(), *pv_tab = bm_tab + (codec == EMIT_ZSTD ? n : 0);
     // The block lists stay where the indexing threads wrote them, in page-locked host memory: the decoders read every entry once,
     // over the link (uploading them meant 3 small copies per thread, each a fixed ~15 us of stream time: 0.7 ms per call).
-    ZdFrameList *bm_list = reinterpret_cast<ZdFrameList *>(u.rd_head.p + o_first), *pv_list = bm_list + n, *raw_list = pv_list + n;
-    ZdFrameList *cbm_list = raw_list + RC_READ_THREADS;
-    uint32_t *pv_bytes = reinterpret_cast<uint32_t *>(cbm_list + n);
-    uint64_t *base2 = reinterpret_cast<uint64_t *>(u.rd_head.p + o_base2), *pv_base = base2 + 2 * (uint64_t)n, *src_base = pv_base + n, *st_base = src_base + n;
-    if (shifts) memcpy(u.rd_head.p + o_shift, shifts, (size_t)n * 8);
+    if (q.shifts) memcpy(shifts, q.shifts, (size_t)n * 8);
     // c0, c_n: the frame's range in its thread's compact offset list (c_n blocks = c_n + 1 offsets); c_skips: tree_skip | seq_skip << 8
     struct FrameIndex { uint32_t bm0 = 0, bm_n = 0, pv0 = 0, pv_n = 0, thread = 0, c0 = 0, c_n = 0, c_skips = 0; int status = ZD_OK; const char *what = nullptr; };
     std::vector<FrameIndex> fi(n);
     const uint32_t hw = usable_cpus();
     static const uint32_t thr_env = getenv("RC_READ_THREADS") ? (uint32_t)atoi(getenv("RC_READ_THREADS")) : 0u;   // (development: 1..16)
-    const uint32_t nthr = std::max(1u, std::min<uint32_t>(std::min<uint32_t>(n, thr_env ? std::min<uint32_t>(thr_env, RC_READ_THREADS) : RC_READ_THREADS), hw));
+    nthr = std::max(1u, std::min<uint32_t>(std::min<uint32_t>(n, thr_env ? std::min<uint32_t>(thr_env, RC_READ_THREADS) : RC_READ_THREADS), hw));
     const int dev_now = U.device;
     // frames are claimed one at a time: the calling thread starts at once, the pool's workers join in as they wake up (their
     // wake-up, not the walk - 30 us per frame - is what a static split waited for)
@@ -385,11 +428,9 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         }
     };
     g_pool->run(nthr, index_range);
-    const double t_1 = now();
-    uint64_t n_bm = 0, n_pv = 0, n_raw = 0;
-    uint32_t bm_max = 0, pv_max = 0, raw_max_regen = 0, cbm_max = 0;
+    t[1] = now_ms();
     for (uint32_t t = 0; t < nthr; ++t) {
-        if (!u.rd_bm[t].ok || !u.rd_pv[t].ok || !u.rd_raw[t].ok || !u.rd_off[t].ok) return bail(RC_ERR_DEVICE, "rc_expand_frames: page-locked host memory exhausted");
+        if (!u.rd_bm[t].ok || !u.rd_pv[t].ok || !u.rd_raw[t].ok || !u.rd_off[t].ok) return fail(RC_ERR_DEVICE, "rc_expand_frames: page-locked host memory exhausted");
         raw_list[t].p = u.rd_raw[t].data(); raw_list[t].n = (uint32_t)u.rd_raw[t].size(); raw_list[t].pad = 0;
         n_raw += u.rd_raw[t].size();
         const ZdBlock *rb = u.rd_raw[t].data();
@@ -398,8 +439,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
     for (uint32_t f = 0; f < n; ++f) {
         const FrameIndex &F = fi[f];
         const uint32_t t = F.thread;
-        if (F.status == ZD_FOREIGN) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: stream outside the device decoders' subset (use the stock decoder)");
-        if (F.status != ZD_OK) return bail(RC_ERR_CORRUPT, F.what ? F.what : "rc_expand_frames: malformed compressed stream");
+        if (F.status == ZD_FOREIGN) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: stream outside the device decoders' subset (use the stock decoder)");
+        if (F.status != ZD_OK) return fail(RC_ERR_CORRUPT, F.what ? F.what : "rc_expand_frames: malformed compressed stream");
         bm_list[f].p = u.rd_bm[t].data() + F.bm0; bm_list[f].n = F.bm_n; bm_list[f].pad = 0;
         pv_list[f].p = u.rd_pv[t].data() + F.pv0; pv_list[f].n = F.pv_n; pv_list[f].pad = 0;
         cbm_list[f].p = reinterpret_cast<const ZdBlock *>(u.rd_off[t].data() + F.c0); cbm_list[f].n = F.c_n; cbm_list[f].pad = F.c_skips;
@@ -413,24 +454,25 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         pv_max = std::max(pv_max, F.pv_n);
         n_bm += F.bm_n; n_pv += F.pv_n;
     }
-    if (n_raw >= (1ull << 31)) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
-    const double t_2 = now();
-    // ---- device ----
-    ZdTables *d_bm_tab = u.d_head.as<ZdTables>(), *d_pv_tab = d_bm_tab + (codec == EMIT_ZSTD ? n : 0);
-    const ZdFrameList *d_bm_list = reinterpret_cast<const ZdFrameList *>(u.d_head.p + o_first), *d_pv_list = d_bm_list + n, *d_raw_list = d_pv_list + n;
-    const ZdFrameList *d_cbm_list = d_raw_list + RC_READ_THREADS;
-    uint32_t *d_pv_bytes = reinterpret_cast<uint32_t *>(u.d_head.p + o_first + (3 * (uint64_t)n + RC_READ_THREADS) * sizeof(ZdFrameList));
-    uint64_t *d_base2 = reinterpret_cast<uint64_t *>(u.d_head.p + o_base2), *d_pvbase = d_base2 + 2 * (uint64_t)n, *d_src_base = d_pvbase + n, *d_st_base = d_src_base + n;
-    const int32_t *d_shifts = shifts ? reinterpret_cast<const int32_t *>(u.d_head.p + o_shift) : nullptr;
-    HIP_TRY(hipMemcpyAsync(u.d_head.p, u.rd_head.p, sz_head, hipMemcpyHostToDevice, s));
-    const double t_3 = now();
+    if (n_raw >= (1ull << 31)) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
+    t[2] = now_ms();
+    return RC_OK;
+}
+
+// ---- stage 3: the head's one copy, then the decoders ------------------------------------------------------------------------------------------
+int ReadRun::decode()
+{
+    Util &U = *pU; ReadRes &u = *pu;
+    const HeadView &d = dev;
+    HIP_TRY(hipMemcpyAsync(u.d_head.p, u.rd_head.p, head.bytes, hipMemcpyHostToDevice, s));
+    t[3] = now_ms();
     // the value streams' chunks (few, long serial chains) decode next to the binary maps' blocks (many, short), on a second stream
     static const bool serial = getenv("RC_READ_SERIAL") != nullptr;   // development: both decoders on one stream (clean per-kernel times)
-    if (n_pv && serial) launch_block_decode(EMIT_ZSTD, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, s);
+    if (n_pv && serial) launch_block_decode(EMIT_ZSTD, 1024, d_data, d.pv_list, n, pv_max, d.pv_tab, U.zd_predef, d_out, d.pv_base, d_err, s);
     else if (n_pv) {
         HIP_TRY(hipEventRecord(u.ev_a, s));
         HIP_TRY(hipStreamWaitEvent(u.stream2, u.ev_a, 0));
-        launch_block_decode(EMIT_ZSTD, 1024, d_data, d_pv_list, n, pv_max, d_pv_tab, U.zd_predef, d_out, d_pvbase, d_err, u.stream2);
+        launch_block_decode(EMIT_ZSTD, 1024, d_data, d.pv_list, n, pv_max, d.pv_tab, U.zd_predef, d_out, d.pv_base, d_err, u.stream2);
         HIP_TRY(hipEventRecord(u.ev_b, u.stream2));
     }
     if (codec == EMIT_DEFLATE) {
@@ -438,7 +480,8 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
         const uint32_t ns = values ? 2 * n : n;
         uint64_t cand_total = 0, unit_total = 0;
         uint32_t cap_max[2] = {0, 0}, units_max[2] = {0, 0};
-        if ((r = u.h_inf.ensure(U.hmem, (uint64_t)ns * sizeof(InfStream))) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+        int r = u.h_inf.ensure(U.hmem, (uint64_t)ns * sizeof(InfStream));
+        if (r != RC_OK) return r;
         InfStream *st = u.h_inf.as<InfStream>();
         for (uint32_t j = 0; j < ns; ++j) {
             const uint32_t f = j < n ? j : j - n, v = j < n ? 0u : 1u;
@@ -454,49 +497,65 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             cand_total += S.cap; unit_total += S.units;
             cap_max[v] = std::max(cap_max[v], S.cap); units_max[v] = std::max(units_max[v], S.units);
         }
-        if (cand_total >= (1ull << 31)) return bail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
+        if (cand_total >= (1ull << 31)) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: too many blocks in one call");
         const uint64_t o_tab = ((uint64_t)ns * sizeof(InfStream) + 15) & ~15ull;
-        if ((r = u.d_inf.ensure(U.dmem, o_tab + (2 * cand_total + unit_total + ns) * 4 + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
+        if ((r = u.d_inf.ensure(U.dmem, o_tab + (2 * cand_total + unit_total + ns) * 4 + 64)) != RC_OK) return r;
         HIP_TRY(hipMemcpyAsync(u.d_inf.p, st, (uint64_t)ns * sizeof(InfStream), hipMemcpyHostToDevice, s));
         uint32_t *d_cand = reinterpret_cast<uint32_t *>(u.d_inf.p + o_tab), *d_link = d_cand + cand_total, *d_unit = d_link + cand_total, *d_ncand = d_unit + unit_total;
         launch_inflate(d_data, u.d_inf.as<InfStream>(), n, ns - n, cap_max[0], units_max[0], cap_max[1], units_max[1], d_cand, d_ncand, d_link, d_unit, d_out,
                        d_err, s);
     }
-    if (cbm_max) launch_bitmap_decode_compact(codec, d_data, d_cbm_list, d_src_base, n, cbm_max, d_bm_tab, U.zd_predef, d_out, d_base2, nb, d_err, s);
-    if (n_bm && codec == EMIT_BLOSC) launch_blosc_decode_blocks(d_data, d_bm_list, n, bm_max, d_out, d_base2, d_err, s);
-    else if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d_bm_list, n, bm_max, d_bm_tab, U.zd_predef, d_out, d_base2, d_err, s);
-    launch_block_copy(d_data, d_raw_list, nthr, (uint32_t)n_raw, raw_max_regen, d_out, d_base2, s);
+    if (cbm_max) launch_bitmap_decode_compact(codec, d_data, d.cbm_list, d.src_base, n, cbm_max, d.bm_tab, U.zd_predef, d_out, d.base2, nb, d_err, s);
+    if (n_bm && codec == EMIT_BLOSC) launch_blosc_decode_blocks(d_data, d.bm_list, n, bm_max, d_out, d.base2, d_err, s);
+    else if (n_bm) launch_block_decode(codec, TILE_BM, d_data, d.bm_list, n, bm_max, d.bm_tab, U.zd_predef, d_out, d.base2, d_err, s);
+    launch_block_copy(d_data, d.raw_list, nthr, (uint32_t)n_raw, raw_max_regen, d_out, d.base2, s);
     if (n_pv && !serial) HIP_TRY(hipStreamWaitEvent(s, u.ev_b, 0));
-    const uint8_t *d_bm = d_out, *d_pv = d_out + (uint64_t)n * bm_stride;
+    return RC_OK;
+}
+
+// ---- stage 4: the output route of the kind - where the kernels write, and the count and the kernels behind it.  An output in host memory is
+// staged in d_triplets: kinds that are `held` in both forms; entries for a submitted batch too (page-locked memory: one asynchronous copy of
+// cap entries follows the emit kernel - the copy engine moves 64 MB in 1.3 ms under the next batch's work; letting the emit kernel write over
+// the link itself - 8-byte stores, 24 bytes apart - took 4 ms); the synchronous call's entries are emitted by finish(), their number known.
+int ReadRun::route()
+{
+    Util &U = *pU; ReadRes &u = *pu;
+    const HeadView &d = dev; const ReadKindInfo &k = kind;
+    int r = RC_OK;
     // level-2 statistics: unpacked where the caller wants them when the device can write there, otherwise staged - a submitted batch's
     // page-locked destination gets ONE asynchronous copy of all of them (their number is known here), the synchronous call copies at its end
-    uint16_t *stats_dev = stats;
-    bool stats_staged = false;
-    if (l2out && !stats_short && stats_total) {
-        if (!is_device_ptr(stats)) {
-            if (submit_only) {
-                hipPointerAttribute_t a;
-                if (hipPointerGetAttributes(&a, stats) != hipSuccess || a.type != hipMemoryTypeHost) {
-                    (void)hipGetLastError();
-                    return bail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: stats must be device or page-locked host memory");
-                }
-            }
-            if ((r = u.d_stats.ensure(U.dmem, stats_total * 2 + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-            stats_dev = u.d_stats.as<uint16_t>();
-            stats_staged = true;
+    stats_dev = q.stats;
+    if (k.stats && !stats_short && stats_total) {
+        if (!is_device_ptr(q.stats)) {
+            if (q.submit && (r = need_page_locked(q.stats, "rc_expand_frames_l2_submit: stats must be device or page-locked host memory")) != RC_OK) return r;
+            if ((r = u.d_stats.ensure(U.dmem, stats_total * 2 + 64)) != RC_OK) return r;
+            stats_dev = u.d_stats.as<uint16_t>(); stats_staged = true;
         }
-        launch_stats_unpack(d_pv, pv_stride, d_pv_bytes, d_st_base, n, stats_max, bit_depth, stats_dev, d_err, s);
-        if (stats_staged && submit_only) HIP_TRY(hipMemcpyAsync(stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
+        launch_stats_unpack(d_pv, pv_stride, d.pv_bytes, d.st_base, n, stats_max, bit_depth, stats_dev, d_err, s);
+        if (stats_staged && q.submit) HIP_TRY(hipMemcpyAsync(q.stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
     }
-    // Triplets wanted in DEVICE memory: the emit kernel is queued right behind the count - no host round trip in between; the kernel that
+    // Entries wanted in DEVICE memory: the emit kernel is queued right behind the count - no host round trip in between; the kernel that
     // finishes the count (k_expand_bases) checks what the host otherwise would (total <= cap, value streams long enough) and the emit
-    // kernel writes nothing once any check or decoder has raised *d_err.  Host memory: the output is staged, so its size must be known
-    // first (one more synchronisation).
-    // A submitted batch may also name PAGE-LOCKED host memory: the triplets are then staged in device memory and one asynchronous copy of
-    // cap entries follows the emit kernel (the copy engine moves 64 MB in 1.3 ms under the next batch's work; letting the emit kernel
-    // write over the link itself - 8-byte stores, 24 bytes apart - took 4 ms).
-    if (cnt) {
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
+    // kernel writes nothing once any check or decoder has raised *d_err.
+    if (q.kind == RK_TRACE) cell_bytes = (uint64_t)n * (TRACE_MOMENTS + q.trace.k) * 8;
+    if (q.kind == RK_DENSE) cell_bytes = (uint64_t)n * q.dense.region.w * q.dense.region.h * q.dense.cell_bytes;
+    auto place = [&]() -> int {      // where the kernels write: the caller's device memory, or d_triplets for its host memory
+        if (!out || is_device_ptr(out)) { target = out; return RC_OK; }
+        host_dst = static_cast<uint8_t *>(out);
+        if (q.submit && need_page_locked(out, k.pageable) != RC_OK) return RC_ERR_BAD_ARG;
+        if (!k.held && !q.submit) return RC_OK;
+        const int e = u.d_triplets.ensure(U.dmem, (k.cells ? cell_bytes : cap * k.esz) + 64);
+        if (e == RC_OK) target = u.d_triplets.p;
+        return e;
+    };
+    if (!k.counts && (r = place()) != RC_OK) return r;
+    // the count: with a capacity only where entries follow it at once
+    const bool emit_now = k.esz && !k.counts && target;
+    if (k.esz && !k.counts && !emit_now) launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s);
+    else
+        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d.pv_bytes, bit_depth, klevel,
+                                  emit_now ? cap : ~0ull, d_err);
+    if (k.counts) {
         // The workspace is sized by the set pixels the batch can hold.  Level 1: a frame's value stream bounds them (k_expand_bases refuses
         // a frame with more set pixels than its stream has fields), so nothing waits.  Levels 2 and 3: only the frame's size does - the
         // count is fetched first (one synchronisation, in the submit form too).
@@ -508,261 +567,180 @@ static int expand_run(uint32_t slot, bool submit_only, uint32_t nx, uint32_t ny,
             HIP_TRY(hipStreamSynchronize(s));
             id_cap = h_res[0];
         }
-        if (id_cap >= 0xFFFFFFFEull) return bail(RC_ERR_UNSUPPORTED, "rc_count_frames: 2^32 set pixels or more in one call (fewer frames per call)");
+        if (id_cap >= 0xFFFFFFFEull) return fail(RC_ERR_UNSUPPORTED, "rc_count_frames: 2^32 set pixels or more in one call (fewer frames per call)");
         id_cap = std::max<uint64_t>(id_cap, 1);
-        if ((r = u.d_count.ensure(U.dmem, cnt_workspace_bytes(nb8, n, id_cap, cnt->method) + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-        // events for host memory are staged and copied once the batch is known to be good: a refused batch writes nothing
-        void *events = triplets;
-        const bool staged = triplets && !is_device_ptr(triplets);
-        if (staged) {
-            hipPointerAttribute_t a;
-            if (submit_only && (hipPointerGetAttributes(&a, triplets) != hipSuccess || a.type != hipMemoryTypeHost)) {
-                (void)hipGetLastError();
-                return bail(RC_ERR_BAD_ARG, "rc_count_frames_submit: events must be device or page-locked host memory");
-            }
-            if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-            events = u.d_triplets.p;
-        }
-        if (sum)
-            launch_count_place(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
-                               cnt->area_threshold, u.d_count.p, id_cap, sum->acc, (uint64_t)sum->nx * sum->ny, cnt->upsample, sum->ev, d_err, s, d_shifts);
+        if ((r = u.d_count.ensure(U.dmem, cnt_workspace_bytes(nb8, n, id_cap, q.count.method) + 64)) != RC_OK || (r = place()) != RC_OK) return r;
+        if (k.sums)
+            launch_count_place(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.count.method,
+                               q.count.area_threshold, u.d_count.p, id_cap, q.sum->acc, (uint64_t)q.sum->nx * q.sum->ny, q.count.upsample, q.sum->ev, d_err, s,
+                               d.shifts);
         else
-            launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cnt->method,
-                                cnt->area_threshold, u.d_count.p, id_cap, events, cap, d_err, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_res, cnt_ev_base(u.d_count.p, n), (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
-        if (submit_only) {
-            HIP_TRY(hipEventRecord(u.done, s));
-            u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
-            u.late_events = true; u.late_coo = false; u.late_value_bytes = 0; u.late_dense = 0;
-            u.pending = true;
-            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
-            u.pv_bytes.assign(pv_bytes, pv_bytes + n);
-            return RC_OK;
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        const int err = (int)(uint32_t)h_res[n + 1];
-        memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
-        if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
-        if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
-        if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
-        if (!triplets) return RC_OK;
-        const uint64_t total = nnz_prefix[n];
-        if (total > cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_count_frames: events holds fewer entries than the frames have events");
-        if (staged && total) {
-            HIP_TRY(copy_events(reinterpret_cast<uint8_t *>(triplets), u.d_triplets.p, cap, total, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        return RC_OK;
-    }
-    if (dense || trace) {
-        // The cells for device memory are written where the caller wants them; for host memory they are staged and copied once the batch is
-        // known to be good (a submitted batch: by rc_expand_frames_wait) - a refused batch writes nothing.
-        const uint64_t out_bytes_dense = trace ? (uint64_t)n * (rc::TRACE_MOMENTS + trace->k) * 8 : (uint64_t)n * dense->region.w * dense->region.h * dense->cell_bytes;
-        void *cells = triplets;
-        const bool staged = !is_device_ptr(triplets);
-        if (staged) {
-            hipPointerAttribute_t a;
-            if (submit_only && (hipPointerGetAttributes(&a, triplets) != hipSuccess || a.type != hipMemoryTypeHost)) {
-                (void)hipGetLastError();
-                return bail(RC_ERR_BAD_ARG, trace ? "rc_trace_frames_submit: out must be device or page-locked host memory"
-                                                        : "rc_expand_frames_dense_submit: out must be device or page-locked host memory");
-            }
-            if ((r = u.d_triplets.ensure(U.dmem, out_bytes_dense + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-            cells = u.d_triplets.p;
-        }
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
-        if (trace) {
-            // the per-(frame, block) partial sums live in the counting workspace: no counting request shares a batch with a trace
-            if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, trace->k) + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-            launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, trace->weights, trace->k,
-                                      u.d_count.as<int64_t>(), static_cast<int64_t *>(cells), d_err, s);
-        } else
-            launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, dense->region, dense->cell_bytes,
-                                      cells, d_err, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
-        if (submit_only) {
-            HIP_TRY(hipEventRecord(u.done, s));
-            u.late_dst = staged ? reinterpret_cast<uint8_t *>(triplets) : nullptr;
-            u.late_dense = out_bytes_dense;
-            u.late_events = false; u.late_coo = false; u.late_value_bytes = 0;
-            u.pending = true;
-            u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = ~0ull;
-            u.pv_bytes.assign(pv_bytes, pv_bytes + n);
-            return RC_OK;
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        const int err = (int)(uint32_t)h_res[n + 1];
-        if (nnz_prefix) memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
-        if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
-        if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
-        if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
-        if (staged) {
-            HIP_TRY(hipMemcpyAsync(triplets, cells, out_bytes_dense, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        return RC_OK;
-    }
-    bool dev_out = sum || (triplets && is_device_ptr(triplets));
-    uint64_t *host_async = nullptr;
-    if (submit_only && !dev_out) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, triplets) == hipSuccess && a.type == hipMemoryTypeHost) {
-            if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) { (void)hipStreamSynchronize(s); return r; }
-            host_async = triplets;
-            triplets = u.d_triplets.as<uint64_t>();
-            dev_out = true;
-        } else (void)hipGetLastError();
-    }
-    if (submit_only && !dev_out) return bail(RC_ERR_BAD_ARG, "rc_expand_frames_submit: triplets must be device or page-locked host memory");
-    if (sum) {
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, ~0ull, d_err);
-        HIP_TRY(hipStreamWaitEvent(s, sum->ev, 0));
-        if (d_shifts)
-            launch_expand_batch_sum_shifted(d_bm, bm_stride, nb8, N, nx, ny, n, d_blk_off, d_fnnz, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, d_shifts,
-                                            sum->acc, d_err, s);
+            launch_count_events(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.count.method,
+                                q.count.area_threshold, u.d_count.p, id_cap, target, cap, d_err, s);
+        d_prefix = cnt_ev_base(u.d_count.p, n);      // (the frames' EVENT prefix)
+    } else if (q.kind == RK_TRACE) {
+        // the per-(frame, block) partial sums live in the counting workspace: no counting request shares a batch with a trace
+        if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, q.trace.k) + 64)) != RC_OK) return r;
+        launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.trace.weights, q.trace.k,
+                                  u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+    } else if (q.kind == RK_DENSE)
+        launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.dense.region,
+                                  q.dense.cell_bytes, target, d_err, s);
+    else if (k.sums) {
+        HIP_TRY(hipStreamWaitEvent(s, q.sum->ev, 0));
+        if (d.shifts)
+            launch_expand_batch_sum_shifted(d_bm, bm_stride, nb8, N, nx, ny, n, d_blk_off, d_fnnz, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel,
+                                            d.shifts, q.sum->acc, d_err, s);
         else
-            launch_expand_batch_sum(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, sum->acc, d_err, s);
-        HIP_TRY(hipEventRecord(sum->ev, s));
-    } else if (dev_out) {
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s, d_pv_bytes, bit_depth, klevel, cap, d_err);
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, triplets, s, d_err, coo);
-    } else
-        launch_expand_batch_count(d_bm, bm_stride, nb8, N, n, d_blk_cnt, d_blk_off, d_fnnz, d_fbase, s);
+            launch_expand_batch_sum(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.sum->acc, d_err, s);
+        HIP_TRY(hipEventRecord(q.sum->ev, s));
+    } else if (emit_now)
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, cap, target, s,
+                                 d_err, k.coo);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h_res, d_fbase, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
-    // (the device inflate may refuse a batch on the device - "use the stock decoder" - and then nothing may reach the caller's output: its
-    // page-locked destination is filled by rc_expand_frames_wait, once the batch is known to be good)
-    const bool late_copy = host_async && codec == EMIT_DEFLATE;
-    if (host_async && cap && !late_copy) HIP_TRY(hipMemcpyAsync(host_async, triplets, cap * esz, hipMemcpyDeviceToHost, s));
-    if (submit_only) {   // (dev_out is a precondition, checked above)
-        HIP_TRY(hipEventRecord(u.done, s));
-        u.late_dst = late_copy ? reinterpret_cast<uint8_t *>(host_async) : nullptr;
-        u.late_value_bytes = l2out ? 0 : coo;
-        u.late_coo = coo != 0;
-        u.late_events = false;
-        u.late_dense = 0;
-        u.pending = true;
-        u.n = n; u.level = level; u.bit_depth = bit_depth; u.cap = sum ? ~0ull : cap;
-        u.pv_bytes.assign(pv_bytes, pv_bytes + n);
-        return RC_OK;
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    const int err = (int)(uint32_t)h_res[n + 1];
-    memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
-    const double t_4 = now();
-    if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
-    if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
-    const uint64_t total = nnz_prefix[n];
-    if (sum) return (err & 4) ? fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits") : RC_OK;
-    if (stats_short) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_l2: stats holds fewer entries than the frames have statistics");
-    if (stats_staged) {
-        HIP_TRY(hipMemcpyAsync(stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (!triplets) return RC_OK;
-    if (total > cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
-    if (level == 1)
-        for (uint32_t f = 0; f < n; ++f)
-            if (((nnz_prefix[f + 1] - nnz_prefix[f]) * bit_depth + 7) / 8 > pv_bytes[f])
-                return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
-    if (dev_out) {
-        if (timing)
-            fprintf(stderr, "rc_expand_frames: index %.3f ms, merge %.3f, enqueue copies %.3f, decode+count+emit (to sync) %.3f\n", t_1 - t_0, t_2 - t_1,
-                    t_3 - t_2, t_4 - t_3);
-        return RC_OK;
-    }
-    if (total == 0) return RC_OK;
-    if (coo) {
-        // the three arrays keep the caller's stride (cap) on the device as in the caller's buffer: three copies of `total` entries
-        if ((r = u.d_triplets.ensure(U.dmem, cap * esz + 64)) != RC_OK) return r;
-        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, cap, u.d_triplets.p, s, nullptr, coo);
-        HIP_TRY(hipGetLastError());
-        uint8_t *h = reinterpret_cast<uint8_t *>(triplets);
-        HIP_TRY(hipMemcpyAsync(h, u.d_triplets.p, total * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h + cap * 4, u.d_triplets.p + cap * 4, total * 4, hipMemcpyDeviceToHost, s));
-        if (!l2out) HIP_TRY(hipMemcpyAsync(h + cap * 8, u.d_triplets.p + cap * 8, total * coo, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return RC_OK;
-    }
-    if ((r = u.d_triplets.ensure(U.dmem, total * 24)) != RC_OK) return r;
-    uint64_t *d_trip = u.d_triplets.as<uint64_t>();
-    launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, d_pv_bytes, bit_depth, klevel, total, d_trip, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(triplets, d_trip, total * 24, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (timing)
-        fprintf(stderr, "rc_expand_frames: index %.3f ms, merge %.3f, enqueue copies %.3f, decode+count (to sync) %.3f, emit %.3f\n", t_1 - t_0, t_2 - t_1,
-                t_3 - t_2, t_4 - t_3, now() - t_4);
     return RC_OK;
 }
 
+// ---- stage 5: finish.  Both forms fetch the prefix and the error word; a submit notes what rc_expand_frames_wait needs and is done ---------------
+int ReadRun::results()
+{
+    ReadRes &u = *pu;
+    HIP_TRY(hipMemcpyAsync(h_res, d_prefix, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_res + n + 1, d_err, 4, hipMemcpyDeviceToHost, s));
+    if (!q.submit) return RC_OK;
+    const bool late = read_copy_is_late(q.kind, codec == EMIT_DEFLATE);
+    const int r = host_dst && !late ? run_copy_plan(read_copy_plan_early(q.kind, cap), host_dst, u.d_triplets.p, s) : RC_OK;
+    if (r != RC_OK) return r;
+    HIP_TRY(hipEventRecord(u.done, s));
+    u.late_dst = late ? host_dst : nullptr;
+    u.kind = q.kind; u.n = n; u.cap = cap; u.cell_bytes = cell_bytes; u.pending = true;
+    return RC_OK;
+}
+// ... both forms, once the stream (rc_expand_frames_wait: the event) has been waited for: the prefix out before any refusal, then the verdict
+static rc::Verdict read_judge(ReadRes &u, rc::VerdictRoute route, uint32_t n, uint64_t cap, uint64_t *nnz_prefix, rc::VerdictFacts f)
+{
+    const uint64_t *h_res = u.h_res.as<uint64_t>();
+    if (nnz_prefix) memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
+    f.err = (uint32_t)h_res[n + 1]; f.total = h_res[n]; f.cap = cap;
+    const rc::Verdict v = rc::read_verdict(route, u.kind, f);
+    if (v.status != RC_OK) fail(v.status, v.msg);
+    return v;
+}
+// ... and a good batch's output, staged in d_triplets, goes back to the caller
+static int read_copy_back(ReadRes &u, uint32_t n, uint64_t cap, uint64_t cell_bytes, uint8_t *dst)
+{
+    const rc::CopyPlan plan = rc::read_copy_plan(u.kind, cap, u.h_res.as<uint64_t>()[n], cell_bytes);
+    if (!plan.nseg) return RC_OK;
+    const int r = run_copy_plan(plan, dst, u.d_triplets.p, u.stream);
+    if (r != RC_OK) return r;
+    HIP_TRY(hipStreamSynchronize(u.stream));
+    return RC_OK;
+}
+int ReadRun::finish()
+{
+    ReadRes &u = *pu;
+    const VerdictRoute route = verdict_route_sync(kind);
+    VerdictFacts f{0, 0, 0, out != nullptr, stats_short, false};
+    // (level 1: the host checks each frame's share of the prefix against its value stream's bytes, where a waited-for batch has bit 4)
+    for (uint32_t i = 0; i < n && route == VR_SYNC_ENTRIES && level == 1; ++i)
+        f.values_short = f.values_short || ((h_res[i + 1] - h_res[i]) * bit_depth + 7) / 8 > pv_bytes[i];
+    u.kind = q.kind; t[4] = now_ms();
+    const Verdict v = read_judge(u, route, n, cap, q.nnz_prefix, f);
+    if (stats_staged && v.decoded()) {      // (the statistics of a batch that decoded, whatever becomes of its entries)
+        HIP_TRY(hipMemcpyAsync(q.stats, stats_dev, stats_total * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (v.status != RC_OK || v.step == VS_NO_OUTPUT) return v.status;
+    static const bool timing = getenv("RC_READ_TIMING") != nullptr;   // development: phase times on stderr
+    const uint64_t total = h_res[n];
+    if (!host_dst) {
+        if (timing && route == VR_SYNC_ENTRIES)
+            fprintf(stderr, "rc_expand_frames: index %.3f ms, merge %.3f, enqueue copies %.3f, decode+count+emit (to sync) %.3f\n", t[1] - t[0], t[2] - t[1],
+                    t[3] - t[2], t[4] - t[3]);
+        return RC_OK;
+    }
+    if (!target && total) {
+        // entries for host memory, now that their number is known: the triplets packed, the arrays of a COO output at the caller's stride
+        const uint64_t ecap = q.kind == RK_TRIPLETS ? total : cap;
+        const int r = u.d_triplets.ensure(pU->dmem, ecap * kind.esz + 64);
+        if (r != RC_OK) return r;
+        launch_expand_batch_emit(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_fbase, d_pv, pv_stride, dev.pv_bytes, bit_depth, klevel, ecap,
+                                 u.d_triplets.p, s, nullptr, kind.coo);
+        HIP_TRY(hipGetLastError());
+    }
+    const int r = read_copy_back(u, n, cap, cell_bytes, host_dst);
+    if (r == RC_OK && timing && q.kind == RK_TRIPLETS && total)
+        fprintf(stderr, "rc_expand_frames: index %.3f ms, merge %.3f, enqueue copies %.3f, decode+count (to sync) %.3f, emit %.3f\n", t[1] - t[0], t[2] - t[1],
+                t[3] - t[2], t[4] - t[3], now_ms() - t[4]);
+    return r;
+}
+
+// The batched reader behind every entry point below.  A stage that fails after the copy-in has been queued returns here, and the copy-in -
+// it reads the caller's memory - is waited for before the call returns, whatever the failure was.
+static int expand_run(ReadRequest q, const uint32_t *slot = nullptr)      // slot: a _submit form's (the entry point has checked it)
+{
+    if (slot) { q.slot = *slot; q.submit = true; }
+    ReadRun R(q);
+    int r = R.begin();                                             // checks, sizes, the slot and its buffers
+    if (r != RC_OK) return r;
+    if ((r = R.host_walk()) == RC_OK &&                            // copy-in queued; the host indexes the frames' blocks
+        (r = R.decode()) == RC_OK &&                               // the decoders, on the slot's two streams
+        (r = R.route()) == RC_OK)                                  // the count and the kind's kernels behind it
+        r = R.results();                                           // prefix and error word on their way; a submit is noted for its wait
+    if (r == RC_OK && q.submit) return RC_OK;
+    const hipError_t e = hipStreamSynchronize(R.s);
+    if (r != RC_OK) return r;
+    HIP_TRY(e);
+    return R.finish();                                             // verdict, and a staged output's way back
+}
+
+// ---- the entry points: a _submit form differs from its synchronous twin in the slot (checked first), in insisting on an output, and in
+// leaving the prefix to rc_expand_frames_wait - `slot` is nullptr for the synchronous form -----------------------------------------------------
+struct EntryNames { const char *slot, *no_out; uint32_t max_depth; const char *depth; };
+static int entries_run(ReadRequest q, const uint32_t *slot)
+{
+    static const EntryNames names[4] = {
+        {"rc_expand_frames_submit: slot 0 or 1", "rc_expand_frames_submit: triplets must be device or page-locked host memory", 0, nullptr},
+        {"rc_expand_frames_coo_submit: slot 0 or 1", "rc_expand_frames_coo_submit: the output must be device or page-locked host memory", 16,
+         "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)"},
+        {"rc_expand_frames_coo32_submit: slot 0 or 1", "rc_expand_frames_coo32_submit: the output must be device or page-locked host memory", 32,
+         "rc_expand_frames_coo32: values are uint32 (bit_depth <= 32)"},
+        {"rc_expand_frames_l2_submit: slot 0 or 1", "rc_expand_frames_l2_submit: the output must be device or page-locked host memory", 0, nullptr}};
+    static_assert(RK_TRIPLETS == 0 && RK_COO16 == 1 && RK_COO32 == 2 && RK_L2 == 3, "names[] is indexed by the kind");
+    const EntryNames &nm = names[q.kind];
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, nm.slot);
+    if (slot && !q.out) return fail(RC_ERR_BAD_ARG, nm.no_out);
+    if (nm.max_depth && q.in.level == 1 && q.in.bit_depth > nm.max_depth) return fail(RC_ERR_BAD_ARG, nm.depth);
+    return expand_run(q, slot);
+}
 RC_EXPORT int rc_expand_frames(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, uint64_t *triplets, uint64_t cap)
-{
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, triplets, cap);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_TRIPLETS, .out = triplets, .cap = cap},
+                       nullptr); }
 RC_EXPORT int rc_expand_frames_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
                                       uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *triplets_dev, uint64_t cap)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_submit: slot 0 or 1");
-    if (!triplets_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_submit: triplets must be device or page-locked host memory");
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, triplets_dev, cap);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_TRIPLETS, .out = triplets_dev, .cap = cap}, &slot); }
 RC_EXPORT int rc_expand_frames_coo(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                    const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap)
-{
-    if (level == 1 && bit_depth > 16) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)");
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(coo), cap, 2);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_COO16, .out = coo, .cap = cap}, nullptr); }
 RC_EXPORT int rc_expand_frames_coo_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
                                           uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo_submit: slot 0 or 1");
-    if (!coo_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo_submit: the output must be device or page-locked host memory");
-    if (level == 1 && bit_depth > 16) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo: values are uint16 (bit_depth <= 16)");
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, 2);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_COO16, .out = coo_dev, .cap = cap}, &slot); }
 RC_EXPORT int rc_expand_frames_coo32(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *coo, uint64_t cap)
-{
-    if (level == 1 && bit_depth > 32) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32: values are uint32 (bit_depth <= 32)");
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(coo), cap, 4);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_COO32, .out = coo, .cap = cap}, nullptr); }
 RC_EXPORT int rc_expand_frames_coo32_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
                                             uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, void *coo_dev, uint64_t cap)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32_submit: slot 0 or 1");
-    if (!coo_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32_submit: the output must be device or page-locked host memory");
-    if (level == 1 && bit_depth > 32) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_coo32: values are uint32 (bit_depth <= 32)");
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(coo_dev), cap, 4);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_COO32, .out = coo_dev, .cap = cap}, &slot); }
 RC_EXPORT int rc_expand_frames_l2(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                   const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix, void *rc, uint64_t cap, uint16_t *stats, uint64_t stats_cap)
-{
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(rc), cap, 2, true,
-                      stats, stats_cap);
-}
-
+{ return entries_run({.in = {nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_L2, .out = rc, .cap = cap,
+                        .stats = stats, .stats_cap = stats_cap}, nullptr); }
 RC_EXPORT int rc_expand_frames_l2_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t op_mode, uint32_t scheme,
                                          const uint8_t *data, const uint32_t *sizes, uint32_t n, void *rc_dev, uint64_t cap, uint16_t *stats_dev,
                                          uint64_t stats_cap)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: slot 0 or 1");
-    if (!rc_dev) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_l2_submit: the output must be device or page-locked host memory");
-    return expand_run(slot, true, nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(rc_dev), cap, 2, true, stats_dev,
-                      stats_cap);
-}
+{ return entries_run({.in = {nx, ny, bit_depth, 2, op_mode, scheme, data, sizes, n}, .kind = rc::RK_L2, .out = rc_dev, .cap = cap, .stats = stats_dev,
+                        .stats_cap = stats_cap}, &slot); }
 
 RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
 {
@@ -774,33 +752,8 @@ RC_EXPORT int rc_expand_frames_wait(uint32_t slot, uint64_t *nnz_prefix)
     if (!u.pending) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_wait: nothing was submitted to this slot");
     u.pending = false;
     HIP_TRY(hipEventSynchronize(u.done));
-    const uint32_t n = u.n;
-    const uint64_t *h_res = u.h_res.as<uint64_t>();
-    const int err = (int)(uint32_t)h_res[n + 1];
-    memcpy(nnz_prefix, h_res, (size_t)(n + 1) * 8);
-    if (err & 8) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: not the device DEFLATE encoder's stream (use the stock decoder)");
-    if (err & 1) return fail(RC_ERR_CORRUPT, "rc_expand_frames: a block does not decode to its expected size");
-    if (nnz_prefix[n] > u.cap || (err & 2)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames: triplets holds fewer entries than the frames have set pixels");
-    if (err & 4) return fail(RC_ERR_CORRUPT, "rc_expand_frames: value stream shorter than popcount(bitmap) * bit_depth bits");
-    if (u.late_dst && u.late_dense) {
-        // a dense batch's cells, staged in d_triplets: all of them, whatever the set pixels number
-        HIP_TRY(hipMemcpyAsync(u.late_dst, u.d_triplets.p, u.late_dense, hipMemcpyDeviceToHost, u.stream));
-        HIP_TRY(hipStreamSynchronize(u.stream));
-    } else if (u.late_dst && nnz_prefix[n]) {
-        // the output staged in d_triplets keeps the caller's layout (triplet rows, or the COO arrays cap entries apart)
-        const uint64_t total = nnz_prefix[n];
-        const uint8_t *src = u.d_triplets.p;
-        if (u.late_events) HIP_TRY(copy_events(u.late_dst, src, u.cap, total, u.stream));
-        else if (!u.late_coo) HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 24, hipMemcpyDeviceToHost, u.stream));
-        else {
-            HIP_TRY(hipMemcpyAsync(u.late_dst, src, total * 4, hipMemcpyDeviceToHost, u.stream));
-            HIP_TRY(hipMemcpyAsync(u.late_dst + u.cap * 4, src + u.cap * 4, total * 4, hipMemcpyDeviceToHost, u.stream));
-            if (u.late_value_bytes)
-                HIP_TRY(hipMemcpyAsync(u.late_dst + u.cap * 8, src + u.cap * 8, total * u.late_value_bytes, hipMemcpyDeviceToHost, u.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(u.stream));
-    }
-    return RC_OK;
+    const rc::Verdict v = read_judge(u, rc::VR_WAIT, u.n, u.cap, nnz_prefix, {});
+    return v.status == RC_OK && u.late_dst ? read_copy_back(u, u.n, u.cap, u.cell_bytes, u.late_dst) : v.status;
 }
 
 // ---- dense frame batches: a region of every frame as an array of cells (rc_dense.hip) -------------------------------------------------
@@ -820,29 +773,22 @@ static int dense_admit(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t le
     if (out_cells < (uint64_t)n * g.w * g.h) return fail(RC_ERR_OUT_TOO_SMALL, "rc_expand_frames_dense: out holds fewer than n * w * h cells");
     return RC_OK;
 }
-
+static int dense_run(const uint32_t *slot, ReadRequest q)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: slot 0 or 1");
+    const int r = dense_admit(q.in.nx, q.in.ny, q.in.bit_depth, q.in.level, q.in.n, q.dense, q.out, q.cap);
+    return r != RC_OK ? r : expand_run(q, slot);
+}
 RC_EXPORT int rc_expand_frames_dense(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                      const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t step_x, uint32_t step_y,
                                      uint32_t cell_bytes, void *out, uint64_t out_cells, uint64_t *nnz_prefix)
-{
-    const DenseReq req{{x0, y0, w, h, step_x, step_y}, cell_bytes};
-    const int r = dense_admit(nx, ny, bit_depth, level, n, req, out, out_cells);
-    if (r != RC_OK) return r;
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, static_cast<uint64_t *>(out), out_cells, 0, false,
-                      nullptr, 0, nullptr, nullptr, &req);
-}
-
+{ return dense_run(nullptr, {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_DENSE, .out = out,
+                               .cap = out_cells, .dense = {{x0, y0, w, h, step_x, step_y}, cell_bytes}}); }
 RC_EXPORT int rc_expand_frames_dense_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                             const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                             uint32_t step_x, uint32_t step_y, uint32_t cell_bytes, void *out, uint64_t out_cells)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: slot 0 or 1");
-    const DenseReq req{{x0, y0, w, h, step_x, step_y}, cell_bytes};
-    const int r = dense_admit(nx, ny, bit_depth, level, n, req, out, out_cells);
-    if (r != RC_OK) return r;
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(out), out_cells, 0, false, nullptr, 0,
-                      nullptr, nullptr, &req);
-}
+{ return dense_run(&slot, {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_DENSE, .out = out, .cap = out_cells,
+                             .dense = {{x0, y0, w, h, step_x, step_y}, cell_bytes}}); }
 
 // ---- electron counting: one event per connected component of a frame's set pixels (rc_count.hip) -------------------------------------
 static int count_admit(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t method)
@@ -852,29 +798,22 @@ static int count_admit(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t le
     if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_count_frames: bit_depth above 16 (the sums are exact in 64 bits for 16-bit values)");
     return RC_OK;
 }
-
+static int count_run(const uint32_t *slot, ReadRequest q)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: slot 0 or 1");
+    if (slot && !q.out) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: events must be device or page-locked host memory");
+    const int r = count_admit(q.in.nx, q.in.ny, q.in.bit_depth, q.in.level, q.count.method);
+    return r != RC_OK ? r : expand_run(q, slot);
+}
 RC_EXPORT int rc_count_frames(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                               const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, uint64_t *nev_prefix, void *events, uint64_t cap)
-{
-    const int r = count_admit(nx, ny, bit_depth, level, method);
-    if (r != RC_OK) return r;
-    const CountReq req{method, area_threshold};
-    return expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, static_cast<uint64_t *>(events), cap, 0, false,
-                      nullptr, 0, nullptr, &req);
-}
-
+{ return count_run(nullptr, {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nev_prefix, .kind = rc::RK_EVENTS, .out = events,
+                               .cap = cap, .count = {method, area_threshold, 0}}); }
 RC_EXPORT int rc_count_frames_submit(uint32_t slot, uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                      const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, void *events_dev,
                                      uint64_t cap)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: slot 0 or 1");
-    if (!events_dev) return fail(RC_ERR_BAD_ARG, "rc_count_frames_submit: events must be device or page-locked host memory");
-    const int r = count_admit(nx, ny, bit_depth, level, method);
-    if (r != RC_OK) return r;
-    const CountReq req{method, area_threshold};
-    return expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, static_cast<uint64_t *>(events_dev), cap, 0, false, nullptr,
-                      0, nullptr, &req);
-}
+{ return count_run(&slot, {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_EVENTS, .out = events_dev, .cap = cap,
+                             .count = {method, area_threshold, 0}}); }
 
 // ---- summed views: an accumulator the caller owns, and expand_run's route into it ------------------------------------------------------
 RC_EXPORT rc_sum *rc_sum_create(uint32_t nx, uint32_t ny, int *status)
@@ -942,66 +881,47 @@ static int sum_on_its_device(const rc_sum *s)
     return g_util.device == s->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_sum_add_frames: the handle belongs to another device");
 }
 
-RC_EXPORT int rc_sum_add_frames(rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
-                                const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix)
+// the end of every add, plain or counted: the synchronous forms lend a prefix of their own to a caller without one; the bound grows with
+// what was queued (a submit: a batch the device rejects later adds nothing, the bound stays an upper bound)
+static int add_run(rc_sum *s, const uint32_t *slot, uint64_t grow, ReadRequest &q)
 {
-    uint64_t grow = 0;
-    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
-    if (r == RC_OK) r = sum_on_its_device(s);
-    if (r != RC_OK) return r;
-    std::vector<uint64_t> own;
-    if (!nnz_prefix) { own.resize((size_t)n + 1); nnz_prefix = own.data(); }
-    r = expand_run(RC_READ_SLOTS, false, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, nullptr, 0, 0, false, nullptr, 0, s);
+    std::vector<uint64_t> own(slot || q.nnz_prefix ? 0 : (size_t)q.in.n + 1);
+    if (!own.empty()) q.nnz_prefix = own.data();
+    q.sum = s;
+    const int r = expand_run(q, slot);
     if (r == RC_OK) s->bound += grow;
     return r;
 }
-
-RC_EXPORT int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
-                                       const uint8_t *data, const uint32_t *sizes, uint32_t n)
+// shifts_msg: the form takes shifts, and this is what it says without them (q.in.nx, ny: the handle's, filled in here)
+static int sum_add_run(rc_sum *s, const uint32_t *slot, const char *slot_msg, const char *shifts_msg, ReadRequest q)
 {
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_submit: slot 0 or 1");
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, slot_msg);
+    if (shifts_msg && !q.shifts) return fail(RC_ERR_BAD_ARG, shifts_msg);
     uint64_t grow = 0;
-    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
+    int r = sum_admit(s, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.sizes, q.in.n, &grow);
     if (r == RC_OK) r = sum_on_its_device(s);
     if (r != RC_OK) return r;
-    r = expand_run(slot, true, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s);
-    if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
-    return r;
+    q.in.nx = s->nx; q.in.ny = s->ny;
+    return add_run(s, slot, grow, q);
 }
+RC_EXPORT int rc_sum_add_frames(rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                const uint32_t *sizes, uint32_t n, uint64_t *nnz_prefix)
+{ return sum_add_run(s, nullptr, nullptr, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_SUM}); }
+RC_EXPORT int rc_sum_add_frames_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
+                                       const uint8_t *data, const uint32_t *sizes, uint32_t n)
+{ return sum_add_run(s, &slot, "rc_sum_add_frames_submit: slot 0 or 1", nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_SUM}); }
 
 // ---- aligned views: the same adds with frame f translated by (shifts[2 * f], shifts[2 * f + 1]) = (dy, dx) cells of the view ---------------
 // Everything the unshifted calls check is checked as they check it, in their order; the shifts themselves cannot be wrong (any int32 pair
 // is legal), only missing.  The bound grows as for the unshifted add: dropping only lowers a sum.
 RC_EXPORT int rc_sum_add_frames_shifted(rc_sum *s, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                         const uint32_t *sizes, uint32_t n, const int32_t *shifts, uint64_t *nnz_prefix)
-{
-    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted: shifts is NULL");
-    uint64_t grow = 0;
-    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
-    if (r == RC_OK) r = sum_on_its_device(s);
-    if (r != RC_OK) return r;
-    std::vector<uint64_t> own;
-    if (!nnz_prefix) { own.resize((size_t)n + 1); nnz_prefix = own.data(); }
-    r = expand_run(RC_READ_SLOTS, false, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, nullptr, 0, 0, false, nullptr, 0, s, nullptr,
-                   nullptr, nullptr, shifts);
-    if (r == RC_OK) s->bound += grow;
-    return r;
-}
-
+{ return sum_add_run(s, nullptr, nullptr, "rc_sum_add_frames_shifted: shifts is NULL",
+                       {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_SUM, .shifts = shifts}); }
 RC_EXPORT int rc_sum_add_frames_shifted_submit(rc_sum *s, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                                const uint8_t *data, const uint32_t *sizes, uint32_t n, const int32_t *shifts)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted_submit: slot 0 or 1");
-    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_frames_shifted_submit: shifts is NULL");
-    uint64_t grow = 0;
-    int r = sum_admit(s, bit_depth, level, op_mode, sizes, n, &grow);
-    if (r == RC_OK) r = sum_on_its_device(s);
-    if (r != RC_OK) return r;
-    r = expand_run(slot, true, s->nx, s->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, nullptr, nullptr,
-                   nullptr, shifts);
-    if (r == RC_OK) s->bound += grow;      // (queued: as rc_sum_add_frames_submit)
-    return r;
-}
+{ return sum_add_run(s, &slot, "rc_sum_add_frames_shifted_submit: slot 0 or 1", "rc_sum_add_frames_shifted_submit: shifts is NULL",
+                       {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_SUM, .shifts = shifts}); }
 
 RC_EXPORT int rc_sum_fetch(rc_sum *s, uint32_t *dst, int reset)
 {
@@ -1043,68 +963,36 @@ static int counted_admit(const rc_sum *s, uint32_t nx, uint32_t ny, uint32_t ups
         return fail(RC_ERR_OUT_TOO_SMALL, "rc_sum_add_counted: a cell could pass 2^32 - 1 (rc_sum_fetch with reset first)");
     return RC_OK;
 }
-
+static int counted_run(rc_sum *s, const uint32_t *slot, const char *slot_msg, const char *shifts_msg, ReadRequest q)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, slot_msg);
+    if (shifts_msg && !q.shifts) return fail(RC_ERR_BAD_ARG, shifts_msg);
+    uint64_t grow = 0;
+    const int r = counted_admit(s, q.in.nx, q.in.ny, q.count.upsample, q.in.bit_depth, q.in.level, q.in.sizes, q.in.n, q.count.method, &grow);
+    return r != RC_OK ? r : add_run(s, slot, grow, q);
+}
 RC_EXPORT int rc_sum_add_counted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme,
                                  const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold, uint64_t *nev_prefix)
-{
-    uint64_t grow = 0;
-    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
-    if (r != RC_OK) return r;
-    std::vector<uint64_t> own;
-    if (!nev_prefix) { own.resize((size_t)n + 1); nev_prefix = own.data(); }
-    const CountReq req{method, area_threshold, upsample};
-    r = expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, nullptr, 0, 0, false, nullptr, 0, s, &req);
-    if (r == RC_OK) s->bound += grow;
-    return r;
-}
-
+{ return counted_run(s, nullptr, nullptr, nullptr, {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nev_prefix,
+                                                      .kind = rc::RK_COUNTED_SUM, .count = {method, area_threshold, upsample}}); }
 RC_EXPORT int rc_sum_add_counted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level,
                                         uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
                                         uint32_t area_threshold)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_submit: slot 0 or 1");
-    uint64_t grow = 0;
-    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
-    if (r != RC_OK) return r;
-    const CountReq req{method, area_threshold, upsample};
-    r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req);
-    if (r == RC_OK) s->bound += grow;      // (queued: a batch the device rejects later adds nothing, the bound stays an upper bound)
-    return r;
-}
-
+{ return counted_run(s, &slot, "rc_sum_add_counted_submit: slot 0 or 1", nullptr,
+                       {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_COUNTED_SUM, .count = {method, area_threshold, upsample}}); }
 // the counted adds with shifts in FINE cells (1 / upsample pixel): the event is placed as above and then translated
 RC_EXPORT int rc_sum_add_counted_shifted(rc_sum *s, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level, uint32_t op_mode,
                                          uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method, uint32_t area_threshold,
                                          const int32_t *shifts, uint64_t *nev_prefix)
-{
-    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted: shifts is NULL");
-    uint64_t grow = 0;
-    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
-    if (r != RC_OK) return r;
-    std::vector<uint64_t> own;
-    if (!nev_prefix) { own.resize((size_t)n + 1); nev_prefix = own.data(); }
-    const CountReq req{method, area_threshold, upsample};
-    r = expand_run(RC_READ_SLOTS, false, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nev_prefix, nullptr, 0, 0, false, nullptr, 0, s, &req, nullptr,
-                   nullptr, shifts);
-    if (r == RC_OK) s->bound += grow;
-    return r;
-}
-
+{ return counted_run(s, nullptr, nullptr, "rc_sum_add_counted_shifted: shifts is NULL",
+                       {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nev_prefix, .kind = rc::RK_COUNTED_SUM, .shifts = shifts,
+                        .count = {method, area_threshold, upsample}}); }
 RC_EXPORT int rc_sum_add_counted_shifted_submit(rc_sum *s, uint32_t slot, uint32_t nx, uint32_t ny, uint32_t upsample, uint32_t bit_depth, uint32_t level,
                                                 uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes, uint32_t n, uint32_t method,
                                                 uint32_t area_threshold, const int32_t *shifts)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted_submit: slot 0 or 1");
-    if (!shifts) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted_shifted_submit: shifts is NULL");
-    uint64_t grow = 0;
-    int r = counted_admit(s, nx, ny, upsample, bit_depth, level, sizes, n, method, &grow);
-    if (r != RC_OK) return r;
-    const CountReq req{method, area_threshold, upsample};
-    r = expand_run(slot, true, nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, nullptr, 0, 0, false, nullptr, 0, s, &req, nullptr, nullptr,
-                   shifts);
-    if (r == RC_OK) s->bound += grow;      // (queued: as rc_sum_add_counted_submit)
-    return r;
-}
+{ return counted_run(s, &slot, "rc_sum_add_counted_shifted_submit: slot 0 or 1", "rc_sum_add_counted_shifted_submit: shifts is NULL",
+                       {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_COUNTED_SUM, .shifts = shifts,
+                        .count = {method, area_threshold, upsample}}); }
 
 // ---- frame traces: per frame the set pixels, the sum, its first moments and the sums under the handle's weight planes (rc_trace.hip) ----
 // The handle owns the weights: an interleaved copy, int32[ny * nx][kp] (kp = k rounded up to a multiple of 4; the padding planes are zero),
@@ -1210,26 +1098,18 @@ static int trace_on_its_device(const rc_trace *t)
     if (r != RC_OK) return r;
     return g_util.device == t->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_trace_frames: the handle belongs to another device");
 }
-
+static int trace_run(rc_trace *t, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.trace: the handle's, filled in here)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_trace_frames_submit: slot 0 or 1");
+    int r = trace_admit(t, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
+    if (r == RC_OK) r = trace_on_its_device(t);
+    if (r != RC_OK) return r;
+    q.in.nx = t->nx; q.in.ny = t->ny; q.trace = {t->weights, t->k};
+    return expand_run(q, slot);
+}
 RC_EXPORT int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                               uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
-{
-    int r = trace_admit(t, bit_depth, level, op_mode, data, sizes, n, out, out_cells);
-    if (r == RC_OK) r = trace_on_its_device(t);
-    if (r != RC_OK) return r;
-    const TraceReq req{t->weights, t->k};
-    return expand_run(RC_READ_SLOTS, false, t->nx, t->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nnz_prefix, reinterpret_cast<uint64_t *>(out), out_cells,
-                      0, false, nullptr, 0, nullptr, nullptr, nullptr, &req);
-}
-
+{ return trace_run(t, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_TRACE, .out = out, .cap = out_cells}); }
 RC_EXPORT int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                      const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
-{
-    if (slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_trace_frames_submit: slot 0 or 1");
-    int r = trace_admit(t, bit_depth, level, op_mode, data, sizes, n, out, out_cells);
-    if (r == RC_OK) r = trace_on_its_device(t);
-    if (r != RC_OK) return r;
-    const TraceReq req{t->weights, t->k};
-    return expand_run(slot, true, t->nx, t->ny, bit_depth, level, op_mode, scheme, data, sizes, n, nullptr, reinterpret_cast<uint64_t *>(out), out_cells, 0, false,
-                      nullptr, 0, nullptr, nullptr, nullptr, &req);
-}
+{ return trace_run(t, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_TRACE, .out = out, .cap = out_cells}); }
