@@ -44,9 +44,11 @@ def _stock_decoded(h):
 def _route(h, foreign, device_blosc, device_zlib, family):
     """Which way a file's batches go, decided in this one place: ('device', the scheme code they are offered to the device decoders under),
     ('host-decode', None) - stock decoders on the thread pool, then one device call on the stored pieces - or ('per-frame', None).
-    foreign: the device decoders refused this file's streams once (ReCoDeReader._foreign_file).  family: 'triplets' (get_frames_triplets,
-    iter_frames_triplets, the read-ahead), 'l2' (get_frames_l2, iter_frames_l2) or 'sum' (sum_frames, iter_frame_sums; get_frames_counted, iter_frames_counted).  The families
-    differ, and each difference is tested behaviour: 'triplets' offers blosc-LZ4 and zlib only behind its switches (device_blosc,
+    foreign: the device decoders refused this file's streams once (ReCoDeReader._foreign_file).  family: what the ladder's kinds name
+    (_Kind.family, asked by _offer with the kind's switches) - 'triplets' (_Entries: get_frames_triplets, iter_frames_triplets, the
+    read-ahead), 'l2' (_L2: get_frames_l2, iter_frames_l2) or 'sum' (every other kind: the summed and counted views, the events, dense
+    batches, traces).  The entry points of 'triplets' and 'l2' ask it once more beforehand: a 'per-frame' file does not enter the ladder,
+    and a 'host-decode' file streams through _iter_host_decoded.  The families differ, and each difference is tested behaviour: 'triplets' offers blosc-LZ4 and zlib only behind its switches (device_blosc,
     device_zlib); 'sum' has no such history to keep and offers both by default - zlib as RC_SCHEME_ZLIB_DEVICE, which refuses every zlib
     stream but this library's own; 'l2' needs fields of 8 to 16 bits and has no host-decoded route."""
     level, mode, scheme = int(h['reduction_level']), int(h['rc_operation_mode']), int(h['compression_scheme'])
@@ -147,12 +149,14 @@ def _area_threshold(area_threshold):
 
 
 class _Kind:
-    """What the ladder of the 'sum' route family (BatchedAccess._offer / _settle) is told about the kind of result a batch becomes; one
-    small subclass per kind.  geom is a batch's tuple for rc_expand_frames - (nx, ny, bit depth, level, op_mode, scheme) -, and every
-    rung of the ladder makes the same call under another one: the file's own, the stored pieces' (.., 0, scheme) of a host-decoded batch,
-    _stored_pieces_per_frame's.  What a kind keeps between the calls for a job is in job.payload, next to the ladder's own fields."""
+    """What the ladder (BatchedAccess._offer / _settle) is told about the kind of result a batch becomes; one small subclass per kind.
+    geom is a batch's tuple for rc_expand_frames - (nx, ny, bit depth, level, op_mode, scheme) -, and every rung of the ladder makes the
+    same call under another one: the file's own, the stored pieces' (.., 0, scheme) of a host-decoded batch, _stored_pieces_per_frame's.
+    What a kind keeps between the calls for a job is in job.payload, next to the ladder's own fields."""
     what = None                           # the library call, as _lib.check's messages name it (queued: what + '_submit')
     verdict = 'rc_expand_frames_wait'     # ... and as they name a streamed batch's verdict
+    family, switches = 'sum', ()          # what _route is asked with: the route family, and (device_blosc, device_zlib) where it has them
+    retry = ()                            # verdicts of a queued batch that send it through the synchronous call once before it is judged
 
     @staticmethod
     def queues(level):
@@ -166,6 +170,12 @@ class _Kind:
         """the device call, status returned: queued on `slot`, or (None) synchronous"""
         raise NotImplementedError
 
+    def per_frame(self, reader, job):
+        """the bottom rung: the frame-at-a-time reader's frames restated as stored ones, through the same call"""
+        geom, data, sizes = reader._stored_pieces_per_frame(job.first, job.count, job.frames)
+        self.room(job, geom, sizes, job.count)
+        _lib.check(self.call(job, geom, data, sizes, job.count), self.what)
+
     def item(self, job):
         """what the stream yields for a finished job (None: nothing)"""
 
@@ -173,9 +183,16 @@ class _Kind:
 class _PlainAdder(_Kind):
     """A batch's frames added into a _lib.FrameSum, their values (rc_sum_add_frames / _submit): the job's payload names the handle (fs),
     its window and whether it is the window's last job.  fold(fs, grow), where set, is called before an add that grows fs's bound by
-    `grow` - the host-decoded and per-frame adds included, so a batch that was queued and then refused grows the bound twice."""
+    `grow` - the host-decoded and per-frame adds included, so a batch that was queued and then refused grows the bound twice.
+    shifts: None, or (dy, dx) rows for frames z0 .. z0 + n - 1 of the call, checked against n (_lib.shift_rows) (rc_sum_add_frames_shifted / _submit): every rung of the ladder -
+    the device decoders, the host-decoded batch, the per-frame restatement - then makes the shifted call, with the rows of the job's frames."""
     what = 'rc_sum_add_frames'
     fold = None
+
+    def __init__(self, z0=0, shifts=None, n=None):
+        self.z0, self.shifts = int(z0), None if shifts is None else _lib.shift_rows(shifts, n)
+        if shifts is not None:
+            self.what += '_shifted'
 
     @staticmethod
     def view_shape(nx, ny):
@@ -189,9 +206,16 @@ class _PlainAdder(_Kind):
         if self.fold is not None:
             self.fold(job.payload.fs, self.grows_by(geom, sizes, k))
 
+    def rows(self, job):
+        a = job.first - self.z0
+        return self.shifts[a:a + job.count]
+
     def call(self, job, geom, data, sizes, k, slot=None):
         fs = job.payload.fs
-        return fs.add_status(geom, data, sizes, k) if slot is None else fs.submit_status(slot, geom, data, sizes, k)
+        if self.shifts is None:
+            return fs.add_status(geom, data, sizes, k) if slot is None else fs.submit_status(slot, geom, data, sizes, k)
+        rows = self.rows(job)
+        return fs.add_shifted_status(geom, data, sizes, k, rows) if slot is None else fs.submit_shifted_status(slot, geom, data, sizes, k, rows)
 
     def item(self, job):
         return job.payload.window if job.payload.last else None
@@ -199,13 +223,15 @@ class _PlainAdder(_Kind):
 
 class _CountedAdder(_PlainAdder):
     """The counted add (rc_sum_add_counted / _submit): one count per event of the frames, the view `upsample` times finer than they are.
-    Levels 2 and 3 wait for their set-pixel count inside the call: they go through the synchronous one, like the events themselves."""
+    Levels 2 and 3 wait for their set-pixel count inside the call: they go through the synchronous one, like the events themselves.
+    shifts: as _PlainAdder's, in fine cells (rc_sum_add_counted_shifted / _submit)."""
     what = 'rc_sum_add_counted'
 
-    def __init__(self, method, area_threshold, upsample):
+    def __init__(self, method, area_threshold, upsample, z0=0, shifts=None, n=None):
         self.code, self.thr, self.s = count_method(method), _area_threshold(area_threshold), int(upsample)
         if not 1 <= self.s <= 16:
             raise ValueError('upsample must be in 1..16')
+        super().__init__(z0, shifts, n)
 
     @staticmethod
     def queues(level):
@@ -220,52 +246,12 @@ class _CountedAdder(_PlainAdder):
 
     def call(self, job, geom, data, sizes, k, slot=None):
         fs, how = job.payload.fs, (self.code, self.thr, self.s)
-        return fs.add_counted_status(geom, data, sizes, k, *how) if slot is None else fs.submit_counted_status(slot, geom, data, sizes, k, *how)
-
-
-class _ShiftedPlainAdder(_PlainAdder):
-    """_PlainAdder with per-frame shifts (rc_sum_add_frames_shifted / _submit): shifts is int32[n, 2] for frames z0 .. z0 + n - 1 of the call,
-    and every rung of the ladder - the device decoders, the host-decoded batch, the per-frame restatement - makes this call, with the rows of
-    the job's frames."""
-    what = 'rc_sum_add_frames_shifted'
-
-    def __init__(self, z0, shifts):
-        self.z0, self.shifts = int(z0), shifts
-
-    def rows(self, job):
-        a = job.first - self.z0
-        return self.shifts[a:a + job.count]
-
-    def call(self, job, geom, data, sizes, k, slot=None):
-        fs, rows = job.payload.fs, self.rows(job)
-        return fs.add_shifted_status(geom, data, sizes, k, rows) if slot is None else fs.submit_shifted_status(slot, geom, data, sizes, k, rows)
-
-
-class _ShiftedCountedAdder(_CountedAdder):
-    """_CountedAdder with per-frame shifts in fine cells (rc_sum_add_counted_shifted / _submit), on every rung like _ShiftedPlainAdder"""
-    what = 'rc_sum_add_counted_shifted'
-    rows = _ShiftedPlainAdder.rows
-
-    def __init__(self, method, area_threshold, upsample, z0, shifts):
-        super().__init__(method, area_threshold, upsample)
-        self.z0, self.shifts = int(z0), shifts
-
-    def call(self, job, geom, data, sizes, k, slot=None):
-        fs, rows, how = job.payload.fs, self.rows(job), (self.code, self.thr, self.s)
+        if self.shifts is None:
+            return fs.add_counted_status(geom, data, sizes, k, *how) if slot is None else fs.submit_counted_status(slot, geom, data, sizes, k, *how)
+        rows = self.rows(job)
         if slot is None:
             return fs.add_counted_shifted_status(geom, data, sizes, k, rows, *how)
         return fs.submit_counted_shifted_status(slot, geom, data, sizes, k, rows, *how)
-
-
-def _plain_adder(z0, n, shifts):
-    """the adder of sum_frames / iter_frame_sums: today's without shifts, the shifted one with (shifts checked against the n frames)"""
-    return _PlainAdder() if shifts is None else _ShiftedPlainAdder(z0, _lib.shift_rows(shifts, n))
-
-
-def _counted_adder(method, area_threshold, upsample, z0, n, shifts):
-    if shifts is None:
-        return _CountedAdder(method, area_threshold, upsample)
-    return _ShiftedCountedAdder(method, area_threshold, upsample, z0, _lib.shift_rows(shifts, n))
 
 
 class _Events(_Kind):
@@ -482,6 +468,123 @@ class _BatchOut:
         return (trip[:, 0].astype(np.int32), trip[:, 1].astype(np.int32), trip[:, 2].astype(np.uint32 if value_bytes == 4 else np.uint16))
 
 
+class _Entries(_Kind):
+    """A batch's set pixels as triplet rows or as the COO arrays (rc_expand_frames, _coo, _coo32 / _submit: the layout is
+    _BatchOut.for_file's).  Level 1 bounds them from the sizes and is queued; level 3 needs the counting call, which the synchronous form
+    has.  out: the caller's holder of the synchronous form (get_frames_triplets' `out`); slots: the reader's stream buffers, whose outputs
+    the queued level takes - that batch's item is a VIEW of the slot's page-locked output, valid until the generator is advanced; any
+    other batch's arrays are the call's own.  The bottom rung builds the entries on the host from the frame-at-a-time reader's frames."""
+    what, family = 'rc_expand_frames', 'triplets'
+
+    def __init__(self, header, coo=False, out=None, device_blosc=False, device_zlib=False, slots=None):
+        self.header, self.coo, self.out, self.slots = header, coo, out, slots
+        self.switches = (device_blosc, device_zlib)
+
+    @staticmethod
+    def queues(level):
+        return level == 1
+
+    def room(self, job, geom, sizes, k):
+        holder, at = (self.out, 0) if self.slots is None or geom[3] != 1 else (self.slots, 2 + job.slot)
+        job.payload.dst = _BatchOut.for_file(self.header, self.coo, holder, at)
+        if geom[3] == 1:
+            job.payload.dst.room(_l1_cap(sizes, geom[2]))
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        p, L = job.payload, _lib.lib()
+        dst, src, p.result = p.dst, tuple(geom) + (_lib.ptr(data), _lib.ptr(sizes), k), None
+        if slot is not None:
+            return dst.fn(L, submit=True)(slot, *src, dst.ptr(), dst.cap)
+        p.prefix = np.zeros(k + 1, np.uint64)
+        if geom[3] != 1:
+            st = L.rc_expand_frames(*src, _lib.ptr(p.prefix), None, 0)
+            if st != _lib.RC_OK:
+                return st
+            dst.room(max(int(p.prefix[k]), 1))
+        return dst.fn(L)(*src, _lib.ptr(p.prefix), dst.ptr(), dst.cap)
+
+    def per_frame(self, reader, job):
+        p, parts, reader.last_batch_path = job.payload, [], 'per-frame'
+        p.prefix = np.zeros(job.count + 1, np.uint64)
+        for i, m in enumerate(reader._frames_one_by_one(job.first, job.count, job.frames)):
+            m = m[0] if isinstance(m, tuple) else m
+            t = np.stack([m.row.astype(np.uint64), m.col.astype(np.uint64), m.data.astype(np.uint64)], axis=1) if m is not None and m.nnz \
+                else np.zeros((0, 3), np.uint64)
+            parts.append(t)
+            p.prefix[i + 1] = p.prefix[i] + t.shape[0]
+        trip = np.concatenate(parts) if parts else np.zeros((0, 3), np.uint64)
+        p.result = _BatchOut.from_triplets(trip, self.coo, _BatchOut.for_file(self.header, self.coo).value_bytes)
+
+    def item(self, job):
+        p = job.payload
+        return job.first, p.prefix, p.result if p.result is not None else p.dst.result(int(p.prefix[job.count]))
+
+
+class _L2(_Kind):
+    """A level-2 batch's set pixels and summary statistics (rc_expand_frames_l2 / _submit; dtype: the file's, as get_frame returns the
+    statistics).  A batch's set pixels cannot be bounded from the metadata: the synchronous call counts first; a stream's first queued
+    batch is counted as well, and every later one is given the room the densest batch delivered so far needed per frame (`densest`) plus
+    a quarter - one that still does not fit (retry) raises the estimate from its verdict's prefix and goes through the synchronous call.
+    outs, stats: the reader's stream buffers and statistics buffers, which the queued form writes; the items are copies of their own."""
+    what, family = 'rc_expand_frames_l2', 'l2'
+    retry = (_lib.RC_ERR_OUT_TOO_SMALL,)
+
+    def __init__(self, dtype, outs=None, stats=None):
+        self.dtype, self.outs, self.stats, self.densest = dtype, outs, stats, None
+
+    def room(self, job, geom, sizes, k):
+        job.payload.sp = np.zeros(k + 1, np.int64)        # the statistics prefix: one field of the file's bit depth per component
+        np.cumsum(sizes[:, 2].astype(np.int64) * 8 // geom[2], out=job.payload.sp[1:])
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        p, L = job.payload, _lib.lib()
+        shape, codec, src, ns, p.result = geom[:3], geom[4:], (_lib.ptr(data), _lib.ptr(sizes), k), int(p.sp[k]), None
+        if slot is None and p.prefix is not None:         # (a queued batch that did not fit: its verdict's prefix says what it needs)
+            self.densest = max(self.densest or 0, int(p.prefix[k]) / k)
+        if slot is None or self.densest is None:
+            prefix = np.zeros(k + 1, np.uint64)
+            st = L.rc_expand_frames(*shape, 2, *codec, *src, _lib.ptr(prefix), None, 0)      # the counting call sizes rows / columns
+            if st != _lib.RC_OK:
+                return st
+            p.cap = max(int(prefix[k]), 1)
+        else:
+            p.cap = int(self.densest * k * 1.25) + 1024
+        if slot is not None:
+            self.outs[2 + slot] = _pinned(self.outs[2 + slot], 8 * p.cap)
+            self.stats[slot] = _pinned(self.stats[slot], 2 * max(ns, 1))
+            return L.rc_expand_frames_l2_submit(slot, *shape, *codec, *src, self.outs[2 + slot]._p, p.cap, self.stats[slot]._p, ns)
+        rc, stats = np.empty(2 * p.cap, np.int32), np.empty(max(ns, 1), np.uint16)
+        st = L.rc_expand_frames_l2(*shape, *codec, *src, _lib.ptr(prefix), _lib.ptr(rc), p.cap, _lib.ptr(stats), ns)
+        tot, p.prefix = int(prefix[k]), prefix
+        if st == _lib.RC_OK:
+            p.result = rc[:tot], rc[p.cap:p.cap + tot], stats[:ns].astype(self.dtype, copy=False)
+        return st
+
+    def per_frame(self, reader, job):
+        p, n, reader.last_batch_path = job.payload, job.count, 'per-frame'
+        rows, cols, stats = [], [], []
+        p.prefix, p.sp = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.int64)
+        for i, (m, st) in enumerate(reader._frames_one_by_one(job.first, n, job.frames)):
+            if m is not None and m.nnz:
+                rows.append(m.row.astype(np.int32))
+                cols.append(m.col.astype(np.int32))
+            if st is not None:
+                stats.append(np.asarray(st, self.dtype))
+            p.prefix[i + 1] = p.prefix[i] + (m.nnz if m is not None else 0)
+            p.sp[i + 1] = p.sp[i] + (len(st) if st is not None else 0)
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+        p.result = cat(rows, np.int32), cat(cols, np.int32), cat(stats, self.dtype)
+
+    def item(self, job):
+        p, k = job.payload, job.count
+        if p.result is None:          # (the queued call delivered: copies of the slot's outputs)
+            tot, ns = int(p.prefix[k]), int(p.sp[k])
+            self.densest = max(self.densest or 0, tot / k)
+            rc = self.outs[2 + job.slot].array[:8 * p.cap].view(np.int32)
+            p.result = rc[:tot].copy(), rc[p.cap:p.cap + tot].copy(), self.stats[job.slot].array[:2 * ns].view(np.uint16).astype(self.dtype)
+        return (job.first, p.prefix) + p.result[:2] + (p.sp,) + p.result[2:]
+
+
 class BatchedAccess:
     """Mixin of ReCoDeReader: see the module docstring.  State it uses is declared in ReCoDeReader.__init__; its buffers and pools are
     ReCoDeReader._bufs (a _BatchBuffers)."""
@@ -602,25 +705,6 @@ class BatchedAccess:
         else:
             self._note_batch_end(ids[-1] + 1 if len(ids) else z0)
 
-    def _expand_now(self, mode, scheme, data, sizes, n, dst):
-        """One synchronous device call for n frames (rc_expand_frames & co. into `dst`, a _BatchOut), their streams back to back in `data`
-        and offered under (mode, scheme): (status, nnz prefix, the entries in dst's layout - None unless the status is RC_OK).  Level 1
-        bounds the output from the sizes; level 3 needs a counting call first."""
-        h = self._header
-        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
-        L = _lib.lib()
-        prefix = np.zeros(n + 1, np.uint64)
-        args = (int(h['nx']), int(h['ny']), d, level, mode, scheme, _lib.ptr(data), _lib.ptr(sizes), n)
-        if level == 1:
-            cap = _l1_cap(sizes, d)
-        else:
-            st = L.rc_expand_frames(*args, _lib.ptr(prefix), None, 0)
-            if st != _lib.RC_OK:
-                return st, prefix, None
-            cap = max(int(prefix[n]), 1)
-        st = dst.fn(L)(*args, _lib.ptr(prefix), dst.room(cap).ptr(), cap)
-        return st, prefix, dst.result(int(prefix[n])) if st == _lib.RC_OK else None
-
     def _two_slots(self, jobs, start, finish, stop=None):
         """The driver of the streaming pipelines: two jobs in flight over the list `jobs` (_Job), job j on slot j & 1 of the whole sequence.
         start(job) reads the job's bytes and queues it on the device (job.queued says whether it did); finish(job) waits for it and returns
@@ -664,18 +748,18 @@ class BatchedAccess:
         finally:
             self._user_iters -= 1
 
-    # ---- the ladder of the 'sum' route family: a batch is offered to the device decoders and falls back rung by rung ----------------------
+    # ---- the ladder: a batch is offered to the device decoders and falls back rung by rung ----------------------------------------------
     def _batch_geom(self, mode, scheme):
         h = self._header
         return int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['reduction_level']), mode, scheme
 
     def _offer(self, kind, job, sync=False):
         """The ladder's first half, _two_slots' start: the job's file bytes are read into page-locked memory - the slot's blob, or (sync)
-        the synchronous calls' - and, where the route names a device scheme, offered to the device decoders as `kind` (a _Kind) calls them:
-        queued on the job's slot, or through the synchronous call when the kind does not queue this level, when another reader holds
-        the slot, or in the synchronous form.  Of a queued call only RC_OK (job.queued), RC_ERR_UNSUPPORTED and RC_ERR_CORRUPT pass; the
-        synchronous call's status is _settle's to judge.  The job's payload keeps sizes, blob, dev (the scheme offered under, None: not
-        offered) and status."""
+        the synchronous calls' - and, where the route of the kind's family names a device scheme, offered to the device decoders as `kind`
+        (a _Kind) calls them: queued on the job's slot, or through the synchronous call when the kind does not queue this level, when
+        another reader holds the slot, or in the synchronous form.  Of a queued call only RC_OK (job.queued), RC_ERR_UNSUPPORTED and
+        RC_ERR_CORRUPT pass; the synchronous call's status is _settle's to judge.  The job's payload keeps sizes, blob, dev (the scheme
+        offered under, None: not offered), status and prefix (a waited-for verdict's)."""
         if job.payload is None:
             job.payload = SimpleNamespace()
         p, k, bufs = job.payload, job.count, self._bufs
@@ -690,7 +774,7 @@ class BatchedAccess:
             self._read_batch_into(p.blob, job.first, k)
         else:
             self._read_frames_into(p.blob, job.frames)
-        p.dev, p.status = self._route_for('sum')[1], None
+        p.dev, p.status, p.prefix = self._route_for(kind.family, *kind.switches)[1], None, None
         if p.dev is None:
             return
         geom = self._batch_geom(int(self._header['rc_operation_mode']), p.dev)
@@ -708,14 +792,17 @@ class BatchedAccess:
         p.status = kind.call(*call)
 
     def _settle(self, kind, job, sync=False):
-        """The ladder's second half, _two_slots' finish: waits for a queued job's verdict, and takes the batch down the rungs the device
-        decoders left - the stock decoders on the thread pool and the same call on the stored pieces, then the frame-at-a-time reader's
-        frames restated as stored ones (_stored_pieces_per_frame).  Sets last_batch_path; marks the file foreign when a batch that was
-        offered came out of the stock decoders instead.  Returns kind.item(job)."""
+        """The ladder's second half, _two_slots' finish: waits for a queued job's verdict (one the kind lists in `retry` sends the batch
+        through the synchronous call once, and that call's status is judged), and takes the batch down the rungs the device decoders
+        left - the stock decoders on the thread pool and the same call on the stored pieces, then the frame-at-a-time reader
+        (kind.per_frame).  Sets last_batch_path; marks the file foreign when a batch that was offered came out of the stock decoders
+        instead.  Returns kind.item(job)."""
         p, k = job.payload, job.count
         st, offered = p.status, p.dev is not None
         if job.queued:
             st, p.prefix = _wait(job)
+            if st in kind.retry:
+                st = kind.call(job, self._batch_geom(int(self._header['rc_operation_mode']), p.dev), p.blob, p.sizes, k)
         if offered and st == _lib.RC_OK:
             self.last_batch_path = _device_path(p.dev)
         elif offered and st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
@@ -724,20 +811,39 @@ class BatchedAccess:
             # refused by the device decoders (a stock encoder's streams, or damage: the stock decoder is the judge), or never theirs
             got = self._host_decode_batch(p.blob, p.sizes, k, 2) if _stock_decoded(self._header) else None
             if got is not None:
-                (data, sizes), geom, path = got, self._batch_geom(0, int(self._header['compression_scheme'])), 'host-decode + device-expand'
+                (data, sizes), geom = got, self._batch_geom(0, int(self._header['compression_scheme']))
+                kind.room(job, geom, sizes, k)
+                _lib.check(kind.call(job, geom, data, sizes, k), kind.what)
             else:
-                (geom, data, sizes), path = self._stored_pieces_per_frame(job.first, k, job.frames), 'per-frame'
-            kind.room(job, geom, sizes, k)
-            _lib.check(kind.call(job, geom, data, sizes, k), kind.what)
-            self.last_batch_path = path
+                kind.per_frame(self, job)
+            self.last_batch_path = 'host-decode + device-expand' if got is not None else 'per-frame'
             if offered and got is not None:
                 self._foreign_file = True        # not offered to the device decoders again
         return kind.item(job)
 
-    def _ladder(self, kind, jobs):
-        """the streaming form: `jobs` through _offer / _settle on the two slots, the items of `kind` yielded"""
+    def _rungs(self, kind, jobs, stop=None):
+        """the streaming form: `jobs` through _offer / _settle on the two slots, the items of `kind` yielded (stop: see _two_slots)"""
+        return self._two_slots(jobs, lambda job: self._offer(kind, job), lambda job: self._settle(kind, job), stop)
+
+    def _ladder(self, kind, jobs, stop=None):
+        """_rungs as a generator of a caller's own: the read-ahead hands over first"""
         with self._takes_over_from_readahead():
-            yield from self._two_slots(jobs, lambda job: self._offer(kind, job), lambda job: self._settle(kind, job))
+            yield from self._rungs(kind, jobs, stop)
+
+    def _now(self, kind, job):
+        """the synchronous form: one job down the ladder on the synchronous calls' blob, nothing queued; kind.item(job)"""
+        self._offer(kind, job, sync=True)
+        item = self._settle(kind, job, sync=True)
+        self._note_batch_end(job.first + job.count)
+        return item
+
+    def _straight_per_frame(self, kind, jobs):
+        """A file whose route is 'per-frame' does not enter the ladder: its batches are answered straight from kind.per_frame, nothing is
+        read into page-locked memory (the frame-at-a-time reader reads the file itself)."""
+        for job in jobs:
+            job.payload = SimpleNamespace()
+            kind.per_frame(self, job)
+            yield kind.item(job)
 
     _RA_FRAMES = 32          # frames fetched ahead once the calls turn out to be sequential
     _RA_BYTES = 512 << 20    # ... as long as their triplets fit into this much page-locked memory
@@ -857,69 +963,26 @@ class BatchedAccess:
         its tested behaviour: they read frame by frame, and callers - the read-ahead among them - see 'per-frame' in last_batch_path.
         device_zlib=True: a zlib file (compression_scheme 0) at level 1 or 3 is offered to the batched device inflate (rc_expand_frames with
         RC_SCHEME_ZLIB_DEVICE), which reads the streams of this library's device DEFLATE encoder and refuses every other zlib stream; a
-        refused file takes the host-decoded path below, as it does without the switch, and is not offered again.  last_batch_path is
+        refused file takes the host-decoded path (the ladder's next rung), as it does without the switch, and is not offered again.  last_batch_path is
         'device-inflate' for a batch the device decoded.  Off by default: the host-decoded path of such files is tested behaviour."""
-        h = self._header
-        dst = _BatchOut.for_file(h, coo, out)
         n = self._frame_range(z0, n)
-        route, dev = self._route_for('triplets', device_blosc, device_zlib)
-        if route != 'per-frame':
-            sizes, total = self._batch_sizes(z0, n)
-            self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total)        # file -> page-locked memory, no copy in between
-            blob = self._bufs.pin_blob.array[:total]
-            self._read_batch_into(blob, z0, n)
-            if route == 'device':
-                st, prefix, res = self._expand_now(int(h['rc_operation_mode']), dev, blob, sizes, n, dst)
-                if st == _lib.RC_OK:
-                    self._note_batch_end(z0 + n)
-                    self.last_batch_path = _device_path(dev)
-                    return prefix, res
-                # Outside the device decoders' subset - or a stream they could not make sense of (a foreign encoder's independent 64 KiB
-                # LZ4 blocks look like that): the paths below decode with the stock library, which is also the judge of whether
-                # the file is really damaged.
-                if st not in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                    _lib.check(st, 'rc_expand_frames')
-            if _stock_decoded(h):
-                res = self._foreign_batch_triplets(z0, n, blob, sizes, dst)
-                if res is not None:
-                    self._note_batch_end(z0 + n)
-                    self.last_batch_path = 'host-decode + device-expand'
-                    if route == 'device':            # (a host-only scheme never is the device decoders' to refuse; a zlib file the device
-                        self._foreign_file = True    # inflate refused keeps its mark through the host-decoded batches that follow)
-                    return res
-        self.last_batch_path = 'per-frame'
-        parts, prefix = [], np.zeros(n + 1, np.uint64)
-        for i, m in enumerate(self._frames_one_by_one(z0, n)):
-            m = m[0] if isinstance(m, tuple) else m
-            t = np.stack([m.row.astype(np.uint64), m.col.astype(np.uint64), m.data.astype(np.uint64)], axis=1) if m is not None and m.nnz \
-                else np.zeros((0, 3), np.uint64)
-            parts.append(t)
-            prefix[i + 1] = prefix[i] + t.shape[0]
-        return prefix, dst.from_triplets(np.concatenate(parts) if parts else np.zeros((0, 3), np.uint64), coo, dst.value_bytes)
+        kind, job = _Entries(self._header, coo, out, device_blosc, device_zlib), _Job(z0, n)
+        if self._route_for(kind.family, *kind.switches)[0] == 'per-frame':
+            return next(self._straight_per_frame(kind, [job]))[1:]
+        return self._now(kind, job)[1:]
 
     def _note_batch_end(self, z):
         if not self._is_intermediate:        # (a part file's sequential cursor is its file position, which the batched readers leave alone)
             self._current_frame_index = z
 
-    def _foreign_batch_triplets(self, z0, n, blob, sizes, dst=None):
-        """Streams a FOREIGN encoder wrote (the reference's own files: lz4.frame with linked 64 KiB blocks, libzstd with 4-stream
-        literals and real offsets) are serial chains of some 10^5 dependent steps per frame - the stock decoder on a CPU core
-        walks one in about a millisecond, a GPU lane needs ~1 us per step ("Foreign streams").  So they are decoded
-        by the SAME library calls the reference makes (recode_compressors.py:46-49), all 2 n streams of the batch at once on a
-        thread pool (the libraries release the GIL), into the stored-pieces layout of a mode-0 file, and ONE device call expands
-        them (rc_expand_frames, op_mode 0).  None: a stock decoder is not available or rejected a stream (the per-frame path
-        then reports it)."""
-        got = self._host_decode_batch(blob, sizes, n, 2)        # (an image of its own: the iterator's two may be in use between its steps)
-        if got is None:
-            return None
-        st, prefix, res = self._expand_now(0, int(self._header['compression_scheme']), *got, n, dst if dst is not None else _BatchOut())
-        _lib.check(st, 'rc_expand_frames')
-        return prefix, res
-
     def _host_decode_batch(self, blob, sizes, n, slot):
         """The 2 n streams of a batch (file bytes in `blob`, stream sizes in `sizes`) through the stock decoder of the file's scheme on the
         thread pool, each straight into its place of a stored-pieces image in page-locked memory (sizes are known beforehand: the
-        binary map's nb bytes, the value stream's bytes_in_packed_pixvals).  Returns (pieces, sizes of a mode-0 batch), or None when
+        binary map's nb bytes, the value stream's bytes_in_packed_pixvals); ONE device call then expands the image (op_mode 0).
+        Streams a FOREIGN encoder wrote (the reference's own files: lz4.frame with linked 64 KiB blocks, libzstd with 4-stream literals and
+        real offsets) are serial chains of some 10^5 dependent steps per frame - the stock decoder on a CPU core walks one in about a
+        millisecond, a GPU lane needs ~1 us per step ("Foreign streams") -, so they are decoded by the SAME library calls the
+        reference makes (recode_compressors.py:46-49), all of the batch at once (the libraries release the GIL).  Returns (pieces, sizes of a mode-0 batch), or None when
         there is no stock decoder for the scheme or it rejected a stream.  `slot` picks one of three images: two for the streaming
         iterator (a batch is decoded while the device still copies the previous one in), one for the synchronous call."""
         h = self._header
@@ -972,10 +1035,8 @@ class BatchedAccess:
         """iter_frames_triplets for files whose streams only a stock decoder takes (foreign encoders, zlib / bz2 / lzma): batch i + 1 is
         read and decoded on the host's thread pool while the device expands batch i (rc_expand_frames_submit / _wait, op_mode 0, on the
         page-locked stored-pieces image) and the consumer works on its triplets."""
-        h = self._header
-        level, scheme, d = int(h['reduction_level']), int(h['compression_scheme']), int(h['target_bit_depth'])
-        L = _lib.lib()
-        geom0 = (int(h['nx']), int(h['ny']), d, level, 0, scheme)
+        geom0 = self._batch_geom(0, int(self._header['compression_scheme']))
+        kind = _Entries(self._header, coo, slots=self._bufs.stream)
         jobs = _jobs(z0, n, batch)
         bufs = self._bufs
         coord = bufs.pool('coord', 1)
@@ -1009,26 +1070,20 @@ class BatchedAccess:
                     res = self.get_frames_triplets(job.first, job.count, coo=coo)
                 fut = coord.submit(prepare, i + 1) if i + 1 < len(jobs) else None
                 if job.payload is not None:
-                    pieces, sizes0 = job.payload
-                    res = None
-                    if level == 1:
-                        dst = _BatchOut.for_file(h, coo, bufs.stream, 2 + job.slot)
-                        cap = _l1_cap(sizes0, d)
-                        st = dst.fn(L, submit=True)(job.slot, *geom0, _lib.ptr(pieces), _lib.ptr(sizes0), job.count, dst.room(cap).ptr(), cap)
-                        if not _slot_taken(st):
-                            _lib.check(st, 'rc_expand_frames_submit')
-                            job.queued = True
-                            st, prefix = _wait(job)
-                            _lib.check(st, 'rc_expand_frames_wait')
-                            res = prefix, dst.result(int(prefix[job.count]))
-                    else:
-                        dst = _BatchOut.for_file(h, coo)
-                    if res is None:
+                    (pieces, sizes0), job.payload = job.payload, SimpleNamespace()
+                    call = (job, geom0, pieces, sizes0, job.count)
+                    kind.room(job, geom0, sizes0, job.count)
+                    st = kind.call(*call, job.slot) if kind.queues(geom0[3]) else None
+                    if st is None or _slot_taken(st):
                         # level 3 needs a counting call to size its output, and the synchronous form does both; at level 1 another
                         # iterator of this process holds the slot, and the synchronous call has resources of its own
-                        st, prefix, out = self._expand_now(0, scheme, pieces, sizes0, job.count, dst)
-                        _lib.check(st, 'rc_expand_frames')
-                        res = prefix, out
+                        _lib.check(kind.call(*call), kind.what)
+                    else:
+                        _lib.check(st, kind.what + '_submit')
+                        job.queued = True
+                        st, job.payload.prefix = _wait(job)
+                        _lib.check(st, kind.verdict)
+                    res = kind.item(job)[1:]
                     self.last_batch_path = 'host-decode + device-expand'
                 self._note_batch_end(job.first + job.count)
                 yield (job.first,) + res
@@ -1055,93 +1110,37 @@ class BatchedAccess:
         (rc_expand_frames_submit / _wait): while the device decodes one batch, the next one is read from the file, its block headers
         are walked and its bytes copied in.  Yields (first frame index, nnz_prefix uint64[k+1], triplets uint64[total, 3]) per batch
         of k <= `batch` frames; `triplets` is a VIEW of page-locked memory the device wrote directly - valid until the generator is
-        advanced (copy it to keep it).  Files the device path does not take (level 2, host-only schemes, foreign streams) go through
-        get_frames_triplets batch by batch.  coo=True: the third item is (rows int32, columns int32, values) instead of the triplet rows -
+        advanced (copy it to keep it).  The batches go down the ladder as entries (_Entries; a level-3 batch through the synchronous call,
+        which counts first); a file whose streams only a stock decoder takes - known beforehand, or found out when a batch comes out of
+        the stock decoders - goes through _iter_host_decoded (from that batch on), level 2 and what else is left frame by frame.  coo=True: the third item is (rows int32, columns int32, values) instead of the triplet rows -
         10 instead of 24 bytes per set pixel over the link (rc_expand_frames_coo_submit: values uint16), 12 for a level-1 file of more than
         16 bits (rc_expand_frames_coo32_submit: values uint32)."""
-        h = self._header
         n = self._frame_range(z0, n, batch)
-        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
-        route, dev = self._route_for('triplets', device_blosc, device_zlib)
+        kind, jobs = _Entries(self._header, coo, None, device_blosc, device_zlib, self._bufs.stream), _jobs(z0, n, batch)
+        route = self._route_for(kind.family, *kind.switches)[0]
         if route == 'host-decode':
             yield from self._iter_host_decoded(z0, n, batch, coo)  # stock decoders on the pool, one batch ahead of the device
             return
-        jobs = _jobs(z0, n, batch)
-
-        def one_call(job):
-            """the batch through the synchronous call, which knows every fall-back (and sets last_batch_path itself)"""
-            return (job.first,) + self.get_frames_triplets(job.first, job.count, coo=coo, device_blosc=device_blosc, device_zlib=device_zlib)
-        if not (route == 'device' and level == 1):       # (level 3 needs a counting call per batch: the synchronous form has it)
-            for job in jobs:
-                yield one_call(job)
+        if route == 'per-frame':
+            yield from self._straight_per_frame(kind, jobs)
             return
-        L = _lib.lib()
-        zdev = dev == _lib.RC_SCHEME_ZLIB_DEVICE
-        geom = (int(h['nx']), int(h['ny']), d, level, int(h['rc_operation_mode']), dev)
-        bufs = self._bufs.stream                         # page-locked: two input blobs, two outputs; kept until close()
-        outs = [_BatchOut.for_file(h, coo, bufs, 2), _BatchOut.for_file(h, coo, bufs, 3)]
         resume = []
-
-        def start(job):
-            """read the job's bytes into its slot's page-locked blob and queue it; not queued: 'not on the device'"""
-            sizes, total = self._batch_sizes(job.first, job.count)
-            bufs[job.slot] = _pinned(bufs[job.slot], total + 64)
-            blob = bufs[job.slot].array[:total]
-            self._read_batch_into(blob, job.first, job.count)
-            cap, dst = _l1_cap(sizes, d), outs[job.slot]
-            st = dst.fn(L, submit=True)(job.slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), job.count, dst.room(cap).ptr(), cap)
-            if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-                if zdev:
-                    self._foreign_file = True                 # another zlib encoder's file: one refused batch, the host-decoded path from here on
-            elif not _slot_taken(st):
-                _lib.check(st, 'rc_expand_frames_submit')
-                job.queued = True
-
-        def finish(job):
-            if not job.queued:
-                return one_call(job)
-            st, prefix = _wait(job)
-            if st == _lib.RC_ERR_UNSUPPORTED and zdev:        # the device inflate refused a stream: another zlib encoder's file
-                self._foreign_file = True
-            if st == _lib.RC_ERR_CORRUPT or (st == _lib.RC_ERR_UNSUPPORTED and zdev):      # the stock decoder is the judge
-                return one_call(job)
-            _lib.check(st, 'rc_expand_frames_wait')
-            self.last_batch_path = _device_path(dev)
-            return job.first, prefix, outs[job.slot].result(int(prefix[job.count]))
 
         def stop(job):
             """a batch turned out to be a foreign encoder's: the rest of the file, from `job` on, goes through the host-decoded pipeline"""
             if self._foreign_file:
                 resume.append(job.first)
             return self._foreign_file
-        yield from self._two_slots(jobs, start, finish, stop)
+        yield from self._rungs(kind, jobs, stop)         # (not _ladder: the read-ahead's own iterator must not take over from itself)
         if resume:
             yield from self._iter_host_decoded(resume[0], z0 + n - resume[0], batch, coo)
 
     # ---- level 2 in batches: set pixels and summary statistics (rc_expand_frames_l2) ------------------------------------------
-    def _l2_sizes(self, a, k):
-        """(sizes uint32[k][3], bytes of the k frames' data, statistics prefix int64[k+1]) of frames a .. a+k-1 of a level-2 file"""
-        sizes, nbytes = self._batch_sizes(a, k)
-        sp = np.zeros(k + 1, np.int64)
-        np.cumsum(sizes[:, 2].astype(np.int64) * 8 // int(self._header['target_bit_depth']), out=sp[1:])
-        return sizes, nbytes, sp
-
-    def _l2_per_frame(self, z0, n):
-        """get_frames_l2's result from the frame-at-a-time path (_get_frame_sparse): fields narrower than a byte, host-only schemes,
-        foreign or damaged streams - the stock path is the judge"""
-        self.last_batch_path = 'per-frame'
-        rows, cols, stats = [], [], []
-        prefix, sp = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.int64)
-        for i, (m, st) in enumerate(self._frames_one_by_one(z0, n)):
-            if m is not None and m.nnz:
-                rows.append(m.row.astype(np.int32))
-                cols.append(m.col.astype(np.int32))
-            if st is not None:
-                stats.append(np.asarray(st, self._numpy_dtype))
-            prefix[i + 1] = prefix[i] + (m.nnz if m is not None else 0)
-            sp[i + 1] = sp[i] + (len(st) if st is not None else 0)
-        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
-        return prefix, cat(rows, np.int32), cat(cols, np.int32), sp, cat(stats, self._numpy_dtype)
+    def _l2_kind(self, what):
+        """the _L2 kind of this file, which must be a level-2 file, and whether its batches enter the ladder (else: frame by frame)"""
+        if int(self._header['reduction_level']) != 2:
+            raise ValueError('%s reads reduction level 2 files' % what)
+        return _L2(self._numpy_dtype, self._bufs.stream, self._bufs.l2), self._route_for('l2')[0] == 'device'
 
     def get_frames_l2(self, z0, n):
         """Frames z0 .. z0+n-1 of a LEVEL-2 file (records of a part file, indexed like get_frames_triplets') in one device call
@@ -1151,101 +1150,24 @@ class BatchedAccess:
         connected component, in label order, in the file's dtype as get_frame returns them - stats[stats_prefix[i]:stats_prefix[i+1]].
         Falls back to the frame-at-a-time path (last_batch_path says which) for fields narrower than 8 bits, host-only schemes and
         streams the device decoders refuse."""
-        h = self._header
-        if int(h['reduction_level']) != 2:
-            raise ValueError('get_frames_l2 reads reduction level 2 files')
-        n = self._frame_range(z0, n)
-        if self._route_for('l2')[0] != 'device':
-            return self._l2_per_frame(z0, n)
-        sizes, total, sp = self._l2_sizes(z0, n)
-        self._bufs.pin_blob = _pinned(self._bufs.pin_blob, total)
-        blob = self._bufs.pin_blob.array[:total]
-        self._read_batch_into(blob, z0, n)
-        L = _lib.lib()
-        geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']))
-        codec = (int(h['rc_operation_mode']), int(h['compression_scheme']))
-        src = (_lib.ptr(blob), _lib.ptr(sizes), n)
-        prefix = np.zeros(n + 1, np.uint64)
-        st = L.rc_expand_frames(*geom, 2, *codec, *src, _lib.ptr(prefix), None, 0)          # the counting call sizes rows / columns
-        if st == _lib.RC_OK:
-            cap, ns = max(int(prefix[n]), 1), int(sp[n])
-            rc, stats = np.empty(2 * cap, np.int32), np.empty(max(ns, 1), np.uint16)
-            st = L.rc_expand_frames_l2(*geom, *codec, *src, _lib.ptr(prefix), _lib.ptr(rc), cap, _lib.ptr(stats), ns)
-        if st in (_lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT):
-            return self._l2_per_frame(z0, n)
-        _lib.check(st, 'rc_expand_frames_l2')
-        self._note_batch_end(z0 + n)
-        self.last_batch_path = 'device'
-        tot = int(prefix[n])
-        return prefix, rc[:tot], rc[cap:cap + tot], sp, stats[:ns].astype(self._numpy_dtype, copy=False)
+        kind, laddered = self._l2_kind('get_frames_l2')
+        job = _Job(z0, self._frame_range(z0, n))
+        return (self._now(kind, job) if laddered else next(self._straight_per_frame(kind, [job])))[1:]
 
     def iter_frames_l2(self, z0=0, n=None, batch=64):
         """Streams a level-2 file through rc_expand_frames_l2_submit / rc_expand_frames_wait, two batches in flight like
         iter_frames_triplets: yields (first frame index, nnz_prefix, rows, columns, stats_prefix, stats) per batch of up to `batch` frames
         (get_frames_l2's items).  rows / columns / stats are copies of their own.  A level-2 batch's set pixels cannot be bounded from
         the metadata, so the first batch is counted on the device and every later one is given the room the densest batch so far
-        needed per frame plus a quarter; a batch that still does not fit - or that the device path does not take - goes through
-        get_frames_l2."""
-        h = self._header
-        if int(h['reduction_level']) != 2:
-            raise ValueError('iter_frames_l2 reads reduction level 2 files')
-        n = self._frame_range(z0, n, batch)
-        jobs = _jobs(z0, n, batch)
-
-        def one_call(job):
-            """the batch through get_frames_l2, which has resources of its own and knows the fall-back"""
-            return (job.first,) + self.get_frames_l2(job.first, job.count)
-        if self._route_for('l2')[0] != 'device':
-            for job in jobs:
-                yield one_call(job)
+        needed per frame plus a quarter; a batch that still does not fit goes through the synchronous call, which counts first, and one
+        the device path does not take goes frame by frame (_L2)."""
+        kind, laddered = self._l2_kind('iter_frames_l2')
+        jobs = _jobs(z0, self._frame_range(z0, n, batch), batch)
+        if laddered:
+            yield from self._ladder(kind, jobs)
             return
-        L = _lib.lib()
-        geom = (int(h['nx']), int(h['ny']), int(h['target_bit_depth']), int(h['rc_operation_mode']), int(h['compression_scheme']))
-        bufs, sbufs = self._bufs.stream, self._bufs.l2
-        per_frame = [None]                                     # set pixels per frame of the densest batch so far
-
-        def start(job):
-            """read, size and queue the job: its payload is (room for set pixels, statistics prefix)"""
-            k, slot = job.count, job.slot
-            sizes, total, sp = self._l2_sizes(job.first, k)
-            bufs[slot] = _pinned(bufs[slot], total + 64)
-            blob = bufs[slot].array[:total]
-            self._read_batch_into(blob, job.first, k)
-            if per_frame[0] is None:
-                prefix = np.zeros(k + 1, np.uint64)
-                st = L.rc_expand_frames(*geom[:3], 2, *geom[3:], _lib.ptr(blob), _lib.ptr(sizes), k, _lib.ptr(prefix), None, 0)
-                if st != _lib.RC_OK:
-                    return
-                cap = max(int(prefix[k]), 1)
-            else:
-                cap = int(per_frame[0] * k * 1.25) + 1024
-            ns = int(sp[k])
-            bufs[2 + slot] = _pinned(bufs[2 + slot], 8 * cap)
-            sbufs[slot] = _pinned(sbufs[slot], 2 * max(ns, 1))
-            st = L.rc_expand_frames_l2_submit(slot, *geom, _lib.ptr(blob), _lib.ptr(sizes), k, bufs[2 + slot]._p, cap, sbufs[slot]._p, ns)
-            # not queued: outside the device subset, or ANOTHER iterator holds the slot
-            if st not in (_lib.RC_OK, _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT) and not _slot_taken(st):
-                _lib.check(st, 'rc_expand_frames_l2_submit')
-            job.payload, job.queued = SimpleNamespace(cap=cap, sp=sp), st == _lib.RC_OK
-
-        def finish(job):
-            if not job.queued:
-                return one_call(job)
-            k, cap, sp = job.count, job.payload.cap, job.payload.sp
-            st, prefix = _wait(job)
-            if st == _lib.RC_ERR_OUT_TOO_SMALL:
-                per_frame[0] = max(per_frame[0] or 0, int(prefix[k]) / k)
-            if st in (_lib.RC_ERR_CORRUPT, _lib.RC_ERR_OUT_TOO_SMALL):
-                return one_call(job)
-            _lib.check(st, 'rc_expand_frames_wait')
-            tot, ns = int(prefix[k]), int(sp[k])
-            per_frame[0] = max(per_frame[0] or 0, tot / k)
-            rc = bufs[2 + job.slot].array[:8 * cap].view(np.int32)
-            self.last_batch_path = 'device'
-            return (job.first, prefix, rc[:tot].copy(), rc[cap:cap + tot].copy(), sp,
-                    sbufs[job.slot].array[:2 * ns].view(np.uint16).astype(self._numpy_dtype))
         with self._takes_over_from_readahead():
-            yield from self._two_slots(jobs, start, finish)
+            yield from self._straight_per_frame(kind, jobs)
 
     # ---- summed views (rc_sum_*): frames added up on the device, nothing per set pixel over the link --------------------------------
     def _stored_pieces_per_frame(self, a, k, frames=None):
@@ -1302,8 +1224,8 @@ class BatchedAccess:
         pixel (r, c) it then adds to (r + dy_f, c + dx_f), and what leaves the view is dropped (rc_sum_add_frames_shifted, on every route).
         A float dtype, another shape or a value outside int32 is a ValueError."""
         n = self._frame_range(z0, n, batch)
-        self._sum_check_file()
-        return self._sum_into(z0, n, batch, into, _plain_adder(z0, n, shifts))
+        self._check_levels_and_bits(*self._SUMS)
+        return self._sum_into(z0, n, batch, into, _PlainAdder(z0, shifts, n))
 
     def _sum_into(self, z0, n, batch, into, adder):
         """sum_frames and sum_frames_counted behind their argument checks"""
@@ -1328,13 +1250,18 @@ class BatchedAccess:
             if into is None:
                 fs.close()
 
-    def _sum_check_file(self):
-        h = self._header
-        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
+    # (what the summed views, the counting and the traces do not take, as _check_levels_and_bits words it: who refuses, and why 16 bits)
+    _SUMS = ('sum_frames', 'the cells of a summed view are uint32')
+    _COUNTS = ('counting', 'the sums are exact in 64 bits for 16-bit values')
+    _TRACES = ('frame traces', 'the sums are exact in 64 bits for 16-bit values')
+
+    def _check_levels_and_bits(self, who, why):
+        """levels 1 to 3, and at level 1 fields of 16 bits at most: NotImplementedError otherwise"""
+        level, d = int(self._header['reduction_level']), int(self._header['target_bit_depth'])
         if level not in (1, 2, 3):
-            raise NotImplementedError('sum_frames: reduction level %d' % level)
+            raise NotImplementedError('%s: reduction level %d' % (who, level))
         if level == 1 and d > 16:
-            raise NotImplementedError('sum_frames: files of more than 16 bits (target_bit_depth %d): the cells of a summed view are uint32' % d)
+            raise NotImplementedError('%s: files of more than 16 bits (target_bit_depth %d): %s' % (who, d, why))
 
     def iter_frame_sums(self, frames_per_view, z0=0, n=None, batch=64, shifts=None):
         """Views of `frames_per_view` consecutive frames each (the last one of what is left): yields (first index, count, uint32[ny, nx]) -
@@ -1346,8 +1273,8 @@ class BatchedAccess:
         if frames_per_view <= 0 or batch <= 0:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
-        self._sum_check_file()
-        yield from self._iter_sums(frames_per_view, z0, n, batch, _plain_adder(z0, n, shifts))
+        self._check_levels_and_bits(*self._SUMS)
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _PlainAdder(z0, shifts, n))
 
     def _iter_sums(self, frames_per_view, z0, n, batch, adder):
         """iter_frame_sums and iter_frame_sums_counted behind their argument checks"""
@@ -1365,15 +1292,6 @@ class BatchedAccess:
                 v.close()
 
     # ---- electron counting (rc_count_frames): one event per connected component, labelled and reduced on the device -------------------
-    def _count_check_file(self):
-        h = self._header
-        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
-        if level not in (1, 2, 3):
-            raise NotImplementedError('counting: reduction level %d' % level)
-        if level == 1 and d > 16:
-            raise NotImplementedError('counting: files of more than 16 bits (target_bit_depth %d): the sums are exact in 64 bits for '
-                                      '16-bit values' % d)
-
     def _count_stream(self, z0, n, batch, area_threshold, method):
         """The engine of get_frames_counted and iter_frames_counted: the batches go down the ladder as events (_Events:
         rc_count_frames_submit / rc_expand_frames_wait on the two slots), so the next batch is read from the file and queued before this
@@ -1393,7 +1311,7 @@ class BatchedAccess:
         for.  Only the events cross the link (20 bytes each).  Routes and last_batch_path as for sum_frames; files of more than 16 bits are
         not taken (NotImplementedError)."""
         n = self._frame_range(z0, n)
-        self._count_check_file()
+        self._check_levels_and_bits(*self._COUNTS)
         stream = self._count_stream(z0, n, n, area_threshold, method)      # (one batch of n frames)
         try:
             return next(stream)[1:]
@@ -1404,7 +1322,7 @@ class BatchedAccess:
         """get_frames_counted for a whole file, streamed: yields (first frame index, nev_prefix, rows, cols, area, weight) per batch of up to
         `batch` frames, two batches in flight (rc_count_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
         n = self._frame_range(z0, n, batch)
-        self._count_check_file()
+        self._check_levels_and_bits(*self._COUNTS)
         count_method(method)
         yield from self._count_stream(z0, n, batch, area_threshold, method)
 
@@ -1423,9 +1341,9 @@ class BatchedAccess:
         shifts: as for sum_frames, in FINE cells (1 / upsample pixel): the event is placed on the fine grid and then translated, so an
         integer shift is a drift correction at 1 / upsample-pixel resolution (rc_sum_add_counted_shifted)."""
         n = self._frame_range(z0, n, batch)
-        self._sum_check_file()
-        self._count_check_file()
-        return self._sum_into(z0, n, batch, into, _counted_adder(method, area_threshold, upsample, z0, n, shifts))
+        self._check_levels_and_bits(*self._SUMS)
+        self._check_levels_and_bits(*self._COUNTS)
+        return self._sum_into(z0, n, batch, into, _CountedAdder(method, area_threshold, upsample, z0, shifts, n))
 
     def iter_frame_sums_counted(self, frames_per_view, z0=0, n=None, batch=64, area_threshold=0, method='weighted_average', upsample=1, shifts=None):
         """iter_frame_sums with sum_frames_counted's images: yields (first index, count, uint32[upsample * ny, upsample * nx]) per window of
@@ -1433,9 +1351,9 @@ class BatchedAccess:
         if frames_per_view <= 0 or batch <= 0:
             raise ValueError('frames_per_view and batch must be positive')
         n = self._frame_range(z0, n, batch)
-        self._sum_check_file()
-        self._count_check_file()
-        yield from self._iter_sums(frames_per_view, z0, n, batch, _counted_adder(method, area_threshold, upsample, z0, n, shifts))
+        self._check_levels_and_bits(*self._SUMS)
+        self._check_levels_and_bits(*self._COUNTS)
+        yield from self._iter_sums(frames_per_view, z0, n, batch, _CountedAdder(method, area_threshold, upsample, z0, shifts, n))
 
     # ---- dense frame batches (rc_expand_frames_dense): a region of every frame as an array, written on the device --------------------------
     _DENSE_BYTES = 256 << 20      # the dense output of a batch the streaming calls size themselves (8 frames of 4096 x 4096 uint16)
@@ -1516,9 +1434,7 @@ class BatchedAccess:
                 raise ValueError('get_frames_dense: out must be contiguous, of shape %s and %d bytes an element' % (shape, dt.itemsize))
             dst = int(out.data_ptr())
         kind, job = _Dense(region, dt, dst=dst), _Job(z0, n)
-        self._offer(kind, job, sync=True)        # (the ladder in its synchronous form: nothing is queued, `out` is written in place)
-        self._settle(kind, job, sync=True)
-        self._note_batch_end(z0 + n)
+        self._now(kind, job)        # (the ladder in its synchronous form: nothing is queued, `out` is written in place)
         return out
 
     def iter_frames_dense(self, z0=0, n=None, batch=None, roi=None):
@@ -1558,15 +1474,6 @@ class BatchedAccess:
         return vol[0 if dz else slice(None), 0 if dy else slice(None), 0 if dx else slice(None)]
 
     # ---- frame traces (rc_trace_frames): a few exact integers per frame, reduced on the device --------------------------------------------
-    def _trace_check_file(self):
-        h = self._header
-        level, d = int(h['reduction_level']), int(h['target_bit_depth'])
-        if level not in (1, 2, 3):
-            raise NotImplementedError('frame traces: reduction level %d' % level)
-        if level == 1 and d > 16:
-            raise NotImplementedError('frame traces: files of more than 16 bits (target_bit_depth %d): the sums are exact in 64 bits for '
-                                      '16-bit values' % d)
-
     def _trace_handle(self, weights):
         """(the _lib.FrameTrace to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
         nx, ny = int(self._header['nx']), int(self._header['ny'])
@@ -1600,7 +1507,7 @@ class BatchedAccess:
         in which a column could pass 2^63 - 1 raises ValueError.  Routes (last_batch_path) and fall-backs as for sum_frames; files of more
         than 16 bits are not taken (NotImplementedError)."""
         n = self._frame_range(z0, n)
-        self._trace_check_file()
+        self._check_levels_and_bits(*self._TRACES)
         ft, own = self._trace_handle(weights)
         stream = self._trace_stream(z0, n, n, ft)      # (one batch of n frames)
         try:
@@ -1614,7 +1521,7 @@ class BatchedAccess:
         """get_frame_traces for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two batches in
         flight (rc_trace_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
         n = self._frame_range(z0, n, batch)
-        self._trace_check_file()
+        self._check_levels_and_bits(*self._TRACES)
         ft, own = self._trace_handle(weights)
         stream = self._trace_stream(z0, n, batch, ft)
         try:

@@ -426,3 +426,78 @@ def test_device_blosc_switch_routes_level1_blosc_files_through_the_device(tmp_pa
         list(rd.iter_frames_triplets(batch=3, coo=coo))
         assert rd.last_batch_path == 'per-frame'
     rd.close()
+
+
+def _write_sparse_then_dense(tmp_path, base, seed):
+    """a level-2 blosc-LZ4 file of 7 frames of 72 x 136: frames 0..2 hold 4 set pixels each, frames 3..5 about 5 %, frame 6 about 15 %"""
+    from pyrecode_amd.recode_reader import merge_parts
+    ny, nx, d, nz = 72, 136, 12, 7
+    dark, frames = synth_frames(seed, nz, ny, nx, 0.05, d)
+    rng = np.random.default_rng(seed + 1)
+    for z in range(3):
+        frames[z] = dark // 2
+        at = rng.choice(ny * nx, 4, replace=False)
+        frames[z].reshape(-1)[at] = dark.reshape(-1)[at] + 500
+    frames[6] = np.where(rng.random((ny, nx)) < 0.15, dark + rng.integers(1, 2000, (ny, nx)), dark // 2).astype(np.uint16)
+    sub = tmp_path / base
+    sub.mkdir()
+    over = dict(num_rows=ny, num_cols=nx, num_frames=nz, num_threads=1, compression_scheme=8, reduction_level=2,
+                calibration_threshold_epsilon=0, l2_statistics=2)
+    _write_parts(sub, base, dark, frames, 1, load_npz("g3_l1z12.npz"), batch_size=3, **over)
+    merge_parts(str(sub), base + ".rc2", 1)
+    return str(sub / (base + ".rc2")), nz
+
+
+def test_iter_frames_l2_retries_a_batch_its_estimate_was_too_small_for(hip, tmp_path, monkeypatch):
+    """iter_frames_l2 sizes a batch from the densest batch DELIVERED so far.  Frames 0..2 hold 4 set pixels each, frames 3..5 about 5 % of
+    72 x 136 and frame 6 about 15 %.  In batches of three, batch j + 1 is queued before batch j is waited for: the first two batches are
+    both counted on the device, and the third - frame 6 alone, queued when only the first batch has been delivered - is given
+    1 * 4 * 1.25 + 1024 = 1029 entries and needs about 1470.  Its verdict is RC_ERR_OUT_TOO_SMALL and it goes through the synchronous
+    call; every item still equals get_frame's pixels and statistics, and every batch was decoded on the device."""
+    from pyrecode_amd import reader_batched as rb
+    from pyrecode_amd.recode_reader import ReCoDeReader
+    path, nz = _write_sparse_then_dense(tmp_path, "grow", 57)
+    rd = ReCoDeReader(path)
+    rd.open(print_header=False)
+    want = _l2_reference(rd, nz)
+    assert all(0 < w[0].size <= 4 for w in want[:3]) and all(400 < w[0].size < 600 for w in want[3:6]) and want[6][0].size > 1 * 4 * 1.25 + 1024
+    verdicts, wait = [], rb._wait
+    monkeypatch.setattr(rb, "_wait", lambda job: (verdicts.append(wait(job)), verdicts[-1])[1])
+    firsts = []
+    for item in rd.iter_frames_l2(batch=3):
+        assert rd.last_batch_path == 'device'
+        _check_l2_batch(want, item[0], *item[1:], rd._numpy_dtype)
+        firsts.append((item[0], len(item[1]) - 1))
+    assert firsts == [(0, 3), (3, 3), (6, 1)]
+    assert [st for st, _ in verdicts] == [hip.RC_OK, hip.RC_OK, hip.RC_ERR_OUT_TOO_SMALL]
+    rd.close()
+
+
+def test_two_level2_iterators_side_by_side(hip, tmp_path, monkeypatch):
+    """test_gpu_api.py::test_two_streaming_iterators_side_by_side for level 2: two readers of two level-2 files advanced in turn both
+    deliver every frame, and a submit did find its slot held by the other reader's batch - that batch went through the synchronous call."""
+    from pyrecode_amd import reader_batched as rb
+    from pyrecode_amd.recode_reader import ReCoDeReader
+    sets = []
+    for base, seed in (("one", 61), ("two", 67)):
+        path, nz = _write_sparse_then_dense(tmp_path, base, seed)
+        rd = ReCoDeReader(path)
+        rd.open(print_header=False)
+        sets.append((rd, _l2_reference(rd, nz)))
+    taken, asked = [], rb._slot_taken
+    monkeypatch.setattr(rb, "_slot_taken", lambda st: (taken.append(asked(st)), taken[-1])[1])      # (a count of the submits that found a slot held)
+    its = [rd.iter_frames_l2(batch=2) for rd, _ in sets]
+    seen, alive = [0, 0], [True, True]
+    while any(alive):
+        for j in (0, 1):
+            item = next(its[j], None) if alive[j] else None
+            if item is None:
+                alive[j] = False
+                continue
+            rd, want = sets[j]
+            assert rd.last_batch_path == 'device'
+            _check_l2_batch(want, item[0], *item[1:], rd._numpy_dtype)
+            seen[j] += len(item[1]) - 1
+    assert seen == [nz, nz] and any(taken), "no batch found its slot taken: the synchronous call was not exercised"
+    for rd, _ in sets:
+        rd.close()

@@ -648,6 +648,66 @@ def test_the_ladder_of_the_sum_family_rung_by_rung(monkeypatch):
     assert calls(log) == [("call", 0, "sync", 1, 2)] and r.last_batch_path is None
 
 
+def test_the_ladder_of_a_kind_with_a_family_a_bottom_rung_and_a_retry_of_its_own(monkeypatch):
+    """What the triplets and level-2 kinds add to the ladder, on the recording fakes of the test above (three jobs of two frames, no
+    device): the route is asked with the kind's family and switches; a per_frame override is the bottom rung instead of
+    _stored_pieces_per_frame; a queued batch whose verdict the kind lists in `retry` goes through the synchronous call once, and that
+    call's status is what is judged; `stop` ends the stream once a settled job has marked the file foreign."""
+    from pyrecode_amd import _lib, reader_batched as rb
+    UNS, BAD, SMALL = _lib.RC_ERR_UNSUPPORTED, _lib.RC_ERR_CORRUPT, _lib.RC_ERR_OUT_TOO_SMALL
+    items = ["item 0", "item 1", "item 2"]
+
+    def ladder(family=None, switches=None, per_frame=False, retry=None, asked=None, **kw):
+        r, kind, jobs, log = _recording_ladder(monkeypatch, **kw)
+        if family is not None:
+            kind.family, kind.switches = family, switches
+            route = type(r)._route_for
+            monkeypatch.setattr(type(r), "_route_for", lambda self, fam, *sw: (asked.append((fam,) + sw), route(self, 'sum'))[1])
+        if per_frame:
+            kind.per_frame = lambda reader, job: log.append(("per_frame", reader is r, jobs.index(job)))
+        if retry is not None:
+            kind.retry = retry
+        return r, kind, jobs, log
+    # family and switches: _route_for receives exactly those, once per job
+    asked = []
+    r, kind, jobs, log = ladder('triplets', (True, False), asked=asked, dev=2)
+    assert list(r._ladder(kind, jobs)) == items and asked == [('triplets', True, False)] * 3 and r.last_batch_path == "device"
+    # a per_frame override is called at the bottom rung, _stored_pieces_per_frame is not, and the path is 'per-frame'
+    for kw in (dict(dev=2, queued=BAD, stock=False), dict(dev=2, wait=UNS, host_decodes=False), dict(dev=None, stock=False)):
+        r, kind, jobs, log = ladder(per_frame=True, **kw)
+        assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("per-frame", False), kw
+        assert [e for e in log if e[0] == "per_frame"] == [("per_frame", True, j) for j in range(3)], kw
+        assert not any(e[0] == "frame by frame" or e[0] == "call" and e[3:] == (0, 0) for e in log), kw
+    r, kind, jobs, log = ladder(per_frame=True, dev=2, sync=BAD, stock=False)
+    r._offer(kind, jobs[0], sync=True)
+    assert r._settle(kind, jobs[0], sync=True) == "item 0" and r.last_batch_path == "per-frame"
+    assert [e for e in log if e[0] in ("call", "per_frame", "frame by frame")] == [("call", 0, "sync", 1, 2), ("per_frame", True, 0)]
+    # retry: the wait's verdict is listed - exactly one synchronous call follows, with the queued call's arguments, and its status is judged
+    r, kind, jobs, log = ladder(retry=(SMALL,), dev=2, wait=SMALL)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("device", False)
+    assert [e for e in log if e[1:2] == (1,)] == [("read", 1, 16), ("room", 1, 1, 2), ("call", 1, "slot 1", 1, 2), ("wait", 1), ("call", 1, "sync", 1, 2)]
+    assert all(len(a) == 2 and a[0] == a[1] for a in kind.args.values()) and not any(e[0] in ("host-decode", "frame by frame") for e in log)
+    r, kind, jobs, log = ladder(retry=(SMALL,), dev=2, wait=SMALL, sync=UNS)            # (the synchronous call's refusal goes down the rungs)
+    assert list(r._ladder(kind, jobs)) == items and (r.last_batch_path, r._foreign_file) == ("host-decode + device-expand", True)
+    assert [e for e in log if e[0] == "call" and e[1] == 0] == [("call", 0, "slot 0", 1, 2), ("call", 0, "sync", 1, 2), ("call", 0, "sync", 0, 2)]
+    r, kind, jobs, log = ladder(retry=(SMALL,), dev=2, wait=SMALL, sync=SMALL)          # (once: the same status from the synchronous call raises)
+    with pytest.raises(ValueError, match="rc_expand_frames_wait"):
+        list(r._ladder(kind, jobs))
+    assert [e for e in log if e[0] == "call" and e[1] == 0] == [("call", 0, "slot 0", 1, 2), ("call", 0, "sync", 1, 2)]
+    assert r.last_batch_path is None and not any(j.queued for j in jobs)
+    r, kind, jobs, log = ladder(dev=2, wait=SMALL)                                      # (a kind that lists nothing: the verdict raises as it is)
+    with pytest.raises(ValueError, match="rc_expand_frames_wait"):
+        list(r._ladder(kind, jobs))
+    assert not any(e[:3] == ("call", 0, "sync") for e in log)
+    # stop: job 0 comes out of the stock decoders and marks the file; job 1, queued meanwhile, is waited for and not delivered
+    r, kind, jobs, log = ladder(dev=2, wait=UNS)
+    stopped = []
+    gen = r._ladder(kind, jobs, stop=lambda job: (stopped.append((jobs.index(job), r._foreign_file)), r._foreign_file)[1])
+    assert list(gen) == ["item 0"] and stopped == [(0, False), (1, True)] and r._foreign_file
+    assert [e for e in log if e[0] == "wait"] == [("wait", 0), ("wait", 1)] and not any(j.queued for j in jobs)
+    assert not any(e[0] in ("read", "room", "call") and e[1] == 2 for e in log) and [e for e in log if e[0] == "call" and e[1] == 1] == [("call", 1, "slot 1", 1, 2)]
+
+
 # (family, reduction level, operation mode, _foreign_file, then one string per (device_blosc, device_zlib) = (F, F), (F, T), (T, F), (T, T)
 # with one letter per compression scheme 0, 1, 2, 4, 5, 8): D = 'device' under the file's scheme, Z = 'device' under RC_SCHEME_ZLIB_DEVICE,
 # H = 'host-decode', P = 'per-frame'
