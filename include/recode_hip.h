@@ -539,6 +539,37 @@ int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t reduction_level, u
                     const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix);
 int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
                            const uint8_t *data, const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells);
+/* ---- correlation surfaces: per frame the overlap with a reference image over a window of offsets -----------------------------
+ * What drift estimation needs of every frame, and what a caller otherwise computes with a whole-frame FFT per fraction around
+ * ReCoDeReader.get_frame (pyrecode/recode_reader.py:379-471).  A batch is decoded and counted exactly as by rc_expand_frames, and in
+ * place of the emit kernel the kernels of rc_corr.hip write, for frame f and its set pixels (row, col) of stored value v (level 1: the
+ * bit_depth-bit field; levels 2 and 3: 1), with S = 2 * radius + 1 and T the handle's reference (0 outside the image),
+ *   out[f][dy + R][dx + R] = sum v * T[row + dy][col + dx],   -R <= dy, dx <= R
+ * int64[n][S][S], row-major, exact: the overlap with T of frame f translated by (dy, dx) - the sign convention of the shifted adds
+ * (rc_sum_add_frames_shifted), so the argmax is the (dy, dx) to pass there.  The centre cell is rc_trace_frames' column under the
+ * plane T; the surface of a smaller radius is the centre crop of a larger one's.  A frame without a set pixel gives zeros; EVERY cell
+ * is written exactly once: out needs no memset.
+ *   rc_corr_create  nx, ny: the frames' shape, 1..65535; radius 0..16; reference: int32[ny][nx] in C order, host or device memory,
+ *                   copied into the handle with a border of `radius` zeros - the caller's may go away.  A device reference is read on the
+ *                   library's own stream: the ordering rule of rc_trace_create's planes.  NULL with *status set on failure:
+ *                   RC_ERR_BAD_ARG (radius > 16, a shape of 0 or above 65535, reference NULL), RC_ERR_DEVICE without a GPU.  The handle
+ *                   lives on the caller's current GPU (RC_DEVICE) and is read-only after create, so batches on both slots may use one
+ *                   handle.  One thread uses a handle at a time.
+ *   rc_corr_side             2 * radius + 1
+ *   rc_corr_reference_bound  max |T| as uint32 (INT32_MIN counts as 2^31)
+ * No silent wrap, by the rule of the traces with max |T| as the one weight: a batch with max |T| * vmax * P_f > 2^63 - 1 for any frame
+ * is refused with RC_ERR_OUT_TOO_SMALL before any device work.  out, nnz_prefix, the refusals (out_cells < n * S * S is
+ * RC_ERR_OUT_TOO_SMALL), their order before any device work, and "a refused batch writes NOTHING to out" are rc_trace_frames';
+ * rc_corr_frames_submit queues the batch on slot 0 or 1 as rc_trace_frames_submit does, rc_expand_frames_wait gives the verdict. */
+typedef struct rc_corr rc_corr;
+rc_corr *rc_corr_create(uint32_t nx, uint32_t ny, uint32_t radius, const int32_t *reference, int *status);
+int rc_corr_destroy(rc_corr *c);
+uint32_t rc_corr_side(const rc_corr *c);
+uint32_t rc_corr_reference_bound(const rc_corr *c);
+int rc_corr_frames(rc_corr *c, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                   const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix);
+int rc_corr_frames_submit(rc_corr *c, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                          const uint8_t *data, const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

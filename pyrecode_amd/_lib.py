@@ -98,6 +98,12 @@ SIGNATURES = {
     "rc_trace_weight_bound": (C.c_uint32, [C.c_void_p, C.c_uint32]),
     "rc_trace_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
     "rc_trace_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "rc_corr_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
+    "rc_corr_destroy": (C.c_int, [C.c_void_p]),
+    "rc_corr_side": (C.c_uint32, [C.c_void_p]),
+    "rc_corr_reference_bound": (C.c_uint32, [C.c_void_p]),
+    "rc_corr_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
+    "rc_corr_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
     "rc_host_decode_streams": (C.c_int, [C.c_uint32, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32]),
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -361,6 +367,51 @@ class FrameSum:
     __del__ = close
 
 
+def int32_planes(weights, nx, ny, max_planes, who, what="weights"):
+    """(the planes as C-contiguous int32[k, ny, nx] - numpy, or torch on the GPU -, k): what FrameTrace takes as weights and FrameCorrelation
+    as its reference (max_planes 1).  `who` and `what` word the ValueError of anything else."""
+    if weights is None:
+        return None, 0
+    on_gpu = hasattr(weights, "data_ptr") and not isinstance(weights, np.ndarray)
+    if on_gpu and not weights.is_cuda:
+        weights, on_gpu = weights.numpy(), False
+    if not on_gpu and not isinstance(weights, np.ndarray):
+        raise ValueError("%s: %s must be a numpy array or a torch tensor" % (who, what))
+    shape = tuple(int(v) for v in weights.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1:] != (ny, nx) or not 1 <= shape[0] <= max_planes:
+        raise ValueError("%s: %s of shape %s - (ny, nx) or (k, ny, nx) with ny, nx = %d, %d and 1 <= k <= %d"
+                         % (who, what, tuple(weights.shape), ny, nx, max_planes))
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    if on_gpu:
+        import torch
+        if weights.dtype.is_floating_point or weights.dtype.is_complex or weights.dtype == torch.bool:
+            raise ValueError("%s: %s of dtype %s (an integer dtype that fits int32)" % (who, what, weights.dtype))
+        # The library runs on the caller's current device (RC_DEVICE overrides it) and on streams of its own: the tensor must live on that
+        # device, and everything queued on it - the kernels that produced the weights, the int32 copy below - must have finished before
+        # the handle's create call reads it (the library's streams are not ordered behind torch's).
+        lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
+        if weights.device.index != lib_device:
+            raise ValueError("%s: %s on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (who, what, weights.device, lib_device))
+        if weights.dtype not in (torch.int8, torch.int16, torch.int32, torch.uint8) and weights.numel():
+            # (unsigned 32- and 64-bit values are judged through the signed view of the same width: what does not fit int32 is negative
+            # there, or above 2^31 - 1; torch reduces signed dtypes only)
+            signed = {getattr(torch, "uint16", None): torch.int32, getattr(torch, "uint32", None): torch.int32, getattr(torch, "uint64", None): torch.int64}
+            seen = weights if weights.dtype not in signed else weights.to(torch.int32) if weights.element_size() == 2 else weights.view(signed[weights.dtype])
+            floor = lo if weights.dtype not in signed else 0
+            if not (floor <= int(seen.min()) and int(seen.max()) <= hi):
+                raise ValueError("%s: %s do not fit int32" % (who, what))
+        planes = weights.reshape(shape).to(torch.int32).contiguous()
+        torch.cuda.synchronize(weights.device)
+        return planes, shape[0]
+    if weights.dtype.kind not in "iu":
+        raise ValueError("%s: %s of dtype %s (an integer dtype that fits int32)" % (who, what, weights.dtype))
+    if weights.size and not (lo <= int(weights.min()) and int(weights.max()) <= hi):
+        raise ValueError("%s: %s do not fit int32" % (who, what))
+    return np.ascontiguousarray(weights.reshape(shape), dtype=np.int32), shape[0]
+
+
 class FrameTrace:
     """Frame traces on the device: rc_trace_create .. rc_trace_destroy (include/recode_hip.h) - per frame of a batch of stored frames the
     number of set pixels, the sum of their values, the sums weighted by row and by column, and the sums under k weight planes the handle
@@ -384,46 +435,7 @@ class FrameTrace:
 
     def _int32_planes(self, weights):
         """(the planes as C-contiguous int32[k, ny, nx] - numpy, or torch on the GPU -, k)"""
-        if weights is None:
-            return None, 0
-        on_gpu = hasattr(weights, "data_ptr") and not isinstance(weights, np.ndarray)
-        if on_gpu and not weights.is_cuda:
-            weights, on_gpu = weights.numpy(), False
-        if not on_gpu and not isinstance(weights, np.ndarray):
-            raise ValueError("FrameTrace: weights must be a numpy array or a torch tensor")
-        shape = tuple(int(v) for v in weights.shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3 or shape[1:] != (self.ny, self.nx) or not 1 <= shape[0] <= self.MAX_PLANES:
-            raise ValueError("FrameTrace: weights of shape %s - (ny, nx) or (k, ny, nx) with ny, nx = %d, %d and 1 <= k <= %d"
-                             % (tuple(weights.shape), self.ny, self.nx, self.MAX_PLANES))
-        lo, hi = -(1 << 31), (1 << 31) - 1
-        if on_gpu:
-            import torch
-            if weights.dtype.is_floating_point or weights.dtype.is_complex or weights.dtype == torch.bool:
-                raise ValueError("FrameTrace: weights of dtype %s (an integer dtype that fits int32)" % weights.dtype)
-            # The library runs on the caller's current device (RC_DEVICE overrides it) and on streams of its own: the tensor must live on that
-            # device, and everything queued on it - the kernels that produced the weights, the int32 copy below - must have finished before
-            # rc_trace_create reads it (the library's streams are not ordered behind torch's).
-            lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
-            if weights.device.index != lib_device:
-                raise ValueError("FrameTrace: weights on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (weights.device, lib_device))
-            if weights.dtype not in (torch.int8, torch.int16, torch.int32, torch.uint8) and weights.numel():
-                # (unsigned 32- and 64-bit values are judged through the signed view of the same width: what does not fit int32 is negative
-                # there, or above 2^31 - 1; torch reduces signed dtypes only)
-                signed = {getattr(torch, "uint16", None): torch.int32, getattr(torch, "uint32", None): torch.int32, getattr(torch, "uint64", None): torch.int64}
-                seen = weights if weights.dtype not in signed else weights.to(torch.int32) if weights.element_size() == 2 else weights.view(signed[weights.dtype])
-                floor = lo if weights.dtype not in signed else 0
-                if not (floor <= int(seen.min()) and int(seen.max()) <= hi):
-                    raise ValueError("FrameTrace: weights do not fit int32")
-            planes = weights.reshape(shape).to(torch.int32).contiguous()
-            torch.cuda.synchronize(weights.device)
-            return planes, shape[0]
-        if weights.dtype.kind not in "iu":
-            raise ValueError("FrameTrace: weights of dtype %s (an integer dtype that fits int32)" % weights.dtype)
-        if weights.size and not (lo <= int(weights.min()) and int(weights.max()) <= hi):
-            raise ValueError("FrameTrace: weights do not fit int32")
-        return np.ascontiguousarray(weights.reshape(shape), dtype=np.int32), shape[0]
+        return int32_planes(weights, self.nx, self.ny, self.MAX_PLANES, "FrameTrace")
 
     @property
     def handle(self):
@@ -462,6 +474,88 @@ class FrameTrace:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
             _lib.rc_trace_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
+class FrameCorrelation:
+    """Correlation surfaces on the device: rc_corr_create .. rc_corr_destroy (include/recode_hip.h) - per frame of a batch of stored frames
+    the overlap of its set pixels with a reference image at every offset of a window, int64[n, S, S] with S = 2 * radius + 1, exact:
+    out[f, dy + R, dx + R] = sum v * reference[row + dy, col + dx] (0 outside the image).  reference: a numpy array / a torch tensor on the
+    GPU of shape (ny, nx) of an integer dtype whose values fit int32 (what FrameTrace takes as one plane, with its rules for a tensor's
+    device), or a FrameSum of that shape, whose cells are fetched on the device - refused (ValueError) when its bound() exceeds 2^31 - 1.
+    radius: 0..16.  The handle keeps its own zero-bordered copy; batches on both slots and several readers may share it.  `geom` as for
+    FrameTrace."""
+
+    MAX_RADIUS = 16
+
+    def __init__(self, nx, ny, reference, radius=8):
+        self.nx, self.ny, self.radius = int(nx), int(ny), int(radius)
+        if not 0 <= self.radius <= self.MAX_RADIUS:
+            raise ValueError("FrameCorrelation: radius %d (0 .. %d)" % (self.radius, self.MAX_RADIUS))
+        self._h = None
+        plane = self._from_sum(reference) if isinstance(reference, FrameSum) else int32_planes(reference, self.nx, self.ny, 1, "FrameCorrelation", "reference")[0]
+        st = C.c_int(0)                                    # (`plane` is kept alive until rc_corr_create has copied it)
+        self._h = lib().rc_corr_create(self.nx, self.ny, self.radius, plane.data_ptr() if hasattr(plane, "data_ptr") else ptr(plane), C.byref(st))
+        if not self._h:
+            check(st.value, "rc_corr_create")
+
+    def _from_sum(self, fs):
+        """a FrameSum's cells as an int32 tensor on its device: rc_sum_fetch with a device destination, no trip over the link.  The cells
+        are uint32; up to 2^31 - 1 they are the same bits as int32, and the handle's bound says whether any can be larger"""
+        if (fs.nx, fs.ny) != (self.nx, self.ny):
+            raise ValueError("FrameCorrelation: a FrameSum of %d x %d as the reference of frames of %d x %d" % (fs.nx, fs.ny, self.nx, self.ny))
+        if fs.bound() > (1 << 31) - 1:
+            raise ValueError("FrameCorrelation: the FrameSum's cells may exceed 2^31 - 1 (bound %d): they do not fit int32" % fs.bound())
+        import torch
+        dev = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
+        cells = torch.empty((self.ny, self.nx), dtype=torch.int32, device="cuda:%d" % dev)
+        check(lib().rc_sum_fetch(fs._h, cells.data_ptr(), 0), "rc_sum_fetch")      # (returns with the copy done)
+        return cells
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def side(self):
+        return 2 * self.radius + 1
+
+    def reference_bound(self):
+        """max |reference| as the handle holds it for the no-wrap rule (INT32_MIN counts as 2^31)"""
+        return int(lib().rc_corr_reference_bound(self._h))
+
+    def _codec(self, geom):
+        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("FrameCorrelation: frames of %d x %d correlated with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
+        return tuple(int(v) for v in geom[2:6])
+
+    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
+        """rc_corr_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
+        return lib().rc_corr_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
+
+    def frames(self, geom, data, sizes, n):
+        """The surfaces of n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them):
+        (int64[n, S, S], the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
+        out, prefix = np.empty((n, self.side, self.side), np.int64), np.zeros(n + 1, np.uint64)
+        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_corr_frames")
+        return out, prefix
+
+    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
+        """rc_corr_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
+        returned, which gives the verdict and the prefix)"""
+        return lib().rc_corr_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.rc_corr_destroy(h)
 
     def __enter__(self):
         return self

@@ -8,6 +8,7 @@
 #include "rc_inflate.h"
 #include "rc_read_plan.h"
 #include "rc_trace.h"
+#include "rc_corr.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
 namespace {
@@ -124,9 +125,10 @@ struct rc_sum {
 struct CountReq { uint32_t method, area_threshold, upsample; };
 struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
 struct TraceReq { const int32_t *weights; uint32_t k; };   // (the handle's interleaved weights and their planes)
+struct CorrReq { const int32_t *padded; uint32_t radius; };   // (the handle's zero-bordered reference and the window's radius)
 // slot, submit: the synchronous forms = (RC_READ_SLOTS - their own resources -, false); the _submit forms = (slot, true): they return once
 // everything is queued.  kind (rc_read_plan.h) says what out / cap are: entries of the kind's size (cap of them; NULL / 0: the prefix alone),
-// the cells of a dense or trace output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
+// the cells of a dense, trace or corr output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
 // stats_cap (RK_L2 alone; otherwise a level-2 file's statistics stream is stepped over): every frame's fields as uint16.  shifts (with sum
 // only): the caller's int32 (dy, dx) per frame, copied into the slot's page-locked head before anything is queued - the caller may reuse its
 // array once the call has returned.  count.upsample: RK_COUNTED_SUM's grid is that many times finer than the frame (nx, ny: the FRAME's).
@@ -138,7 +140,7 @@ struct ReadRequest {
     rc::ReadKind kind = rc::RK_TRIPLETS; void *out = nullptr; uint64_t cap = 0;
     uint16_t *stats = nullptr; uint64_t stats_cap = 0;
     rc_sum *sum = nullptr; const int32_t *shifts = nullptr;
-    CountReq count{}; DenseReq dense{}; TraceReq trace{};
+    CountReq count{}; DenseReq dense{}; TraceReq trace{}; CorrReq corr{};
 };
 
 // `p` must be memory a queued copy can fill: RC_ERR_BAD_ARG with `msg` for anything but page-locked host memory
@@ -538,6 +540,7 @@ int ReadRun::route()
     // finishes the count (k_expand_bases) checks what the host otherwise would (total <= cap, value streams long enough) and the emit
     // kernel writes nothing once any check or decoder has raised *d_err.
     if (q.kind == RK_TRACE) cell_bytes = (uint64_t)n * (TRACE_MOMENTS + q.trace.k) * 8;
+    if (q.kind == RK_CORR) cell_bytes = (uint64_t)n * corr_cells(q.corr.radius) * 8;
     if (q.kind == RK_DENSE) cell_bytes = (uint64_t)n * q.dense.region.w * q.dense.region.h * q.dense.cell_bytes;
     auto place = [&]() -> int {      // where the kernels write: the caller's device memory, or d_triplets for its host memory
         if (!out || is_device_ptr(out)) { target = out; return RC_OK; }
@@ -583,6 +586,11 @@ int ReadRun::route()
         if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, q.trace.k) + 64)) != RC_OK) return r;
         launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.trace.weights, q.trace.k,
                                   u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+    } else if (q.kind == RK_CORR) {
+        // (its per-(frame, chunk) partial rows live there too: corr_workspace_bytes, bounded by the launch's workgroups, not the frame's blocks)
+        if ((r = u.d_count.ensure(U.dmem, corr_workspace_bytes(nb8, n, q.corr.radius, WG) + 64)) != RC_OK) return r;
+        launch_expand_batch_corr(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.corr.padded, q.corr.radius,
+                                 u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
     } else if (q.kind == RK_DENSE)
         launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.dense.region,
                                   q.dense.cell_bytes, target, d_err, s);
@@ -1113,3 +1121,112 @@ RC_EXPORT int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t level, u
 RC_EXPORT int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                      const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
 { return trace_run(t, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_TRACE, .out = out, .cap = out_cells}); }
+
+// ---- correlation surfaces: per frame the overlap of its set pixels with a reference image at every offset of a window (rc_corr.hip) ------
+// The handle owns the reference: a zero-bordered copy, int32[ny + 2 R][nx + 2 R], read-only after create - batches on both slots and the
+// synchronous call may use it at once -, and its maxabs for the no-wrap rule.
+struct rc_corr {
+    int device = -1;
+    uint32_t nx = 0, ny = 0, radius = 0;
+    int32_t *padded = nullptr;
+    uint32_t bound = 0;
+};
+
+RC_EXPORT rc_corr *rc_corr_create(uint32_t nx, uint32_t ny, uint32_t radius, const int32_t *reference, int *status)
+{
+    using namespace rc;
+    auto done = [&](int code) { if (status) *status = code; return (rc_corr *)nullptr; };
+    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: nx, ny in 1..65535"));
+    if (radius > CORR_MAX_RADIUS) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: radius at most 16"));
+    if (!reference) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: reference is NULL"));
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return done(r);
+    rc_corr *c = new (std::nothrow) rc_corr;
+    if (!c) return done(fail(RC_ERR_WORKSPACE, "rc_corr_create: out of host memory"));
+    c->device = g_util.device; c->nx = nx; c->ny = ny; c->radius = radius;
+    const uint64_t N = (uint64_t)nx * ny, bytes = corr_padded_cells(nx, ny, radius) * 4;
+    const uint32_t nxp = corr_padded_nx(nx, radius);
+    const bool on_device = is_device_ptr(reference);
+    hipStream_t s = g_util.stream;
+    uint32_t *d_bound = nullptr;       // maxabs of a device caller's reference
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->padded), bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(c->padded, 0, bytes, s);
+    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_bound), 4);
+    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_bound, 0, 4, s);
+    if (e == hipSuccess && on_device) {
+        launch_trace_maxabs(reference, N, d_bound, s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&c->bound, d_bound, 4, hipMemcpyDeviceToHost, s);
+    } else if (e == hipSuccess)
+        for (uint64_t p = 0; p < N; ++p) c->bound = std::max(c->bound, trace_abs(reference[p]));
+    // the image's rows into the middle of the border (row r of T starts at padded (r + R, R))
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(c->padded + (uint64_t)radius * nxp + radius, (size_t)nxp * 4, reference, (size_t)nx * 4, (size_t)nx * 4, ny,
+                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    // (also after an error: what was queued before it may still read `d_bound` and the caller's reference)
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e_sync;
+    if (d_bound) (void)hipFree(d_bound);
+    if (e != hipSuccess) {
+        r = hip_fail(e, "rc_corr_create");
+        if (c->padded) (void)hipFree(c->padded);
+        delete c;
+        return done(r);
+    }
+    if (status) *status = RC_OK;
+    return c;
+}
+
+RC_EXPORT int rc_corr_destroy(rc_corr *c)
+{
+    if (!c) return RC_OK;
+    RC_ON_DEVICE(c->device);
+    // (a batch still queued on a slot reads the reference: both slots' streams and the synchronous call's are waited for)
+    (void)hipDeviceSynchronize();
+    if (c->padded) (void)hipFree(c->padded);
+    delete c;
+    return RC_OK;
+}
+
+RC_EXPORT uint32_t rc_corr_side(const rc_corr *c) { return c ? rc::corr_side(c->radius) : 0; }
+RC_EXPORT uint32_t rc_corr_reference_bound(const rc_corr *c) { return c ? c->bound : 0; }
+
+// what both forms check before the device is asked for: from the arguments alone
+static int corr_admit(const rc_corr *c, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
+                      const int64_t *out, uint64_t out_cells)
+{
+    using namespace rc;
+    if (!c || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: NULL / zero argument");
+    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
+    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_corr_frames: bit_depth above 16 (as for the summed views)");
+    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: out must be aligned to its int64 cells");
+    if (out_cells < (uint64_t)n * corr_cells(c->radius)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_corr_frames: out holds fewer than n * (2 R + 1)^2 cells");
+    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
+    const uint64_t nb = ((uint64_t)c->nx * c->ny + 7) / 8;
+    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
+        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: the frames' geometry differs from the handle's");
+    if (!corr_batch_fits(c->nx, c->ny, level, bit_depth, c->bound, sizes, n))
+        return fail(RC_ERR_OUT_TOO_SMALL, "rc_corr_frames: a cell could pass 2^63 - 1 (largest |reference| * largest value * set pixels a frame can hold)");
+    return RC_OK;
+}
+static int corr_run(rc_corr *c, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.corr: the handle's, filled in here)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_corr_frames_submit: slot 0 or 1");
+    int r = corr_admit(c, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
+    if (r != RC_OK) return r;
+    {
+        UtilScope util_scope;
+        if ((r = util_scope.enter()) != RC_OK) return r;
+        if (g_util.device != c->device) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: the handle belongs to another device");
+    }
+    q.in.nx = c->nx; q.in.ny = c->ny; q.corr = {c->padded, c->radius};
+    return expand_run(q, slot);
+}
+RC_EXPORT int rc_corr_frames(rc_corr *c, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
+                             uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
+{ return corr_run(c, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_CORR, .out = out, .cap = out_cells}); }
+RC_EXPORT int rc_corr_frames_submit(rc_corr *c, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                    const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
+{ return corr_run(c, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_CORR, .out = out, .cap = out_cells}); }

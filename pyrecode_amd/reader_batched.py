@@ -116,6 +116,56 @@ def centre_of_mass(traces):
     return row, col
 
 
+def estimate_shifts(corr, group=1):
+    """Per-frame shifts from the surfaces of get_frame_correlations / iter_frame_correlations: corr is int64[n, S, S] (or the dict that holds
+    it as 'corr'), S = 2 R + 1.  The surfaces of each run of `group` consecutive frames are summed first (correlation is linear: a fraction's
+    surface is the sum of its frames'; the last group may be shorter) - ValueError when group * max|corr| could pass 2^63 - 1.  Per group
+    the peak is the largest cell, ties broken by the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx - an all-zero surface
+    gives (0, 0).  Returns a dict of arrays with one entry per FRAME, every frame of a group carrying its group's: 'shifts' int32[n, 2] -
+    (dy, dx), as sum_frames(shifts=...) takes them -, 'peak' int64[n], 'on_border' bool[n] - |dy| == R or |dx| == R: the drift may exceed
+    the window -, 'valid' bool[n] - peak > 0 -, and 'refined' float64[n, 2]: the shift plus, per axis, the vertex of the parabola through
+    the peak and its two neighbours, computed as a Fraction of Python integers and converted once (offset 0 on the border or where the
+    denominator is 0).  For counted views multiply `refined` by upsample and round."""
+    from fractions import Fraction
+    c = np.asarray(corr['corr'] if isinstance(corr, dict) else corr)
+    if c.ndim != 3 or c.shape[1] != c.shape[2] or c.shape[1] % 2 != 1 or c.dtype.kind not in 'iu':
+        raise ValueError('estimate_shifts: corr of shape %s, dtype %s - wanted integer [n, S, S] with S odd' % (c.shape, c.dtype))
+    group = int(group)
+    if group < 1:
+        raise ValueError('estimate_shifts: group must be at least 1')
+    n, S = c.shape[0], c.shape[1]
+    R = S // 2
+    c = c.astype(np.int64, copy=False)
+    if n and group * max(abs(int(c.min())), abs(int(c.max()))) > (1 << 63) - 1:
+        raise ValueError('estimate_shifts: the sum of %d surfaces could pass 2^63 - 1' % group)
+    out = {'shifts': np.zeros((n, 2), np.int32), 'peak': np.zeros(n, np.int64), 'on_border': np.zeros(n, bool), 'valid': np.zeros(n, bool),
+           'refined': np.zeros((n, 2), np.float64)}
+    d = np.arange(-R, R + 1)
+    # the tie-break as one key per cell, smallest first: dy^2 + dx^2, then dy, then dx
+    key = ((d[:, None] ** 2 + d[None, :] ** 2) * S + (d[:, None] + R)) * S + (d[None, :] + R)
+    for a in range(0, n, group):
+        g = c[a:a + group].sum(axis=0, dtype=np.int64)
+        peak = int(g.max())
+        at = int(np.argmin(np.where(g == peak, key, key.max() + 1)))
+        iy, ix = divmod(at, S)
+        dy, dx = iy - R, ix - R
+        border = abs(dy) == R or abs(dx) == R
+        fine = [Fraction(dy), Fraction(dx)]
+        if not border:
+            for axis, (lo, hi) in enumerate(((g[iy - 1, ix], g[iy + 1, ix]), (g[iy, ix - 1], g[iy, ix + 1]))):
+                lo, hi = int(lo), int(hi)
+                den = 2 * (lo - 2 * peak + hi)
+                if den != 0:
+                    fine[axis] += Fraction(lo - hi, den)
+        rows = slice(a, a + group)
+        out['shifts'][rows] = (dy, dx)
+        out['peak'][rows] = peak
+        out['on_border'][rows] = border
+        out['valid'][rows] = peak > 0
+        out['refined'][rows] = (float(fine[0]), float(fine[1]))
+    return out
+
+
 def _event_views(buf, cap, total):
     """(rows int32, cols int32, area uint32, weight uint64): the first `total` events of rc_count_frames' output of capacity `cap`"""
     return (buf[8 * cap:12 * cap].view(np.int32)[:total], buf[12 * cap:16 * cap].view(np.int32)[:total],
@@ -330,6 +380,34 @@ class _Traces(_Kind):
     def item(self, job):
         k, cols = job.count, self.ft.columns
         return job.first, self.as_dict(job.first, k, self.outs[2 + job.slot].array[:8 * k * cols].view(np.int64).reshape(k, cols))
+
+
+class _Correlations(_Kind):
+    """A batch's correlation surfaces (rc_corr_frames / _submit on the _lib.FrameCorrelation fc): int64[k, S, S] in the slot's page-locked
+    output, handed out as as_dict(first, k, cells, prefix) makes them.  The synchronous call's set-pixel prefix is kept where a waited-for
+    verdict's is (job.payload.prefix): whichever call answered last says how many pixels the frames have."""
+    what = 'rc_corr_frames'
+
+    def __init__(self, fc, outs, as_dict):
+        self.fc, self.outs, self.as_dict = fc, outs, as_dict
+
+    def _cells(self, k):
+        return k * self.fc.side * self.fc.side
+
+    def room(self, job, geom, sizes, k):
+        self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * self._cells(k))
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        out = (self.outs[2 + job.slot]._p, self._cells(k))
+        if slot is not None:
+            return self.fc.submit_status(slot, geom, data, sizes, k, *out)
+        job.payload.prefix = np.zeros(k + 1, np.uint64)
+        return self.fc.frames_status(geom, data, sizes, k, *out, job.payload.prefix)
+
+    def item(self, job):
+        k, S = job.count, self.fc.side
+        cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(k, S, S)
+        return job.first, self.as_dict(job.first, k, cells, job.payload.prefix)
 
 
 def _device_path(dev):
@@ -1254,6 +1332,7 @@ class BatchedAccess:
     _SUMS = ('sum_frames', 'the cells of a summed view are uint32')
     _COUNTS = ('counting', 'the sums are exact in 64 bits for 16-bit values')
     _TRACES = ('frame traces', 'the sums are exact in 64 bits for 16-bit values')
+    _CORR = ('correlation surfaces', 'the sums are exact in 64 bits for 16-bit values')
 
     def _check_levels_and_bits(self, who, why):
         """levels 1 to 3, and at level 1 fields of 16 bits at most: NotImplementedError otherwise"""
@@ -1530,6 +1609,64 @@ class BatchedAccess:
             stream.close()
             if own:
                 ft.close()
+
+    # ---- correlation surfaces (rc_corr_frames): what drift estimation needs of every frame, summed on the device -------------------------
+    def _corr_handle(self, reference, radius):
+        """(the _lib.FrameCorrelation to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
+        nx, ny = int(self._header['nx']), int(self._header['ny'])
+        if isinstance(reference, _lib.FrameCorrelation):
+            if (reference.nx, reference.ny) != (nx, ny):
+                raise ValueError('correlation surfaces: a FrameCorrelation of %d x %d for frames of %d x %d' % (reference.nx, reference.ny, nx, ny))
+            return reference, False
+        if reference is None:
+            raise ValueError('correlation surfaces: a reference is needed - an integer (ny, nx) array or GPU tensor, a FrameSum, or a FrameCorrelation')
+        return _lib.FrameCorrelation(nx, ny, reference, radius), True
+
+    def _corr_dict(self, first, k, cells, prefix):
+        """a batch's int64[k, S, S] and set-pixel prefix as the dict get_frame_correlations returns (copies of their own)"""
+        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
+        return {'corr': cells.copy(), 'count': np.diff(np.asarray(prefix[:k + 1]).astype(np.int64)), 'frame_ids': ids}
+
+    def _corr_stream(self, z0, n, batch, fc):
+        """The engine of get_frame_correlations and iter_frame_correlations: the batches go down the ladder as _Correlations
+        (rc_corr_frames_submit / rc_expand_frames_wait on the two slots); 8 * S^2 bytes per frame cross the link.  Yields (first frame,
+        dict).  Routes and fall-backs are the summed views' (sum_frames)."""
+        return self._ladder(_Correlations(fc, self._bufs.stream, self._corr_dict), _jobs(z0, n, batch))
+
+    def get_frame_correlations(self, z0, n, reference=None, radius=8):
+        """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) its correlation surface with `reference`, summed ON THE
+        DEVICE in one call (rc_corr_frames): 'corr' int64[n, S, S], S = 2 * radius + 1, corr[f, dy + R, dx + R] = the sum over the frame's set
+        pixels (row, col) of value * reference[row + dy, col + dx] (0 outside the image; levels 2 and 3: every value is 1) - the overlap
+        with the reference of the frame translated by (dy, dx), so estimate_shifts' argmax is what sum_frames(shifts=...) takes.  Also
+        'count' int64[n] - the frames' set pixels - and 'frame_ids' int64[n].
+        reference: an integer array or GPU tensor of shape (ny, nx) whose values fit int32, a _lib.FrameSum of that shape (a summed view:
+        its cells stay on the device), or a _lib.FrameCorrelation the caller made - `radius` (0..16) is then the handle's -, so that
+        the part files of a run share one copy.  A batch in which a cell could pass 2^63 - 1 raises ValueError.  Routes
+        (last_batch_path) and fall-backs as for sum_frames; files of more than 16 bits are not taken (NotImplementedError)."""
+        n = self._frame_range(z0, n)
+        self._check_levels_and_bits(*self._CORR)
+        fc, own = self._corr_handle(reference, radius)
+        stream = self._corr_stream(z0, n, n, fc)      # (one batch of n frames)
+        try:
+            return next(stream)[1]
+        finally:
+            stream.close()
+            if own:
+                fc.close()
+
+    def iter_frame_correlations(self, z0=0, n=None, batch=64, reference=None, radius=8):
+        """get_frame_correlations for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two
+        batches in flight (rc_corr_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
+        n = self._frame_range(z0, n, batch)
+        self._check_levels_and_bits(*self._CORR)
+        fc, own = self._corr_handle(reference, radius)
+        stream = self._corr_stream(z0, n, batch, fc)
+        try:
+            yield from stream
+        finally:
+            stream.close()
+            if own:
+                fc.close()
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
