@@ -570,6 +570,36 @@ int rc_corr_frames(rc_corr *c, uint32_t bit_depth, uint32_t reduction_level, uin
                    const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix);
 int rc_corr_frames_submit(rc_corr *c, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
                           const uint8_t *data, const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells);
+/* ---- binned frame traces: per frame and bin of a label map the set pixels and the sum of their values ---------------------------
+ * The per-frame reduction of diffraction and 4D-STEM data that is a PARTITION - radial profiles, annular and segmented detectors, ROI
+ * grids -, which a caller otherwise computes with np.bincount over labels[rows, cols] around ReCoDeReader.get_frame
+ * (pyrecode/recode_reader.py:379-471).  A batch is decoded and counted exactly as by rc_expand_frames, and in place of the emit kernel the
+ * kernels of rc_bins.hip write, for frame f and its set pixels (row, col) of stored value v (level 1: the bit_depth-bit field; levels 2
+ * and 3: 1; a level-2 file's statistics stream is stepped over),
+ *   out[f][0][b] = the number of set pixels with labels[row][col] == b,   out[f][1][b] = the sum of their v,   0 <= b < n_bins
+ * int64[n][2][n_bins], row-major, exact.  Summed over b, plane 0 plus the ignored pixels is rc_trace_frames' count and plane 1 its sum;
+ * for n_bins <= 16 plane 1 is its weighted columns under the one-hot planes labels == b.  A frame without a set pixel gives zeros; EVERY
+ * cell is written exactly once: out needs no memset.
+ *   rc_bins_create  nx, ny: the frames' shape, 1..65535; n_bins 1..4096; labels: uint16[ny][nx] in C order, host or device memory, each
+ *                   cell a bin 0 .. n_bins - 1 or 0xFFFF ("in no bin"), copied into the handle - the caller's may go away.  Device
+ *                   labels are read on the library's own stream: the ordering rule of rc_trace_create's planes.  NULL with *status set
+ *                   on failure: RC_ERR_BAD_ARG (a shape of 0 or above 65535, n_bins 0 or above 4096, labels NULL, a label >= n_bins
+ *                   that is not 0xFFFF - host labels are scanned on the host, all of this before the device is asked for; device labels
+ *                   by a small kernel), RC_ERR_DEVICE without a GPU.  The handle lives on the caller's current GPU (RC_DEVICE) and is
+ *                   read-only after create, so batches on both slots may use one handle.  One thread uses a handle at a time.
+ *   rc_bins_count   n_bins
+ * No batch is refused for wrap: a cell is at most 65535 * nx * ny < 2^48.  out, nnz_prefix, the refusals (out_cells < n * 2 * n_bins is
+ * RC_ERR_OUT_TOO_SMALL; level 1 above 16 bits RC_ERR_UNSUPPORTED; a stored frame of another geometry or a handle of another device
+ * RC_ERR_BAD_ARG), their order before any device work, and "a refused batch writes NOTHING to out" are rc_trace_frames';
+ * rc_bins_frames_submit queues the batch on slot 0 or 1 as rc_trace_frames_submit does, rc_expand_frames_wait gives the verdict. */
+typedef struct rc_bins rc_bins;
+rc_bins *rc_bins_create(uint32_t nx, uint32_t ny, uint32_t n_bins, const uint16_t *labels, int *status);
+int rc_bins_destroy(rc_bins *b);
+uint32_t rc_bins_count(const rc_bins *b);
+int rc_bins_frames(rc_bins *b, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                   const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix);
+int rc_bins_frames_submit(rc_bins *b, uint32_t slot, uint32_t bit_depth, uint32_t reduction_level, uint32_t op_mode, uint32_t scheme,
+                          const uint8_t *data, const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells);
 /* The host half of a batch whose streams only a STOCK decoder takes - files the reference's writer produced with zstandard /
  * lz4.frame / zlib (recode_compressors.py:82-120): linked 64 KiB LZ4 blocks, 4-stream Huffman literals and real offsets in zstd,
  * deflate.  Each is one serial chain, which the reference walks with one library call per stream (recode_compressors.py:40-79:

@@ -104,6 +104,11 @@ SIGNATURES = {
     "rc_corr_reference_bound": (C.c_uint32, [C.c_void_p]),
     "rc_corr_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
     "rc_corr_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "rc_bins_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
+    "rc_bins_destroy": (C.c_int, [C.c_void_p]),
+    "rc_bins_count": (C.c_uint32, [C.c_void_p]),
+    "rc_bins_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
+    "rc_bins_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
     "rc_host_decode_streams": (C.c_int, [C.c_uint32, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32]),
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -556,6 +561,104 @@ class FrameCorrelation:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
             _lib.rc_corr_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
+class FrameBins:
+    """Binned frame traces on the device: rc_bins_create .. rc_bins_destroy (include/recode_hip.h) - per frame of a batch of stored frames
+    and per bin of a label map the number of set pixels and the sum of their values, int64[n, 2, B], exact.  labels: a numpy array / a torch
+    tensor on the GPU of shape (ny, nx) of any integer dtype whose values fit uint16 (a tensor by FrameTrace's rules for its device), each
+    cell a bin 0 .. B - 1 or 0xFFFF ("in no bin").  n_bins: B, 1 .. 4096; None: max(label != 0xFFFF) + 1 (1 when every pixel is ignored).
+    The handle keeps its own copy; batches on both slots and several readers may share it.  `geom` as for FrameTrace."""
+
+    MAX_BINS = 4096
+    IGNORE = 0xFFFF
+
+    def __init__(self, nx, ny, labels, n_bins=None):
+        self.nx, self.ny = int(nx), int(ny)
+        self._h = None
+        plane, top = self._uint16_labels(labels)
+        self.n_bins = top + 1 if n_bins is None else int(n_bins)
+        if not 1 <= self.n_bins <= self.MAX_BINS:
+            raise ValueError("FrameBins: n_bins %d (1 .. %d)" % (self.n_bins, self.MAX_BINS))
+        if top >= self.n_bins:
+            raise ValueError("FrameBins: a label of %d with n_bins %d (bins are 0 .. n_bins - 1, 0xFFFF is 'in no bin')" % (top, self.n_bins))
+        st = C.c_int(0)                                    # (`plane` is kept alive until rc_bins_create has copied it)
+        self._h = lib().rc_bins_create(self.nx, self.ny, self.n_bins, plane.data_ptr() if hasattr(plane, "data_ptr") else ptr(plane), C.byref(st))
+        if not self._h:
+            check(st.value, "rc_bins_create")
+
+    def _uint16_labels(self, labels):
+        """(the labels as C-contiguous uint16[ny, nx] - numpy, or torch on the GPU as int16 of the same bits -, the largest label that is
+        not 0xFFFF - 0 when there is none)"""
+        on_gpu = hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray)
+        if on_gpu and not labels.is_cuda:
+            labels, on_gpu = labels.numpy(), False
+        if not on_gpu and not isinstance(labels, np.ndarray):
+            raise ValueError("FrameBins: labels must be a numpy array or a torch tensor")
+        if tuple(int(v) for v in labels.shape) != (self.ny, self.nx):
+            raise ValueError("FrameBins: labels of shape %s - (ny, nx) = (%d, %d)" % (tuple(labels.shape), self.ny, self.nx))
+        if on_gpu:
+            import torch
+            if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+                raise ValueError("FrameBins: labels of dtype %s (an integer dtype whose values fit uint16)" % labels.dtype)
+            # (the tensor's device and the ordering before rc_bins_create reads it: as for FrameTrace's weights)
+            lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
+            if labels.device.index != lib_device:
+                raise ValueError("FrameBins: labels on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (labels.device, lib_device))
+            unsigned = {getattr(torch, "uint16", None): torch.int32, getattr(torch, "uint32", None): torch.int64, getattr(torch, "uint64", None): torch.int64}
+            # (torch reduces signed dtypes: uint16 and uint32 widen, uint64 is judged through its signed view - too large is negative there)
+            wide = labels.view(torch.int64) if labels.dtype == getattr(torch, "uint64", None) else labels.to(unsigned.get(labels.dtype, labels.dtype))
+            if wide.numel() and not (0 <= int(wide.min()) and int(wide.max()) <= 0xFFFF):
+                raise ValueError("FrameBins: labels do not fit uint16")
+            kept = wide[wide != self.IGNORE]
+            top = int(kept.max()) if kept.numel() else 0
+            plane = wide.to(torch.int32).to(torch.int16).contiguous() if wide.dtype != torch.int16 else wide.contiguous()   # (the low 16 bits)
+            torch.cuda.synchronize(labels.device)
+            return plane, top
+        if labels.dtype.kind not in "iu":
+            raise ValueError("FrameBins: labels of dtype %s (an integer dtype whose values fit uint16)" % labels.dtype)
+        if labels.size and not (0 <= int(labels.min()) and int(labels.max()) <= 0xFFFF):
+            raise ValueError("FrameBins: labels do not fit uint16")
+        kept = labels[labels != self.IGNORE]
+        return np.ascontiguousarray(labels, dtype=np.uint16), (int(kept.max()) if kept.size else 0)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _codec(self, geom):
+        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("FrameBins: frames of %d x %d binned with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
+        return tuple(int(v) for v in geom[2:6])
+
+    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
+        """rc_bins_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
+        return lib().rc_bins_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
+
+    def frames(self, geom, data, sizes, n):
+        """The bins of n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them):
+        (int64[n, 2, B] - [:, 0] the counts, [:, 1] the sums -, the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
+        out, prefix = np.empty((n, 2, self.n_bins), np.int64), np.zeros(n + 1, np.uint64)
+        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_bins_frames")
+        return out, prefix
+
+    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
+        """rc_bins_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
+        returned, which gives the verdict and the prefix)"""
+        return lib().rc_bins_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.rc_bins_destroy(h)
 
     def __enter__(self):
         return self

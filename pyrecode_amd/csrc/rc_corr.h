@@ -79,5 +79,8 @@ namespace rc {
 void launch_expand_batch_corr(const uint8_t *bm, uint64_t bm_stride, uint64_t nb8, uint64_t N, uint32_t nx, uint32_t n, const uint32_t *blk_off,
                               const uint8_t *pv, uint64_t pv_stride, const uint32_t *pv_bytes, uint32_t d, uint32_t level, const int32_t *padded,
                               uint32_t radius, int64_t *partials, int64_t *out, const int *err, hipStream_t s);
+// k_corr_reduce on its own: out[f][c] = sum over the chunks of partials[f][chunk][c] for n frames of rows of `ncells` cells, nothing once
+// *err is set (rc_bins.hip's rows are added by it too)
+void launch_rows_reduce(const int64_t *partials, uint32_t nchunk, uint32_t ncells, uint32_t n, int64_t *out, const int *err, hipStream_t s);
 }  // namespace rc
 #endif

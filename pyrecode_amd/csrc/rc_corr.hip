@@ -143,7 +143,7 @@ __global__ __launch_bounds__(WG) void k_expand_corr_b(const uint8_t *__restrict_
 
 // out[f][c] = sum over the chunks of partials[f][chunk][c]: a thread per cell, consecutive threads on consecutive words of every row.
 // (k_trace_reduce's job for rows wider than a workgroup; that kernel and its callers are as they were.)  The only writer of `out`, every
-// cell once; nothing once *err is set.
+// cell once; nothing once *err is set.  launch_rows_reduce is its launch on its own: rc_bins.hip's rows of 2 B cells are added by it too.
 __global__ __launch_bounds__(WG) void k_corr_reduce(const uint64_t *__restrict__ partials, uint32_t nchunk, uint32_t ncells, int64_t *__restrict__ out,
                                                       const int *__restrict__ err)
 {
@@ -173,7 +173,12 @@ void launch_expand_batch_corr(const uint8_t *bm, uint64_t bm_stride, uint64_t nb
     else if (nacc <= 5) go(int_c<5>{});       // R = 6 .. 8
     else if (nacc <= 9) go(int_c<9>{});       // R = 9 .. 11
     else go(int_c<18>{});                     // R = 12 .. 16
-    hipLaunchKernelGGL(k_corr_reduce, dim3(n, (S2 + WG - 1) / WG), dim3(WG), 0, s, part, nchunk, S2, out, err);
+    launch_rows_reduce(partials, nchunk, S2, n, out, err, s);
+}
+
+void launch_rows_reduce(const int64_t *partials, uint32_t nchunk, uint32_t ncells, uint32_t n, int64_t *out, const int *err, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_corr_reduce, dim3(n, (ncells + WG - 1) / WG), dim3(WG), 0, s, reinterpret_cast<const uint64_t *>(partials), nchunk, ncells, out, err);
 }
 
 }  // namespace rc

@@ -300,7 +300,7 @@ struct ReadRes {
     bool pending = false;
     uint32_t n = 0;
     rc::ReadKind kind = rc::RK_TRIPLETS;                   // what the batch leaves behind: the verdict's capacity rule and the copy-back plan follow from it
-    uint64_t cap = 0, cell_bytes = 0;                      // (rc_read_plan.h; cell_bytes: a dense, trace or corr output's size)
+    uint64_t cap = 0, cell_bytes = 0;                      // (rc_read_plan.h; cell_bytes: a dense, trace, corr or bins output's size)
     uint8_t *late_dst = nullptr;                           // page-locked output rc_expand_frames_wait fills from d_triplets once the batch is known to be good
 };
 

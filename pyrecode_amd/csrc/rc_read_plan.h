@@ -8,17 +8,18 @@
 
 namespace rc {
 // triplets, COO with uint16 / uint32 values, level-2 rows / columns + statistics, events (rc_count_frames), the adds into an rc_sum handle
-// (frames' values; one count per event), cells of a region (dense), 4 + k sums per frame (trace), a correlation surface per frame (corr).
-// RK_KINDS counts the kinds up to the traces - the rows read_plan_check.cpp's hand-written tables have; RK_CORR sits behind them (its row is
-// walked by tests/native/corr_index_check.cpp), RK_ALL counts every kind.
-enum ReadKind : uint32_t { RK_TRIPLETS, RK_COO16, RK_COO32, RK_L2, RK_EVENTS, RK_SUM, RK_COUNTED_SUM, RK_DENSE, RK_TRACE, RK_KINDS, RK_CORR = RK_KINDS, RK_ALL };
+// (frames' values; one count per event), cells of a region (dense), 4 + k sums per frame (trace), a correlation surface per frame (corr), counts and sums per frame and
+// bin of a label map (bins).
+// RK_KINDS counts the kinds up to the traces - the rows read_plan_check.cpp's hand-written tables have; RK_CORR and RK_BINS sit behind them
+// (their rows are walked by tests/native/corr_index_check.cpp and bins_index_check.cpp), RK_ALL counts every kind.
+enum ReadKind : uint32_t { RK_TRIPLETS, RK_COO16, RK_COO32, RK_L2, RK_EVENTS, RK_SUM, RK_COUNTED_SUM, RK_DENSE, RK_TRACE, RK_KINDS, RK_CORR = RK_KINDS, RK_BINS, RK_ALL };
 struct ReadKindInfo {
     uint32_t esz;         // bytes per entry of the output, counted against the caller's capacity (0: the kind has no entries)
     uint32_t coo;         // what the emit kernel is told: 0 = triplets, else COO with values of that many bytes (RK_L2: 2, and no value array)
     bool stats;           // level-2 statistics are decoded as values (klevel 2)
     bool counts;          // the kernels of rc_count.hip run behind the count
     bool sums;            // adds into an rc_sum handle
-    bool cells;           // writes cells of a size the arguments give (dense, trace, corr), not entries
+    bool cells;           // writes cells of a size the arguments give (dense, trace, corr, bins), not entries
     bool held;            // host memory is staged in BOTH forms and filled only behind the verdict: a refused batch writes nothing
     const char *pageable; // what a submit says to an output in pageable host memory
 };
@@ -36,6 +37,7 @@ inline ReadKindInfo read_kind_info(ReadKind k)
         /* RK_DENSE       */ {0, 0, false, false, false, true, true, "rc_expand_frames_dense_submit: out must be device or page-locked host memory"},
         /* RK_TRACE       */ {0, 0, false, false, false, true, true, "rc_trace_frames_submit: out must be device or page-locked host memory"},
         /* RK_CORR        */ {0, 0, false, false, false, true, true, "rc_corr_frames_submit: out must be device or page-locked host memory"},
+        /* RK_BINS        */ {0, 0, false, false, false, true, true, "rc_bins_frames_submit: out must be device or page-locked host memory"},
     };
     return table[k];
 }
@@ -58,7 +60,7 @@ enum VerdictStep : uint8_t {
     VS_CAPACITY,          // total > capacity, or bit 2
 };
 // rc_expand_frames_wait (every kind) | synchronous triplets / COO / level-2 | synchronous rc_count_frames and rc_sum_add_counted (no output
-// array: it ends at VS_NO_OUTPUT) | synchronous sum, dense, trace, corr: never RC_ERR_OUT_TOO_SMALL
+// array: it ends at VS_NO_OUTPUT) | synchronous sum, dense, trace, corr, bins: never RC_ERR_OUT_TOO_SMALL
 enum VerdictRoute : uint32_t { VR_WAIT, VR_SYNC_ENTRIES, VR_SYNC_EVENTS, VR_SYNC_QUIET, VR_ROUTES };
 inline VerdictRoute verdict_route_sync(ReadKindInfo i) { return i.counts ? VR_SYNC_EVENTS : i.sums || i.cells ? VR_SYNC_QUIET : VR_SYNC_ENTRIES; }
 struct VerdictFacts {
@@ -102,7 +104,7 @@ inline Verdict read_verdict(VerdictRoute route, ReadKind kind, const VerdictFact
 // ---- the copy-back: an output staged in device memory keeps the caller's layout (the arrays of a COO or event output `cap` entries apart),
 // so it goes back as up to four (offset, bytes) segments, the same offsets on both sides
 struct CopyPlan { uint32_t nseg; struct { uint64_t off, bytes; } seg[4]; };
-// behind the verdict: the `total` entries the batch has (none: nothing to copy), or all `cell_bytes` of a dense / trace / corr output
+// behind the verdict: the `total` entries the batch has (none: nothing to copy), or all `cell_bytes` of a dense / trace / corr / bins output
 inline CopyPlan read_copy_plan(ReadKind k, uint64_t cap, uint64_t total, uint64_t cell_bytes)
 {
     const ReadKindInfo i = read_kind_info(k);

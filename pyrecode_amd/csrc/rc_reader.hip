@@ -9,6 +9,7 @@
 #include "rc_read_plan.h"
 #include "rc_trace.h"
 #include "rc_corr.h"
+#include "rc_bins.h"
 
 // ---- seam 3, batched: decode + expand n stored frames ---------------------------------------------------------------------
 namespace {
@@ -126,9 +127,10 @@ struct CountReq { uint32_t method, area_threshold, upsample; };
 struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
 struct TraceReq { const int32_t *weights; uint32_t k; };   // (the handle's interleaved weights and their planes)
 struct CorrReq { const int32_t *padded; uint32_t radius; };   // (the handle's zero-bordered reference and the window's radius)
+struct BinsReq { const uint16_t *labels; uint32_t bins; };    // (the handle's label map and its number of bins)
 // slot, submit: the synchronous forms = (RC_READ_SLOTS - their own resources -, false); the _submit forms = (slot, true): they return once
 // everything is queued.  kind (rc_read_plan.h) says what out / cap are: entries of the kind's size (cap of them; NULL / 0: the prefix alone),
-// the cells of a dense, trace or corr output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
+// the cells of a dense, trace, corr or bins output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
 // stats_cap (RK_L2 alone; otherwise a level-2 file's statistics stream is stepped over): every frame's fields as uint16.  shifts (with sum
 // only): the caller's int32 (dy, dx) per frame, copied into the slot's page-locked head before anything is queued - the caller may reuse its
 // array once the call has returned.  count.upsample: RK_COUNTED_SUM's grid is that many times finer than the frame (nx, ny: the FRAME's).
@@ -140,7 +142,7 @@ struct ReadRequest {
     rc::ReadKind kind = rc::RK_TRIPLETS; void *out = nullptr; uint64_t cap = 0;
     uint16_t *stats = nullptr; uint64_t stats_cap = 0;
     rc_sum *sum = nullptr; const int32_t *shifts = nullptr;
-    CountReq count{}; DenseReq dense{}; TraceReq trace{}; CorrReq corr{};
+    CountReq count{}; DenseReq dense{}; TraceReq trace{}; CorrReq corr{}; BinsReq bins{};
 };
 
 // `p` must be memory a queued copy can fill: RC_ERR_BAD_ARG with `msg` for anything but page-locked host memory
@@ -541,6 +543,7 @@ int ReadRun::route()
     // kernel writes nothing once any check or decoder has raised *d_err.
     if (q.kind == RK_TRACE) cell_bytes = (uint64_t)n * (TRACE_MOMENTS + q.trace.k) * 8;
     if (q.kind == RK_CORR) cell_bytes = (uint64_t)n * corr_cells(q.corr.radius) * 8;
+    if (q.kind == RK_BINS) cell_bytes = (uint64_t)n * BINS_PLANES * q.bins.bins * 8;
     if (q.kind == RK_DENSE) cell_bytes = (uint64_t)n * q.dense.region.w * q.dense.region.h * q.dense.cell_bytes;
     auto place = [&]() -> int {      // where the kernels write: the caller's device memory, or d_triplets for its host memory
         if (!out || is_device_ptr(out)) { target = out; return RC_OK; }
@@ -590,6 +593,11 @@ int ReadRun::route()
         // (its per-(frame, chunk) partial rows live there too: corr_workspace_bytes, bounded by the launch's workgroups, not the frame's blocks)
         if ((r = u.d_count.ensure(U.dmem, corr_workspace_bytes(nb8, n, q.corr.radius, WG) + 64)) != RC_OK) return r;
         launch_expand_batch_corr(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.corr.padded, q.corr.radius,
+                                 u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+    } else if (q.kind == RK_BINS) {
+        // (and the per-(frame, chunk) rows of 2 B partials: bins_workspace_bytes, the output's size plus BINS_PARTIAL_BUDGET at most)
+        if ((r = u.d_count.ensure(U.dmem, bins_workspace_bytes(nb8, n, q.bins.bins, WG) + 64)) != RC_OK) return r;
+        launch_expand_batch_bins(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.bins.labels, q.bins.bins,
                                  u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
     } else if (q.kind == RK_DENSE)
         launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.dense.region,
@@ -1230,3 +1238,107 @@ RC_EXPORT int rc_corr_frames(rc_corr *c, uint32_t bit_depth, uint32_t level, uin
 RC_EXPORT int rc_corr_frames_submit(rc_corr *c, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                     const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
 { return corr_run(c, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_CORR, .out = out, .cap = out_cells}); }
+
+// ---- binned frame traces: per frame and bin of a label map the set pixels and the sum of their values (rc_bins.hip) -----------------------
+// The handle owns the label map, uint16[ny][nx], read-only after create - batches on both slots and the synchronous call may use it at
+// once.  Every label is below n_bins or BINS_IGNORE: create has checked it, the kernel relies on it for nothing but the result.
+struct rc_bins {
+    int device = -1;
+    uint32_t nx = 0, ny = 0, bins = 0;
+    uint16_t *labels = nullptr;
+};
+
+RC_EXPORT rc_bins *rc_bins_create(uint32_t nx, uint32_t ny, uint32_t n_bins, const uint16_t *labels, int *status)
+{
+    using namespace rc;
+    auto done = [&](int code) { if (status) *status = code; return (rc_bins *)nullptr; };
+    static const char *const range = "rc_bins_create: a label at or above n_bins that is not 0xFFFF";
+    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: nx, ny in 1..65535"));
+    if (n_bins == 0 || n_bins > BINS_MAX) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: n_bins in 1..4096"));
+    if (!labels) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: labels is NULL"));
+    const uint64_t N = (uint64_t)nx * ny;
+    // (without a GPU no pointer is a device pointer: host labels are judged before the device is asked for)
+    const bool on_device = is_device_ptr(labels);
+    if (!on_device)
+        for (uint64_t p = 0; p < N; ++p)
+            if (labels[p] >= n_bins && labels[p] != BINS_IGNORE) return done(fail(RC_ERR_BAD_ARG, range));
+    UtilScope util_scope;
+    int r = util_scope.enter();
+    if (r != RC_OK) return done(r);
+    rc_bins *b = new (std::nothrow) rc_bins;
+    if (!b) return done(fail(RC_ERR_WORKSPACE, "rc_bins_create: out of host memory"));
+    b->device = g_util.device; b->nx = nx; b->ny = ny; b->bins = n_bins;
+    hipStream_t s = g_util.stream;
+    uint32_t *d_top = nullptr, top = 0;      // the largest label of a device caller's map
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->labels), N * 2);
+    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_top), 4);
+    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_top, 0, 4, s);
+    if (e == hipSuccess && on_device) {
+        launch_bins_label_max(labels, N, d_top, s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&top, d_top, 4, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(b->labels, labels, N * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    // (also after an error: what was queued before it may still read `d_top` and the caller's labels)
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e_sync;
+    if (d_top) (void)hipFree(d_top);
+    if (e == hipSuccess && top < n_bins) {
+        if (status) *status = RC_OK;
+        return b;
+    }
+    r = e != hipSuccess ? hip_fail(e, "rc_bins_create") : fail(RC_ERR_BAD_ARG, range);
+    if (b->labels) (void)hipFree(b->labels);
+    delete b;
+    return done(r);
+}
+
+RC_EXPORT int rc_bins_destroy(rc_bins *b)
+{
+    if (!b) return RC_OK;
+    RC_ON_DEVICE(b->device);
+    // (a batch still queued on a slot reads the labels: both slots' streams and the synchronous call's are waited for)
+    (void)hipDeviceSynchronize();
+    if (b->labels) (void)hipFree(b->labels);
+    delete b;
+    return RC_OK;
+}
+
+RC_EXPORT uint32_t rc_bins_count(const rc_bins *b) { return b ? b->bins : 0; }
+
+// what both forms check before the device is asked for: from the arguments alone
+static int bins_admit(const rc_bins *b, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
+                      const int64_t *out, uint64_t out_cells)
+{
+    using namespace rc;
+    if (!b || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: NULL / zero argument");
+    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
+    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_bins_frames: bit_depth above 16 (as for the summed views)");
+    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: out must be aligned to its int64 cells");
+    if (out_cells < (uint64_t)n * BINS_PLANES * b->bins) return fail(RC_ERR_OUT_TOO_SMALL, "rc_bins_frames: out holds fewer than n * 2 * n_bins cells");
+    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
+    const uint64_t nb = ((uint64_t)b->nx * b->ny + 7) / 8;
+    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
+        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: the frames' geometry differs from the handle's");
+    return RC_OK;      // (no wrap rule: rc_bins.h - a cell stays below 2^48)
+}
+static int bins_run(rc_bins *b, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.bins: the handle's, filled in here)
+{
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_bins_frames_submit: slot 0 or 1");
+    int r = bins_admit(b, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
+    if (r != RC_OK) return r;
+    {
+        UtilScope util_scope;
+        if ((r = util_scope.enter()) != RC_OK) return r;
+        if (g_util.device != b->device) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: the handle belongs to another device");
+    }
+    q.in.nx = b->nx; q.in.ny = b->ny; q.bins = {b->labels, b->bins};
+    return expand_run(q, slot);
+}
+RC_EXPORT int rc_bins_frames(rc_bins *b, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
+                             uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
+{ return bins_run(b, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_BINS, .out = out, .cap = out_cells}); }
+RC_EXPORT int rc_bins_frames_submit(rc_bins *b, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
+                                    const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
+{ return bins_run(b, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_BINS, .out = out, .cap = out_cells}); }

@@ -166,6 +166,48 @@ def estimate_shifts(corr, group=1):
     return out
 
 
+def radial_labels(ny, nx, cy, cx, bin_width=1, n_bins=None):
+    """The label map of a radial (azimuthal) profile for get_frame_bins / _lib.FrameBins: uint16[ny, nx], pixel (r, c) in bin
+    isqrt((2 r - 2 cy)^2 + (2 c - 2 cx)^2) // (2 * bin_width) - floor(distance from (cy, cx) / bin_width) in exact integers.  cy, cx: integers
+    or odd halves (2 cy and 2 cx must be integers: a centre on a pixel or between two); bin_width: a positive integer.  n_bins: the bins
+    kept, 1 .. 4096 - a pixel beyond the last one gets 0xFFFF ("in no bin"); None: every bin the frame reaches (ValueError above 4096)."""
+    ny, nx, w = int(ny), int(nx), int(bin_width)
+    cy2, cx2 = 2 * cy, 2 * cx
+    if cy2 != int(cy2) or cx2 != int(cx2):
+        raise ValueError('radial_labels: cy and cx must be integers or odd halves')
+    if ny < 1 or nx < 1 or w < 1 or w != bin_width:
+        raise ValueError('radial_labels: ny, nx and bin_width must be positive integers')
+    cy2, cx2 = int(cy2), int(cx2)
+    dy, dx = 2 * np.arange(ny, dtype=np.int64) - cy2, 2 * np.arange(nx, dtype=np.int64) - cx2
+    if max(abs(int(dy[0])), abs(int(dy[-1]))) >= 1 << 30 or max(abs(int(dx[0])), abs(int(dx[-1]))) >= 1 << 30:
+        raise ValueError('radial_labels: the centre is too far from the frame')
+    sq = dy[:, None] ** 2 + dx[None, :] ** 2                       # below 2^61
+    root = np.floor(np.sqrt(sq.astype(np.float64))).astype(np.int64)
+    root -= root * root > sq                                        # (the float square root is off by one at most: put right in integers)
+    root += (root + 1) * (root + 1) <= sq
+    bins = root // (2 * w)
+    top = int(bins.max()) + 1
+    if n_bins is None:
+        n_bins = top
+        if n_bins > 4096:
+            raise ValueError('radial_labels: the frame reaches %d bins (4096 at most: a larger bin_width, or n_bins)' % n_bins)
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 4096:
+        raise ValueError('radial_labels: n_bins %d (1 .. 4096)' % n_bins)
+    return np.where(bins < n_bins, bins, 0xFFFF).astype(np.uint16)
+
+
+def bin_areas(labels, n_bins):
+    """int64[n_bins]: the pixels of every bin of a label map (0xFFFF and anything at or above n_bins: in no bin) - the denominator of a mean
+    profile, sum / (count of frames * area) or count / area"""
+    labels = np.asarray(labels)
+    if labels.dtype.kind not in 'iu':
+        raise ValueError('bin_areas: labels of dtype %s (an integer dtype)' % labels.dtype)
+    n_bins = int(n_bins)
+    flat = labels.reshape(-1).astype(np.int64)
+    return np.bincount(flat[(flat >= 0) & (flat < n_bins)], minlength=n_bins).astype(np.int64)
+
+
 def _event_views(buf, cap, total):
     """(rows int32, cols int32, area uint32, weight uint64): the first `total` events of rc_count_frames' output of capacity `cap`"""
     return (buf[8 * cap:12 * cap].view(np.int32)[:total], buf[12 * cap:16 * cap].view(np.int32)[:total],
@@ -408,6 +450,32 @@ class _Correlations(_Kind):
         k, S = job.count, self.fc.side
         cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(k, S, S)
         return job.first, self.as_dict(job.first, k, cells, job.payload.prefix)
+
+
+class _Bins(_Kind):
+    """A batch's binned traces (rc_bins_frames / _submit on the _lib.FrameBins fb): int64[k, 2, B] in the slot's page-locked output, handed
+    out as as_dict(first, k, cells) makes them"""
+    what = 'rc_bins_frames'
+
+    def __init__(self, fb, outs, as_dict):
+        self.fb, self.outs, self.as_dict = fb, outs, as_dict
+
+    def _cells(self, k):
+        return k * 2 * self.fb.n_bins
+
+    def room(self, job, geom, sizes, k):
+        self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * self._cells(k))
+
+    def call(self, job, geom, data, sizes, k, slot=None):
+        out = (self.outs[2 + job.slot]._p, self._cells(k))
+        if slot is not None:
+            return self.fb.submit_status(slot, geom, data, sizes, k, *out)
+        return self.fb.frames_status(geom, data, sizes, k, *out)
+
+    def item(self, job):
+        k = job.count
+        cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(k, 2, self.fb.n_bins)
+        return job.first, self.as_dict(job.first, k, cells)
 
 
 def _device_path(dev):
@@ -1333,6 +1401,7 @@ class BatchedAccess:
     _COUNTS = ('counting', 'the sums are exact in 64 bits for 16-bit values')
     _TRACES = ('frame traces', 'the sums are exact in 64 bits for 16-bit values')
     _CORR = ('correlation surfaces', 'the sums are exact in 64 bits for 16-bit values')
+    _BINS = ('binned frame traces', 'the sums are exact in 64 bits for 16-bit values')
 
     def _check_levels_and_bits(self, who, why):
         """levels 1 to 3, and at level 1 fields of 16 bits at most: NotImplementedError otherwise"""
@@ -1667,6 +1736,62 @@ class BatchedAccess:
             stream.close()
             if own:
                 fc.close()
+
+    # ---- binned frame traces (rc_bins_frames): per frame and bin of a label map the set pixels and their summed values ---------------------
+    def _bins_handle(self, labels, n_bins):
+        """(the _lib.FrameBins to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
+        nx, ny = int(self._header['nx']), int(self._header['ny'])
+        if isinstance(labels, _lib.FrameBins):
+            if (labels.nx, labels.ny) != (nx, ny):
+                raise ValueError('binned frame traces: a FrameBins of %d x %d for frames of %d x %d' % (labels.nx, labels.ny, nx, ny))
+            return labels, False
+        if labels is None:
+            raise ValueError('binned frame traces: labels are needed - an integer (ny, nx) array or GPU tensor, or a FrameBins')
+        return _lib.FrameBins(nx, ny, labels, n_bins), True
+
+    def _bins_dict(self, first, k, cells):
+        """a batch's int64[k, 2, B] as the dict get_frame_bins returns (copies of their own)"""
+        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
+        return {'count': cells[:, 0].copy(), 'sum': cells[:, 1].copy(), 'frame_ids': ids}
+
+    def _bins_stream(self, z0, n, batch, fb):
+        """The engine of get_frame_bins and iter_frame_bins: the batches go down the ladder as _Bins (rc_bins_frames_submit /
+        rc_expand_frames_wait on the two slots); 16 * B bytes per frame cross the link.  Yields (first frame, dict).  Routes and fall-backs
+        are the summed views' (sum_frames)."""
+        return self._ladder(_Bins(fb, self._bufs.stream, self._bins_dict), _jobs(z0, n, batch))
+
+    def get_frame_bins(self, z0, n, labels=None, n_bins=None):
+        """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) and per bin of the label map the number of set pixels and the
+        sum of their values, reduced ON THE DEVICE in one call (rc_bins_frames): 'count' int64[n, B], 'sum' int64[n, B] (levels 2 and 3:
+        every value is 1, so 'sum' equals 'count') and 'frame_ids' int64[n].  labels: an integer array or GPU tensor of shape (ny, nx), each
+        cell a bin 0 .. B - 1 or 0xFFFF ("in no bin") - radial_labels makes a radial profile's -, with n_bins = B (1 .. 4096; None: the
+        largest label + 1); or a _lib.FrameBins the caller made - n_bins is then the handle's -, so that the part files of a run share one
+        copy.  bin_areas(labels, B) is the denominator of a mean profile.  Routes (last_batch_path) and fall-backs as for sum_frames; files of
+        more than 16 bits are not taken (NotImplementedError)."""
+        n = self._frame_range(z0, n)
+        self._check_levels_and_bits(*self._BINS)
+        fb, own = self._bins_handle(labels, n_bins)
+        stream = self._bins_stream(z0, n, n, fb)      # (one batch of n frames)
+        try:
+            return next(stream)[1]
+        finally:
+            stream.close()
+            if own:
+                fb.close()
+
+    def iter_frame_bins(self, z0=0, n=None, batch=64, labels=None, n_bins=None):
+        """get_frame_bins for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two batches in
+        flight (rc_bins_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
+        n = self._frame_range(z0, n, batch)
+        self._check_levels_and_bits(*self._BINS)
+        fb, own = self._bins_handle(labels, n_bins)
+        stream = self._bins_stream(z0, n, batch, fb)
+        try:
+            yield from stream
+        finally:
+            stream.close()
+            if own:
+                fb.close()
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of
