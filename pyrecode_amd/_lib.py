@@ -92,23 +92,11 @@ SIGNATURES = {
     "rc_sum_add_counted_shifted_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 8 + [_u8p, _u32p] + [C.c_uint32] * 3 + [_i32p]),
     "rc_sum_fetch": (C.c_int, [C.c_void_p, _u32p, C.c_int]),
     "rc_sum_bound": (C.c_uint64, [C.c_void_p]),
-    "rc_trace_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
-    "rc_trace_destroy": (C.c_int, [C.c_void_p]),
     "rc_trace_columns": (C.c_uint32, [C.c_void_p]),
     "rc_trace_weight_bound": (C.c_uint32, [C.c_void_p, C.c_uint32]),
-    "rc_trace_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
-    "rc_trace_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
-    "rc_corr_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
-    "rc_corr_destroy": (C.c_int, [C.c_void_p]),
     "rc_corr_side": (C.c_uint32, [C.c_void_p]),
     "rc_corr_reference_bound": (C.c_uint32, [C.c_void_p]),
-    "rc_corr_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
-    "rc_corr_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
-    "rc_bins_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
-    "rc_bins_destroy": (C.c_int, [C.c_void_p]),
     "rc_bins_count": (C.c_uint32, [C.c_void_p]),
-    "rc_bins_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
-    "rc_bins_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "rc_host_decoder_available": (C.c_int, [C.c_uint32]),
     "rc_host_decode_streams": (C.c_int, [C.c_uint32, _u8p, _u8p, _u64p, C.c_uint32, C.c_uint32]),
     "rc_split_triplets": (C.c_int, [_u64p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -122,6 +110,13 @@ SIGNATURES = {
     "rc_synth_frames": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u16p, _u16p]),
     "rc_synth_frames_clustered": (C.c_int, [C.c_int] + [C.c_uint32] * 6 + [_u16p, _u16p]),
 }
+for _p in ("rc_trace", "rc_corr", "rc_bins"):      # the per-frame tables: the same four entry points per kind
+    SIGNATURES.update({
+        _p + "_create": (C.c_void_p, [C.c_uint32] * 3 + [C.c_void_p, C.POINTER(C.c_int)]),
+        _p + "_destroy": (C.c_int, [C.c_void_p]),
+        _p + "_frames": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64, _u64p]),
+        _p + "_frames_submit": (C.c_int, [C.c_void_p] + [C.c_uint32] * 5 + [_u8p, _u32p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    })
 
 _lib = None
 
@@ -372,6 +367,18 @@ class FrameSum:
     __del__ = close
 
 
+def library_device():
+    """The device the library's handle-making and batch calls run on: RC_DEVICE when it is set, otherwise torch's current device."""
+    import torch
+    return int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
+
+
+def on_library_device(tensor, who, what):
+    """ValueError for a GPU tensor that does not live on library_device(): a handle copies it there on streams of its own"""
+    if tensor.device.index != library_device():
+        raise ValueError("%s: %s on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (who, what, tensor.device, library_device()))
+
+
 def int32_planes(weights, nx, ny, max_planes, who, what="weights"):
     """(the planes as C-contiguous int32[k, ny, nx] - numpy, or torch on the GPU -, k): what FrameTrace takes as weights and FrameCorrelation
     as its reference (max_planes 1).  `who` and `what` word the ValueError of anything else."""
@@ -396,9 +403,7 @@ def int32_planes(weights, nx, ny, max_planes, who, what="weights"):
         # The library runs on the caller's current device (RC_DEVICE overrides it) and on streams of its own: the tensor must live on that
         # device, and everything queued on it - the kernels that produced the weights, the int32 copy below - must have finished before
         # the handle's create call reads it (the library's streams are not ordered behind torch's).
-        lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
-        if weights.device.index != lib_device:
-            raise ValueError("%s: %s on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (who, what, weights.device, lib_device))
+        on_library_device(weights, who, what)
         if weights.dtype not in (torch.int8, torch.int16, torch.int32, torch.uint8) and weights.numel():
             # (unsigned 32- and 64-bit values are judged through the signed view of the same width: what does not fit int32 is negative
             # there, or above 2^31 - 1; torch reduces signed dtypes only)
@@ -417,7 +422,66 @@ def int32_planes(weights, nx, ny, max_planes, who, what="weights"):
     return np.ascontiguousarray(weights.reshape(shape), dtype=np.int32), shape[0]
 
 
-class FrameTrace:
+class _FrameTable:
+    """What FrameTrace, FrameCorrelation and FrameBins share: a handle (rc_<kind>_create .. rc_<kind>_destroy, include/recode_hip.h) that
+    keeps one read-only plane on the device and turns a batch of stored frames into an int64 table, one row of out_shape(1) per frame.  A
+    subclass names its entry points' prefix and the verb of the geometry refusal, converts its input and calls _create, and says out_shape(n)."""
+
+    _prefix = None      # "rc_trace", "rc_corr", "rc_bins"
+    _verb = None        # "frames of .. <verb> with a handle of .."
+
+    def __init__(self, nx, ny):
+        self.nx, self.ny = int(nx), int(ny)
+        self._h = None
+
+    def _create(self, param, plane):
+        """rc_<kind>_create(nx, ny, param, plane): `plane` (numpy, a torch tensor, or None) is kept alive until the call has copied it"""
+        st = C.c_int(0)
+        addr = None if plane is None else plane.data_ptr() if hasattr(plane, "data_ptr") else ptr(plane)
+        self._h = getattr(lib(), self._prefix + "_create")(self.nx, self.ny, param, addr, C.byref(st))
+        if not self._h:
+            check(st.value, self._prefix + "_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _codec(self, geom):
+        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
+            raise ValueError("%s: frames of %d x %d %s with a handle of %d x %d" % (type(self).__name__, geom[0], geom[1], self._verb, self.nx, self.ny))
+        return tuple(int(v) for v in geom[2:6])
+
+    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
+        """rc_<kind>_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
+        return getattr(lib(), self._prefix + "_frames")(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
+
+    def frames(self, geom, data, sizes, n):
+        """The table of n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them):
+        (int64 of out_shape(n) - the class says what a row holds -, the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
+        out, prefix = np.empty(self.out_shape(n), np.int64), np.zeros(n + 1, np.uint64)
+        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), self._prefix + "_frames")
+        return out, prefix
+
+    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
+        """rc_<kind>_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
+        returned, which gives the verdict and the prefix)"""
+        return getattr(lib(), self._prefix + "_frames_submit")(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            getattr(_lib, self._prefix + "_destroy")(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+
+class FrameTrace(_FrameTable):
     """Frame traces on the device: rc_trace_create .. rc_trace_destroy (include/recode_hip.h) - per frame of a batch of stored frames the
     number of set pixels, the sum of their values, the sums weighted by row and by column, and the sums under k weight planes the handle
     keeps a copy of: int64[n, 4 + k], exact.  weights: None (the four moments alone), or a numpy array / a torch tensor on the GPU of shape
@@ -428,68 +492,26 @@ class FrameTrace:
     thread uses a handle at a time; the weights are read-only, so batches on both slots may share it."""
 
     MAX_PLANES = 16
+    _prefix, _verb = "rc_trace", "traced"
 
     def __init__(self, nx, ny, weights=None):
-        self.nx, self.ny = int(nx), int(ny)
-        planes, self.k = self._int32_planes(weights)       # (`planes` is kept alive until rc_trace_create has copied it)
-        st = C.c_int(0)
-        addr = None if planes is None else planes.data_ptr() if hasattr(planes, "data_ptr") else ptr(planes)
-        self._h = lib().rc_trace_create(self.nx, self.ny, self.k, addr, C.byref(st))
-        if not self._h:
-            check(st.value, "rc_trace_create")
-
-    def _int32_planes(self, weights):
-        """(the planes as C-contiguous int32[k, ny, nx] - numpy, or torch on the GPU -, k)"""
-        return int32_planes(weights, self.nx, self.ny, self.MAX_PLANES, "FrameTrace")
-
-    @property
-    def handle(self):
-        return self._h
+        super().__init__(nx, ny)
+        planes, self.k = int32_planes(weights, self.nx, self.ny, self.MAX_PLANES, "FrameTrace")
+        self._create(self.k, planes)
 
     @property
     def columns(self):
         return 4 + self.k
 
+    def out_shape(self, n):
+        return (n, self.columns)
+
     def weight_bounds(self):
         """max |W_m| of every plane, as the handle holds them for the no-wrap rule (INT32_MIN counts as 2^31)"""
         return [int(lib().rc_trace_weight_bound(self._h, m)) for m in range(self.k)]
 
-    def _codec(self, geom):
-        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
-            raise ValueError("FrameTrace: frames of %d x %d traced with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
-        return tuple(int(v) for v in geom[2:6])
 
-    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
-        """rc_trace_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
-        return lib().rc_trace_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
-
-    def frames(self, geom, data, sizes, n):
-        """Trace n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them): (int64[n, 4 + k],
-        the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
-        out, prefix = np.empty((n, self.columns), np.int64), np.zeros(n + 1, np.uint64)
-        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_trace_frames")
-        return out, prefix
-
-    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
-        """rc_trace_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
-        returned, which gives the verdict and the prefix)"""
-        return lib().rc_trace_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rc_trace_destroy(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    __del__ = close
-
-
-class FrameCorrelation:
+class FrameCorrelation(_FrameTable):
     """Correlation surfaces on the device: rc_corr_create .. rc_corr_destroy (include/recode_hip.h) - per frame of a batch of stored frames
     the overlap of its set pixels with a reference image at every offset of a window, int64[n, S, S] with S = 2 * radius + 1, exact:
     out[f, dy + R, dx + R] = sum v * reference[row + dy, col + dx] (0 outside the image).  reference: a numpy array / a torch tensor on the
@@ -499,17 +521,15 @@ class FrameCorrelation:
     FrameTrace."""
 
     MAX_RADIUS = 16
+    _prefix, _verb = "rc_corr", "correlated"
 
     def __init__(self, nx, ny, reference, radius=8):
-        self.nx, self.ny, self.radius = int(nx), int(ny), int(radius)
+        super().__init__(nx, ny)
+        self.radius = int(radius)
         if not 0 <= self.radius <= self.MAX_RADIUS:
             raise ValueError("FrameCorrelation: radius %d (0 .. %d)" % (self.radius, self.MAX_RADIUS))
-        self._h = None
         plane = self._from_sum(reference) if isinstance(reference, FrameSum) else int32_planes(reference, self.nx, self.ny, 1, "FrameCorrelation", "reference")[0]
-        st = C.c_int(0)                                    # (`plane` is kept alive until rc_corr_create has copied it)
-        self._h = lib().rc_corr_create(self.nx, self.ny, self.radius, plane.data_ptr() if hasattr(plane, "data_ptr") else ptr(plane), C.byref(st))
-        if not self._h:
-            check(st.value, "rc_corr_create")
+        self._create(self.radius, plane)
 
     def _from_sum(self, fs):
         """a FrameSum's cells as an int32 tensor on its device: rc_sum_fetch with a device destination, no trip over the link.  The cells
@@ -519,81 +539,43 @@ class FrameCorrelation:
         if fs.bound() > (1 << 31) - 1:
             raise ValueError("FrameCorrelation: the FrameSum's cells may exceed 2^31 - 1 (bound %d): they do not fit int32" % fs.bound())
         import torch
-        dev = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
-        cells = torch.empty((self.ny, self.nx), dtype=torch.int32, device="cuda:%d" % dev)
+        cells = torch.empty((self.ny, self.nx), dtype=torch.int32, device="cuda:%d" % library_device())
         check(lib().rc_sum_fetch(fs._h, cells.data_ptr(), 0), "rc_sum_fetch")      # (returns with the copy done)
         return cells
-
-    @property
-    def handle(self):
-        return self._h
 
     @property
     def side(self):
         return 2 * self.radius + 1
 
+    def out_shape(self, n):
+        return (n, self.side, self.side)
+
     def reference_bound(self):
         """max |reference| as the handle holds it for the no-wrap rule (INT32_MIN counts as 2^31)"""
         return int(lib().rc_corr_reference_bound(self._h))
 
-    def _codec(self, geom):
-        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
-            raise ValueError("FrameCorrelation: frames of %d x %d correlated with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
-        return tuple(int(v) for v in geom[2:6])
 
-    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
-        """rc_corr_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
-        return lib().rc_corr_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
-
-    def frames(self, geom, data, sizes, n):
-        """The surfaces of n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them):
-        (int64[n, S, S], the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
-        out, prefix = np.empty((n, self.side, self.side), np.int64), np.zeros(n + 1, np.uint64)
-        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_corr_frames")
-        return out, prefix
-
-    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
-        """rc_corr_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
-        returned, which gives the verdict and the prefix)"""
-        return lib().rc_corr_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rc_corr_destroy(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    __del__ = close
-
-
-class FrameBins:
+class FrameBins(_FrameTable):
     """Binned frame traces on the device: rc_bins_create .. rc_bins_destroy (include/recode_hip.h) - per frame of a batch of stored frames
-    and per bin of a label map the number of set pixels and the sum of their values, int64[n, 2, B], exact.  labels: a numpy array / a torch
+    and per bin of a label map the number of set pixels and the sum of their values, int64[n, 2, B] ([:, 0] the counts, [:, 1] the sums),
+    exact.  labels: a numpy array / a torch
     tensor on the GPU of shape (ny, nx) of any integer dtype whose values fit uint16 (a tensor by FrameTrace's rules for its device), each
     cell a bin 0 .. B - 1 or 0xFFFF ("in no bin").  n_bins: B, 1 .. 4096; None: max(label != 0xFFFF) + 1 (1 when every pixel is ignored).
     The handle keeps its own copy; batches on both slots and several readers may share it.  `geom` as for FrameTrace."""
 
     MAX_BINS = 4096
     IGNORE = 0xFFFF
+    _prefix, _verb = "rc_bins", "binned"
 
     def __init__(self, nx, ny, labels, n_bins=None):
-        self.nx, self.ny = int(nx), int(ny)
-        self._h = None
+        super().__init__(nx, ny)
         plane, top = self._uint16_labels(labels)
         self.n_bins = top + 1 if n_bins is None else int(n_bins)
         if not 1 <= self.n_bins <= self.MAX_BINS:
             raise ValueError("FrameBins: n_bins %d (1 .. %d)" % (self.n_bins, self.MAX_BINS))
         if top >= self.n_bins:
             raise ValueError("FrameBins: a label of %d with n_bins %d (bins are 0 .. n_bins - 1, 0xFFFF is 'in no bin')" % (top, self.n_bins))
-        st = C.c_int(0)                                    # (`plane` is kept alive until rc_bins_create has copied it)
-        self._h = lib().rc_bins_create(self.nx, self.ny, self.n_bins, plane.data_ptr() if hasattr(plane, "data_ptr") else ptr(plane), C.byref(st))
-        if not self._h:
-            check(st.value, "rc_bins_create")
+        self._create(self.n_bins, plane)
 
     def _uint16_labels(self, labels):
         """(the labels as C-contiguous uint16[ny, nx] - numpy, or torch on the GPU as int16 of the same bits -, the largest label that is
@@ -609,10 +591,7 @@ class FrameBins:
             import torch
             if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
                 raise ValueError("FrameBins: labels of dtype %s (an integer dtype whose values fit uint16)" % labels.dtype)
-            # (the tensor's device and the ordering before rc_bins_create reads it: as for FrameTrace's weights)
-            lib_device = int(os.environ["RC_DEVICE"]) if os.environ.get("RC_DEVICE") else torch.cuda.current_device()
-            if labels.device.index != lib_device:
-                raise ValueError("FrameBins: labels on %s, the handle is made on cuda:%d (the current device, or RC_DEVICE)" % (labels.device, lib_device))
+            on_library_device(labels, "FrameBins", "labels")      # (and the ordering before rc_bins_create reads it: as for FrameTrace's weights)
             unsigned = {getattr(torch, "uint16", None): torch.int32, getattr(torch, "uint32", None): torch.int64, getattr(torch, "uint64", None): torch.int64}
             # (torch reduces signed dtypes: uint16 and uint32 widen, uint64 is judged through its signed view - too large is negative there)
             wide = labels.view(torch.int64) if labels.dtype == getattr(torch, "uint64", None) else labels.to(unsigned.get(labels.dtype, labels.dtype))
@@ -630,43 +609,8 @@ class FrameBins:
         kept = labels[labels != self.IGNORE]
         return np.ascontiguousarray(labels, dtype=np.uint16), (int(kept.max()) if kept.size else 0)
 
-    @property
-    def handle(self):
-        return self._h
-
-    def _codec(self, geom):
-        if (int(geom[0]), int(geom[1])) != (self.nx, self.ny):
-            raise ValueError("FrameBins: frames of %d x %d binned with a handle of %d x %d" % (geom[0], geom[1], self.nx, self.ny))
-        return tuple(int(v) for v in geom[2:6])
-
-    def frames_status(self, geom, data, sizes, n, out, out_cells, prefix=None):
-        """rc_bins_frames, status returned (the readers fall back on RC_ERR_UNSUPPORTED / RC_ERR_CORRUPT); out: an array or an address"""
-        return lib().rc_bins_frames(self._h, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells, ptr(prefix))
-
-    def frames(self, geom, data, sizes, n):
-        """The bins of n stored frames (data: their blobs back to back, sizes uint32[n][3] - as rc_expand_frames takes them):
-        (int64[n, 2, B] - [:, 0] the counts, [:, 1] the sums -, the frames' set-pixel prefix uint64[n + 1]).  A rejected batch raises."""
-        out, prefix = np.empty((n, 2, self.n_bins), np.int64), np.zeros(n + 1, np.uint64)
-        check(self.frames_status(geom, data, sizes, n, out, out.size, prefix), "rc_bins_frames")
-        return out, prefix
-
-    def submit_status(self, slot, geom, data, sizes, n, out, out_cells):
-        """rc_bins_frames_submit on slot 0 or 1 (out: device or page-locked memory; data stays valid until rc_expand_frames_wait(slot) has
-        returned, which gives the verdict and the prefix)"""
-        return lib().rc_bins_frames_submit(self._h, slot, *self._codec(geom), ptr(data), ptr(sizes), n, ptr(out), out_cells)
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rc_bins_destroy(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    __del__ = close
+    def out_shape(self, n):
+        return (n, 2, self.n_bins)
 
 
 class ReduceContext:

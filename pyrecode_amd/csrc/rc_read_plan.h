@@ -1,7 +1,8 @@
 // rc_read_plan.h - the parts of the batched reader (rc_reader.hip) that hold no HIP call: what a result kind means for the expand kernels,
 // the verdict a finished batch gets from its error word, and how a staged output goes back to the caller.  Plain C++:
 // tests/native/read_plan_check.cpp walks all of it against tables written out by hand (tests/test_read_plan_cpu.py).
-// A new result kind fills in: a row of read_kind_info, its synchronous route (verdict_route_sync), its segments (read_copy_plan).
+// A new result kind fills in: a row of read_kind_info, its synchronous route (verdict_route_sync), its segments (read_copy_plan) - and a
+// hand-written row in each of read_plan_check.cpp's tables, which walk every kind up to RK_KINDS.
 #pragma once
 #include <stdint.h>
 #include "../../include/recode_hip.h"
@@ -10,9 +11,7 @@ namespace rc {
 // triplets, COO with uint16 / uint32 values, level-2 rows / columns + statistics, events (rc_count_frames), the adds into an rc_sum handle
 // (frames' values; one count per event), cells of a region (dense), 4 + k sums per frame (trace), a correlation surface per frame (corr), counts and sums per frame and
 // bin of a label map (bins).
-// RK_KINDS counts the kinds up to the traces - the rows read_plan_check.cpp's hand-written tables have; RK_CORR and RK_BINS sit behind them
-// (their rows are walked by tests/native/corr_index_check.cpp and bins_index_check.cpp), RK_ALL counts every kind.
-enum ReadKind : uint32_t { RK_TRIPLETS, RK_COO16, RK_COO32, RK_L2, RK_EVENTS, RK_SUM, RK_COUNTED_SUM, RK_DENSE, RK_TRACE, RK_KINDS, RK_CORR = RK_KINDS, RK_BINS, RK_ALL };
+enum ReadKind : uint32_t { RK_TRIPLETS, RK_COO16, RK_COO32, RK_L2, RK_EVENTS, RK_SUM, RK_COUNTED_SUM, RK_DENSE, RK_TRACE, RK_CORR, RK_BINS, RK_KINDS };
 struct ReadKindInfo {
     uint32_t esz;         // bytes per entry of the output, counted against the caller's capacity (0: the kind has no entries)
     uint32_t coo;         // what the emit kernel is told: 0 = triplets, else COO with values of that many bytes (RK_L2: 2, and no value array)
@@ -26,7 +25,7 @@ struct ReadKindInfo {
 inline ReadKindInfo read_kind_info(ReadKind k)
 {
     static const char *const entries = "rc_expand_frames_submit: triplets must be device or page-locked host memory";
-    static const ReadKindInfo table[RK_ALL] = {
+    static const ReadKindInfo table[RK_KINDS] = {
         /* RK_TRIPLETS    */ {24, 0, false, false, false, false, false, entries},
         /* RK_COO16       */ {10, 2, false, false, false, false, false, entries},
         /* RK_COO32       */ {12, 4, false, false, false, false, false, entries},

@@ -125,9 +125,9 @@ struct rc_sum {
 // ---- one request: what an entry point asks of expand_run ---------------------------------------------------------------------------------
 struct CountReq { uint32_t method, area_threshold, upsample; };
 struct DenseReq { rc::DenseRegion region; uint32_t cell_bytes; };
-struct TraceReq { const int32_t *weights; uint32_t k; };   // (the handle's interleaved weights and their planes)
-struct CorrReq { const int32_t *padded; uint32_t radius; };   // (the handle's zero-bordered reference and the window's radius)
-struct BinsReq { const uint16_t *labels; uint32_t bins; };    // (the handle's label map and its number of bins)
+// a per-frame table (trace, corr, bins): the handle's device plane, its parameter (weight planes k, radius R, bins B) and the cells of one
+// frame's row; a dense batch names its row - w * h cells - here too, so that every kind of cells has its output's size in one place
+struct TableReq { const void *plane; uint32_t param; uint64_t row_cells; };
 // slot, submit: the synchronous forms = (RC_READ_SLOTS - their own resources -, false); the _submit forms = (slot, true): they return once
 // everything is queued.  kind (rc_read_plan.h) says what out / cap are: entries of the kind's size (cap of them; NULL / 0: the prefix alone),
 // the cells of a dense, trace, corr or bins output (the entry points have checked that cap holds them), nothing for the adds into `sum`.  stats /
@@ -142,7 +142,7 @@ struct ReadRequest {
     rc::ReadKind kind = rc::RK_TRIPLETS; void *out = nullptr; uint64_t cap = 0;
     uint16_t *stats = nullptr; uint64_t stats_cap = 0;
     rc_sum *sum = nullptr; const int32_t *shifts = nullptr;
-    CountReq count{}; DenseReq dense{}; TraceReq trace{}; CorrReq corr{}; BinsReq bins{};
+    CountReq count{}; DenseReq dense{}; TableReq table{};
 };
 
 // `p` must be memory a queued copy can fill: RC_ERR_BAD_ARG with `msg` for anything but page-locked host memory
@@ -541,10 +541,7 @@ int ReadRun::route()
     // Entries wanted in DEVICE memory: the emit kernel is queued right behind the count - no host round trip in between; the kernel that
     // finishes the count (k_expand_bases) checks what the host otherwise would (total <= cap, value streams long enough) and the emit
     // kernel writes nothing once any check or decoder has raised *d_err.
-    if (q.kind == RK_TRACE) cell_bytes = (uint64_t)n * (TRACE_MOMENTS + q.trace.k) * 8;
-    if (q.kind == RK_CORR) cell_bytes = (uint64_t)n * corr_cells(q.corr.radius) * 8;
-    if (q.kind == RK_BINS) cell_bytes = (uint64_t)n * BINS_PLANES * q.bins.bins * 8;
-    if (q.kind == RK_DENSE) cell_bytes = (uint64_t)n * q.dense.region.w * q.dense.region.h * q.dense.cell_bytes;
+    if (k.cells) cell_bytes = (uint64_t)n * q.table.row_cells * (q.kind == RK_DENSE ? q.dense.cell_bytes : 8u);      // (a table's cells are int64)
     auto place = [&]() -> int {      // where the kernels write: the caller's device memory, or d_triplets for its host memory
         if (!out || is_device_ptr(out)) { target = out; return RC_OK; }
         host_dst = static_cast<uint8_t *>(out);
@@ -586,19 +583,19 @@ int ReadRun::route()
         d_prefix = cnt_ev_base(u.d_count.p, n);      // (the frames' EVENT prefix)
     } else if (q.kind == RK_TRACE) {
         // the per-(frame, block) partial sums live in the counting workspace: no counting request shares a batch with a trace
-        if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, q.trace.k) + 64)) != RC_OK) return r;
-        launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.trace.weights, q.trace.k,
-                                  u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+        if ((r = u.d_count.ensure(U.dmem, trace_workspace_bytes(nb8, n, q.table.param) + 64)) != RC_OK) return r;
+        launch_expand_batch_trace(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel,
+                                  static_cast<const int32_t *>(q.table.plane), q.table.param, u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
     } else if (q.kind == RK_CORR) {
         // (its per-(frame, chunk) partial rows live there too: corr_workspace_bytes, bounded by the launch's workgroups, not the frame's blocks)
-        if ((r = u.d_count.ensure(U.dmem, corr_workspace_bytes(nb8, n, q.corr.radius, WG) + 64)) != RC_OK) return r;
-        launch_expand_batch_corr(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.corr.padded, q.corr.radius,
-                                 u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+        if ((r = u.d_count.ensure(U.dmem, corr_workspace_bytes(nb8, n, q.table.param, WG) + 64)) != RC_OK) return r;
+        launch_expand_batch_corr(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel,
+                                 static_cast<const int32_t *>(q.table.plane), q.table.param, u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
     } else if (q.kind == RK_BINS) {
         // (and the per-(frame, chunk) rows of 2 B partials: bins_workspace_bytes, the output's size plus BINS_PARTIAL_BUDGET at most)
-        if ((r = u.d_count.ensure(U.dmem, bins_workspace_bytes(nb8, n, q.bins.bins, WG) + 64)) != RC_OK) return r;
-        launch_expand_batch_bins(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.bins.labels, q.bins.bins,
-                                 u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
+        if ((r = u.d_count.ensure(U.dmem, bins_workspace_bytes(nb8, n, q.table.param, WG) + 64)) != RC_OK) return r;
+        launch_expand_batch_bins(d_bm, bm_stride, nb8, N, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel,
+                                 static_cast<const uint16_t *>(q.table.plane), q.table.param, u.d_count.as<int64_t>(), static_cast<int64_t *>(target), d_err, s);
     } else if (q.kind == RK_DENSE)
         launch_expand_batch_dense(d_bm, bm_stride, nb8, N, nx, n, d_blk_off, d_pv, pv_stride, d.pv_bytes, bit_depth, klevel, q.dense.region,
                                   q.dense.cell_bytes, target, d_err, s);
@@ -793,7 +790,9 @@ static int dense_run(const uint32_t *slot, ReadRequest q)
 {
     if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_expand_frames_dense_submit: slot 0 or 1");
     const int r = dense_admit(q.in.nx, q.in.ny, q.in.bit_depth, q.in.level, q.in.n, q.dense, q.out, q.cap);
-    return r != RC_OK ? r : expand_run(q, slot);
+    if (r != RC_OK) return r;
+    q.table.row_cells = (uint64_t)q.dense.region.w * q.dense.region.h;
+    return expand_run(q, slot);
 }
 RC_EXPORT int rc_expand_frames_dense(uint32_t nx, uint32_t ny, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                      const uint32_t *sizes, uint32_t n, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t step_x, uint32_t step_y,
@@ -888,13 +887,13 @@ static int sum_admit(const rc_sum *s, uint32_t bit_depth, uint32_t level, uint32
         return fail(RC_ERR_OUT_TOO_SMALL, "rc_sum_add_frames: a cell could pass 2^32 - 1 (rc_sum_fetch with reset first)");
     return RC_OK;
 }
-static int sum_on_its_device(const rc_sum *s)
+// expand_run runs on the caller's current device or RC_DEVICE; what a handle (a view, a per-frame table) owns lives on the device it was created on
+static int handle_on_current_device(int device, const char *who)
 {
-    // (expand_run runs on the caller's current device or RC_DEVICE; the handle's cells live on the device it was created on)
     UtilScope util_scope;
-    int r = util_scope.enter();
+    const int r = util_scope.enter();
     if (r != RC_OK) return r;
-    return g_util.device == s->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_sum_add_frames: the handle belongs to another device");
+    return g_util.device == device ? RC_OK : fail(RC_ERR_BAD_ARG, (std::string(who) + ": the handle belongs to another device").c_str());
 }
 
 // the end of every add, plain or counted: the synchronous forms lend a prefix of their own to a caller without one; the bound grows with
@@ -915,7 +914,7 @@ static int sum_add_run(rc_sum *s, const uint32_t *slot, const char *slot_msg, co
     if (shifts_msg && !q.shifts) return fail(RC_ERR_BAD_ARG, shifts_msg);
     uint64_t grow = 0;
     int r = sum_admit(s, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.sizes, q.in.n, &grow);
-    if (r == RC_OK) r = sum_on_its_device(s);
+    if (r == RC_OK) r = handle_on_current_device(s->device, "rc_sum_add_frames");
     if (r != RC_OK) return r;
     q.in.nx = s->nx; q.in.ny = s->ny;
     return add_run(s, slot, grow, q);
@@ -963,11 +962,7 @@ static int counted_admit(const rc_sum *s, uint32_t nx, uint32_t ny, uint32_t ups
     int r = count_admit(nx, ny, bit_depth, level, method);
     if (r != RC_OK) return r;
     if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    {
-        UtilScope util_scope;
-        if ((r = util_scope.enter()) != RC_OK) return r;
-        if (g_util.device != s->device) return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: the handle belongs to another device");
-    }
+    if ((r = handle_on_current_device(s->device, "rc_sum_add_counted")) != RC_OK) return r;
     if ((uint64_t)upsample * nx != s->nx || (uint64_t)upsample * ny != s->ny)
         return fail(RC_ERR_BAD_ARG, "rc_sum_add_counted: the handle's shape is not (upsample * nx, upsample * ny)");
     // a frame's events: an aligned 2 x 2 block of pixels belongs to at most one 8-connected component; at level 1 the value stream has room
@@ -1010,335 +1005,256 @@ RC_EXPORT int rc_sum_add_counted_shifted_submit(rc_sum *s, uint32_t slot, uint32
                        {.in = {nx, ny, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_COUNTED_SUM, .shifts = shifts,
                         .count = {method, area_threshold, upsample}}); }
 
-// ---- frame traces: per frame the set pixels, the sum, its first moments and the sums under the handle's weight planes (rc_trace.hip) ----
-// The handle owns the weights: an interleaved copy, int32[ny * nx][kp] (kp = k rounded up to a multiple of 4; the padding planes are zero),
-// read-only after create - batches on both slots and the synchronous call may use it at once -, and every plane's maxabs for the no-wrap rule.
-struct rc_trace {
+// ---- per-frame tables: a batch of frames becomes int64[n][row_cells], one row per frame (rc_trace.hip, rc_corr.hip, rc_bins.hip) -----------
+// What the three kinds share.  A handle owns one plane in device memory, read-only after create - batches on both slots and the synchronous
+// call may use it at once - and knows the frames' shape, the kernels' parameter and the cells of a row.  A kind adds what its no-wrap rule needs:
+//   traces        int32[ny * nx][kp], the weight planes interleaved (kp = k rounded up to a multiple of 4; the padding planes are zero);
+//                 param = k, a row = the set pixels, the sum, its first moments and k weighted sums; every plane's maxabs
+//   correlations  int32[ny + 2 R][nx + 2 R], the reference inside a border of zeros; param = R, a row = the (2 R + 1)^2 cells of the window;
+//                 the reference's maxabs
+//   bins          uint16[ny][nx], the label map - every label below n_bins or BINS_IGNORE: create has checked it, the kernel relies on it
+//                 for nothing but the result; param = n_bins, a row = [counts n_bins][sums n_bins]; no rule (rc_bins.h: a cell stays below 2^48)
+struct FrameTable {
     int device = -1;
-    uint32_t nx = 0, ny = 0, k = 0;
-    int32_t *weights = nullptr;
-    uint32_t bound[rc::TRACE_MAX_PLANES] = {};
+    uint32_t nx = 0, ny = 0, param = 0;
+    void *plane = nullptr;
+    uint64_t row_cells = 0;
 };
+struct rc_trace : FrameTable { uint32_t bound[rc::TRACE_MAX_PLANES] = {}; };
+struct rc_corr : FrameTable { uint32_t bound = 0; };
+struct rc_bins : FrameTable {};
+// what a kind's calls say: who = the synchronous entry point (a NULL handle is answered in its name too, so it is not the handle's to keep);
+// row, wrap: the refusals of an output too small and of a batch that could wrap, behind `who`
+struct TableKind { rc::ReadKind kind; const char *who, *row, *wrap; };
+static const TableKind TRACE_KIND = {rc::RK_TRACE, "rc_trace_frames", ": out holds fewer than n * (4 + k) cells",
+                                     ": a column could pass 2^63 - 1 (largest weight * largest value * set pixels a frame can hold)"};
+static const TableKind CORR_KIND = {rc::RK_CORR, "rc_corr_frames", ": out holds fewer than n * (2 R + 1)^2 cells",
+                                    ": a cell could pass 2^63 - 1 (largest |reference| * largest value * set pixels a frame can hold)"};
+static const TableKind BINS_KIND = {rc::RK_BINS, "rc_bins_frames", ": out holds fewer than n * 2 * n_bins cells", nullptr};
 
-RC_EXPORT rc_trace *rc_trace_create(uint32_t nx, uint32_t ny, uint32_t k, const int32_t *planes, int *status)
+// Create, for every kind: `check` judges the kind's own arguments before the device is asked for (nullptr, or the refusal's text); `fill`
+// queues on `s` whatever brings the caller's data into t->plane and returns the first HIP error.  What it needs on the side it takes from
+// `tmp`, which is given back here, behind the wait - a fill may return wherever it fails.  plane_bytes 0: a handle without a plane.
+#define HIP_PASS(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+struct TableTemps {
+    std::vector<void *> held;
+    template <class P> hipError_t alloc(P **p, size_t bytes)
+    {
+        HIP_PASS(hipMalloc(reinterpret_cast<void **>(p), bytes));
+        held.push_back(*p);
+        return hipSuccess;
+    }
+};
+template <class T, class Check, class Fill>
+static T *table_create(const char *who, uint32_t nx, uint32_t ny, uint32_t param, uint64_t row_cells, uint64_t plane_bytes, int *status, Check check, Fill fill)
 {
-    using namespace rc;
-    auto done = [&](int code) { if (status) *status = code; return (rc_trace *)nullptr; };
-    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: nx, ny in 1..65535"));
-    if (k > TRACE_MAX_PLANES) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: at most 16 weight planes"));
-    if (k && !planes) return done(fail(RC_ERR_BAD_ARG, "rc_trace_create: planes is NULL with k > 0"));
+    auto done = [&](int code) { if (status) *status = code; return (T *)nullptr; };
+    const std::string name(who);
+    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, (name + ": nx, ny in 1..65535").c_str()));
+    if (const char *refusal = check()) return done(fail(RC_ERR_BAD_ARG, refusal));
     UtilScope util_scope;
     int r = util_scope.enter();
     if (r != RC_OK) return done(r);
-    rc_trace *t = new (std::nothrow) rc_trace;
-    if (!t) return done(fail(RC_ERR_WORKSPACE, "rc_trace_create: out of host memory"));
-    t->device = g_util.device; t->nx = nx; t->ny = ny; t->k = k;
-    if (k == 0) { if (status) *status = RC_OK; return t; }
-    const uint64_t N = (uint64_t)nx * ny;
-    const uint32_t kp = trace_padded_planes(k);
-    const bool on_device = is_device_ptr(planes);
-    hipStream_t s = g_util.stream;
-    int32_t *stage = nullptr;          // one plane of a host caller's, on its way into the interleaved copy
-    uint32_t *d_bound = nullptr;       // maxabs of a device caller's planes
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->weights), N * kp * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(t->weights, 0, N * kp * 4, s);
-    if (e == hipSuccess && !on_device) e = hipMalloc(reinterpret_cast<void **>(&stage), N * 4);
-    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_bound), TRACE_MAX_PLANES * 4);
-    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_bound, 0, TRACE_MAX_PLANES * 4, s);
-    for (uint32_t m = 0; m < k && e == hipSuccess; ++m) {
-        const int32_t *plane = planes + (uint64_t)m * N;
-        if (on_device) launch_trace_maxabs(plane, N, d_bound + m, s);
-        else {
-            uint32_t a = 0;
-            for (uint64_t p = 0; p < N; ++p) a = std::max(a, trace_abs(plane[p]));
-            t->bound[m] = a;
-            e = hipMemcpyAsync(stage, plane, N * 4, hipMemcpyHostToDevice, s);      // (`stage` is reused per plane: the stream orders copy and kernel)
-            plane = stage;
+    T *t = new (std::nothrow) T;
+    if (!t) return done(fail(RC_ERR_WORKSPACE, (name + ": out of host memory").c_str()));
+    t->device = g_util.device; t->nx = nx; t->ny = ny; t->param = param; t->row_cells = row_cells;
+    if (plane_bytes) {
+        TableTemps tmp;
+        hipStream_t s = g_util.stream;
+        hipError_t e = hipMalloc(&t->plane, plane_bytes);
+        if (e == hipSuccess) e = fill(t, tmp, s);
+        // (also after an error: copies and kernels queued before it may still read `tmp`'s memory and the caller's)
+        const hipError_t e_sync = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = e_sync;
+        for (void *p : tmp.held) (void)hipFree(p);
+        if (e != hipSuccess) {
+            r = hip_fail(e, who);
+            if (t->plane) (void)hipFree(t->plane);
+            delete t;
+            return done(r);
         }
-        if (e == hipSuccess) launch_trace_interleave(plane, N, m, kp, t->weights, s);
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e == hipSuccess && on_device) e = hipMemcpyAsync(t->bound, d_bound, k * 4, hipMemcpyDeviceToHost, s);
-    // (also after an error: copies and kernels queued before it may still read `stage`, `d_bound` and the caller's planes)
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e_sync;
-    if (stage) (void)hipFree(stage);
-    if (d_bound) (void)hipFree(d_bound);
-    if (e != hipSuccess) {
-        r = hip_fail(e, "rc_trace_create");
-        if (t->weights) (void)hipFree(t->weights);
-        delete t;
-        return done(r);
     }
     if (status) *status = RC_OK;
     return t;
 }
-
-RC_EXPORT int rc_trace_destroy(rc_trace *t)
+template <class T>
+static int table_destroy(T *t)
 {
     if (!t) return RC_OK;
     RC_ON_DEVICE(t->device);
-    // (a batch still queued on a slot reads the weights: both slots' streams and the synchronous call's are waited for)
+    // (a batch still queued on a slot reads the plane: both slots' streams and the synchronous call's are waited for)
     (void)hipDeviceSynchronize();
-    if (t->weights) (void)hipFree(t->weights);
+    if (t->plane) (void)hipFree(t->plane);
     delete t;
     return RC_OK;
 }
 
-RC_EXPORT uint32_t rc_trace_columns(const rc_trace *t) { return t ? rc::TRACE_MOMENTS + t->k : 0; }
-RC_EXPORT uint32_t rc_trace_weight_bound(const rc_trace *t, uint32_t m) { return t && m < t->k ? t->bound[m] : 0; }
-
-// what both forms check before the device is asked for: from the arguments alone
-static int trace_admit(const rc_trace *t, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
-                       const int64_t *out, uint64_t out_cells)
+// what both forms check before the device is asked for: from the arguments alone.  fits: the kind's no-wrap rule, asked last
+template <class Fits>
+static int table_admit(const TableKind &K, const FrameTable *t, const ReadFrames &in, const void *out, uint64_t out_cells, Fits fits)
 {
-    using namespace rc;
-    if (!t || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: NULL / zero argument");
-    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
-    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_trace_frames: bit_depth above 16 (as for the summed views)");
-    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: out must be aligned to its int64 cells");
-    if (out_cells < (uint64_t)n * (TRACE_MOMENTS + t->k)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_trace_frames: out holds fewer than n * (4 + k) cells");
+    auto refuse = [&](int code, const char *what) { return fail(code, (std::string(K.who) + what).c_str()); };
+    if (!t || !in.data || !in.sizes || !out || in.n == 0) return refuse(RC_ERR_BAD_ARG, ": NULL / zero argument");
+    if (in.level < 1 || in.level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
+    if (in.level == 1 && in.bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
+    if (in.level == 1 && in.bit_depth > 16) return refuse(RC_ERR_UNSUPPORTED, ": bit_depth above 16 (as for the summed views)");
+    if ((uintptr_t)out % 8) return refuse(RC_ERR_BAD_ARG, ": out must be aligned to its int64 cells");
+    if (out_cells < (uint64_t)in.n * t->row_cells) return refuse(RC_ERR_OUT_TOO_SMALL, K.row);
     // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
     const uint64_t nb = ((uint64_t)t->nx * t->ny + 7) / 8;
-    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
-        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_trace_frames: the frames' geometry differs from the handle's");
-    if (!trace_batch_fits(t->nx, t->ny, level, bit_depth, t->k, t->bound, sizes, n))
-        return fail(RC_ERR_OUT_TOO_SMALL, "rc_trace_frames: a column could pass 2^63 - 1 (largest weight * largest value * set pixels a frame can hold)");
-    return RC_OK;
+    for (uint32_t f = 0; f < in.n && in.op_mode == 0; ++f)
+        if (in.sizes[3 * f] != nb) return refuse(RC_ERR_BAD_ARG, ": the frames' geometry differs from the handle's");
+    return fits() ? RC_OK : refuse(RC_ERR_OUT_TOO_SMALL, K.wrap);
 }
-static int trace_on_its_device(const rc_trace *t)
+template <class Fits>
+static int table_run(const TableKind &K, FrameTable *t, const uint32_t *slot, ReadRequest q, Fits fits)      // (q.kind, q.in.nx, ny and q.table: filled in here)
 {
-    UtilScope util_scope;
-    int r = util_scope.enter();
+    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, (std::string(K.who) + "_submit: slot 0 or 1").c_str());
+    int r = table_admit(K, t, q.in, q.out, q.cap, fits);
+    if (r == RC_OK) r = handle_on_current_device(t->device, K.who);
     if (r != RC_OK) return r;
-    return g_util.device == t->device ? RC_OK : fail(RC_ERR_BAD_ARG, "rc_trace_frames: the handle belongs to another device");
-}
-static int trace_run(rc_trace *t, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.trace: the handle's, filled in here)
-{
-    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_trace_frames_submit: slot 0 or 1");
-    int r = trace_admit(t, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
-    if (r == RC_OK) r = trace_on_its_device(t);
-    if (r != RC_OK) return r;
-    q.in.nx = t->nx; q.in.ny = t->ny; q.trace = {t->weights, t->k};
+    q.kind = K.kind; q.in.nx = t->nx; q.in.ny = t->ny; q.table = {t->plane, t->param, t->row_cells};
     return expand_run(q, slot);
+}
+
+// ---- frame traces ---------------------------------------------------------------------------------------------------------------------------
+RC_EXPORT rc_trace *rc_trace_create(uint32_t nx, uint32_t ny, uint32_t k, const int32_t *planes, int *status)
+{
+    using namespace rc;
+    const uint64_t N = (uint64_t)nx * ny;
+    const uint32_t kp = trace_padded_planes(k);
+    auto check = [&]() -> const char * {
+        if (k > TRACE_MAX_PLANES) return "rc_trace_create: at most 16 weight planes";
+        return k && !planes ? "rc_trace_create: planes is NULL with k > 0" : nullptr;
+    };
+    auto fill = [&](rc_trace *t, TableTemps &tmp, hipStream_t s) -> hipError_t {
+        int32_t *weights = static_cast<int32_t *>(t->plane);
+        const bool on_device = is_device_ptr(planes);
+        int32_t *stage = nullptr;          // one plane of a host caller's, on its way into the interleaved copy
+        uint32_t *d_bound = nullptr;       // maxabs of a device caller's planes
+        HIP_PASS(hipMemsetAsync(weights, 0, N * kp * 4, s));
+        if (!on_device) HIP_PASS(tmp.alloc(&stage, N * 4));
+        else {
+            HIP_PASS(tmp.alloc(&d_bound, TRACE_MAX_PLANES * 4));
+            HIP_PASS(hipMemsetAsync(d_bound, 0, TRACE_MAX_PLANES * 4, s));
+        }
+        for (uint32_t m = 0; m < k; ++m) {
+            const int32_t *plane = planes + (uint64_t)m * N;
+            if (on_device) launch_trace_maxabs(plane, N, d_bound + m, s);
+            else {
+                uint32_t a = 0;
+                for (uint64_t p = 0; p < N; ++p) a = std::max(a, trace_abs(plane[p]));
+                t->bound[m] = a;
+                HIP_PASS(hipMemcpyAsync(stage, plane, N * 4, hipMemcpyHostToDevice, s));      // (`stage` is reused per plane: the stream orders copy and kernel)
+                plane = stage;
+            }
+            launch_trace_interleave(plane, N, m, kp, weights, s);
+            HIP_PASS(hipGetLastError());
+        }
+        return on_device ? hipMemcpyAsync(t->bound, d_bound, k * 4, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    return table_create<rc_trace>("rc_trace_create", nx, ny, k, TRACE_MOMENTS + k, N * kp * 4, status, check, fill);      // (k = 0: no plane)
+}
+RC_EXPORT int rc_trace_destroy(rc_trace *t) { return table_destroy(t); }
+RC_EXPORT uint32_t rc_trace_columns(const rc_trace *t) { return t ? (uint32_t)t->row_cells : 0; }
+RC_EXPORT uint32_t rc_trace_weight_bound(const rc_trace *t, uint32_t m) { return t && m < t->param ? t->bound[m] : 0; }
+static int trace_run(rc_trace *t, const uint32_t *slot, const ReadRequest &q)
+{
+    return table_run(TRACE_KIND, t, slot, q,
+                     [&] { return rc::trace_batch_fits(t->nx, t->ny, q.in.level, q.in.bit_depth, t->param, t->bound, q.in.sizes, q.in.n); });
 }
 RC_EXPORT int rc_trace_frames(rc_trace *t, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                               uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
-{ return trace_run(t, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_TRACE, .out = out, .cap = out_cells}); }
+{ return trace_run(t, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .out = out, .cap = out_cells}); }
 RC_EXPORT int rc_trace_frames_submit(rc_trace *t, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                      const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
-{ return trace_run(t, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_TRACE, .out = out, .cap = out_cells}); }
+{ return trace_run(t, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .out = out, .cap = out_cells}); }
 
-// ---- correlation surfaces: per frame the overlap of its set pixels with a reference image at every offset of a window (rc_corr.hip) ------
-// The handle owns the reference: a zero-bordered copy, int32[ny + 2 R][nx + 2 R], read-only after create - batches on both slots and the
-// synchronous call may use it at once -, and its maxabs for the no-wrap rule.
-struct rc_corr {
-    int device = -1;
-    uint32_t nx = 0, ny = 0, radius = 0;
-    int32_t *padded = nullptr;
-    uint32_t bound = 0;
-};
-
+// ---- correlation surfaces -------------------------------------------------------------------------------------------------------------------
 RC_EXPORT rc_corr *rc_corr_create(uint32_t nx, uint32_t ny, uint32_t radius, const int32_t *reference, int *status)
 {
     using namespace rc;
-    auto done = [&](int code) { if (status) *status = code; return (rc_corr *)nullptr; };
-    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: nx, ny in 1..65535"));
-    if (radius > CORR_MAX_RADIUS) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: radius at most 16"));
-    if (!reference) return done(fail(RC_ERR_BAD_ARG, "rc_corr_create: reference is NULL"));
-    UtilScope util_scope;
-    int r = util_scope.enter();
-    if (r != RC_OK) return done(r);
-    rc_corr *c = new (std::nothrow) rc_corr;
-    if (!c) return done(fail(RC_ERR_WORKSPACE, "rc_corr_create: out of host memory"));
-    c->device = g_util.device; c->nx = nx; c->ny = ny; c->radius = radius;
-    const uint64_t N = (uint64_t)nx * ny, bytes = corr_padded_cells(nx, ny, radius) * 4;
-    const uint32_t nxp = corr_padded_nx(nx, radius);
-    const bool on_device = is_device_ptr(reference);
-    hipStream_t s = g_util.stream;
-    uint32_t *d_bound = nullptr;       // maxabs of a device caller's reference
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->padded), bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(c->padded, 0, bytes, s);
-    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_bound), 4);
-    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_bound, 0, 4, s);
-    if (e == hipSuccess && on_device) {
-        launch_trace_maxabs(reference, N, d_bound, s);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&c->bound, d_bound, 4, hipMemcpyDeviceToHost, s);
-    } else if (e == hipSuccess)
-        for (uint64_t p = 0; p < N; ++p) c->bound = std::max(c->bound, trace_abs(reference[p]));
-    // the image's rows into the middle of the border (row r of T starts at padded (r + R, R))
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(c->padded + (uint64_t)radius * nxp + radius, (size_t)nxp * 4, reference, (size_t)nx * 4, (size_t)nx * 4, ny,
-                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
-    // (also after an error: what was queued before it may still read `d_bound` and the caller's reference)
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e_sync;
-    if (d_bound) (void)hipFree(d_bound);
-    if (e != hipSuccess) {
-        r = hip_fail(e, "rc_corr_create");
-        if (c->padded) (void)hipFree(c->padded);
-        delete c;
-        return done(r);
-    }
-    if (status) *status = RC_OK;
-    return c;
+    auto check = [&]() -> const char * {
+        if (radius > CORR_MAX_RADIUS) return "rc_corr_create: radius at most 16";
+        return reference ? nullptr : "rc_corr_create: reference is NULL";
+    };
+    auto fill = [&](rc_corr *c, TableTemps &tmp, hipStream_t s) -> hipError_t {
+        int32_t *padded = static_cast<int32_t *>(c->plane);
+        const uint64_t N = (uint64_t)nx * ny;
+        const uint32_t nxp = corr_padded_nx(nx, radius);
+        const bool on_device = is_device_ptr(reference);
+        uint32_t *d_bound = nullptr;       // maxabs of a device caller's reference
+        HIP_PASS(hipMemsetAsync(padded, 0, corr_padded_cells(nx, ny, radius) * 4, s));
+        if (on_device) {
+            HIP_PASS(tmp.alloc(&d_bound, 4));
+            HIP_PASS(hipMemsetAsync(d_bound, 0, 4, s));
+            launch_trace_maxabs(reference, N, d_bound, s);
+            HIP_PASS(hipGetLastError());
+            HIP_PASS(hipMemcpyAsync(&c->bound, d_bound, 4, hipMemcpyDeviceToHost, s));
+        } else
+            for (uint64_t p = 0; p < N; ++p) c->bound = std::max(c->bound, trace_abs(reference[p]));
+        // the image's rows into the middle of the border (row r of T starts at padded (r + R, R))
+        return hipMemcpy2DAsync(padded + (uint64_t)radius * nxp + radius, (size_t)nxp * 4, reference, (size_t)nx * 4, (size_t)nx * 4, ny,
+                                on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    };
+    return table_create<rc_corr>("rc_corr_create", nx, ny, radius, corr_cells(radius), corr_padded_cells(nx, ny, radius) * 4, status, check, fill);
 }
-
-RC_EXPORT int rc_corr_destroy(rc_corr *c)
-{
-    if (!c) return RC_OK;
-    RC_ON_DEVICE(c->device);
-    // (a batch still queued on a slot reads the reference: both slots' streams and the synchronous call's are waited for)
-    (void)hipDeviceSynchronize();
-    if (c->padded) (void)hipFree(c->padded);
-    delete c;
-    return RC_OK;
-}
-
-RC_EXPORT uint32_t rc_corr_side(const rc_corr *c) { return c ? rc::corr_side(c->radius) : 0; }
+RC_EXPORT int rc_corr_destroy(rc_corr *c) { return table_destroy(c); }
+RC_EXPORT uint32_t rc_corr_side(const rc_corr *c) { return c ? rc::corr_side(c->param) : 0; }
 RC_EXPORT uint32_t rc_corr_reference_bound(const rc_corr *c) { return c ? c->bound : 0; }
-
-// what both forms check before the device is asked for: from the arguments alone
-static int corr_admit(const rc_corr *c, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
-                      const int64_t *out, uint64_t out_cells)
+static int corr_run(rc_corr *c, const uint32_t *slot, const ReadRequest &q)
 {
-    using namespace rc;
-    if (!c || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: NULL / zero argument");
-    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
-    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_corr_frames: bit_depth above 16 (as for the summed views)");
-    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: out must be aligned to its int64 cells");
-    if (out_cells < (uint64_t)n * corr_cells(c->radius)) return fail(RC_ERR_OUT_TOO_SMALL, "rc_corr_frames: out holds fewer than n * (2 R + 1)^2 cells");
-    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
-    const uint64_t nb = ((uint64_t)c->nx * c->ny + 7) / 8;
-    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
-        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: the frames' geometry differs from the handle's");
-    if (!corr_batch_fits(c->nx, c->ny, level, bit_depth, c->bound, sizes, n))
-        return fail(RC_ERR_OUT_TOO_SMALL, "rc_corr_frames: a cell could pass 2^63 - 1 (largest |reference| * largest value * set pixels a frame can hold)");
-    return RC_OK;
-}
-static int corr_run(rc_corr *c, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.corr: the handle's, filled in here)
-{
-    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_corr_frames_submit: slot 0 or 1");
-    int r = corr_admit(c, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
-    if (r != RC_OK) return r;
-    {
-        UtilScope util_scope;
-        if ((r = util_scope.enter()) != RC_OK) return r;
-        if (g_util.device != c->device) return fail(RC_ERR_BAD_ARG, "rc_corr_frames: the handle belongs to another device");
-    }
-    q.in.nx = c->nx; q.in.ny = c->ny; q.corr = {c->padded, c->radius};
-    return expand_run(q, slot);
+    return table_run(CORR_KIND, c, slot, q, [&] { return rc::corr_batch_fits(c->nx, c->ny, q.in.level, q.in.bit_depth, c->bound, q.in.sizes, q.in.n); });
 }
 RC_EXPORT int rc_corr_frames(rc_corr *c, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                              uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
-{ return corr_run(c, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_CORR, .out = out, .cap = out_cells}); }
+{ return corr_run(c, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .out = out, .cap = out_cells}); }
 RC_EXPORT int rc_corr_frames_submit(rc_corr *c, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                     const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
-{ return corr_run(c, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_CORR, .out = out, .cap = out_cells}); }
+{ return corr_run(c, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .out = out, .cap = out_cells}); }
 
-// ---- binned frame traces: per frame and bin of a label map the set pixels and the sum of their values (rc_bins.hip) -----------------------
-// The handle owns the label map, uint16[ny][nx], read-only after create - batches on both slots and the synchronous call may use it at
-// once.  Every label is below n_bins or BINS_IGNORE: create has checked it, the kernel relies on it for nothing but the result.
-struct rc_bins {
-    int device = -1;
-    uint32_t nx = 0, ny = 0, bins = 0;
-    uint16_t *labels = nullptr;
-};
-
+// ---- binned frame traces --------------------------------------------------------------------------------------------------------------------
 RC_EXPORT rc_bins *rc_bins_create(uint32_t nx, uint32_t ny, uint32_t n_bins, const uint16_t *labels, int *status)
 {
     using namespace rc;
-    auto done = [&](int code) { if (status) *status = code; return (rc_bins *)nullptr; };
     static const char *const range = "rc_bins_create: a label at or above n_bins that is not 0xFFFF";
-    if (nx == 0 || ny == 0 || nx > 65535u || ny > 65535u) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: nx, ny in 1..65535"));
-    if (n_bins == 0 || n_bins > BINS_MAX) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: n_bins in 1..4096"));
-    if (!labels) return done(fail(RC_ERR_BAD_ARG, "rc_bins_create: labels is NULL"));
     const uint64_t N = (uint64_t)nx * ny;
-    // (without a GPU no pointer is a device pointer: host labels are judged before the device is asked for)
-    const bool on_device = is_device_ptr(labels);
-    if (!on_device)
-        for (uint64_t p = 0; p < N; ++p)
-            if (labels[p] >= n_bins && labels[p] != BINS_IGNORE) return done(fail(RC_ERR_BAD_ARG, range));
-    UtilScope util_scope;
-    int r = util_scope.enter();
-    if (r != RC_OK) return done(r);
-    rc_bins *b = new (std::nothrow) rc_bins;
-    if (!b) return done(fail(RC_ERR_WORKSPACE, "rc_bins_create: out of host memory"));
-    b->device = g_util.device; b->nx = nx; b->ny = ny; b->bins = n_bins;
-    hipStream_t s = g_util.stream;
-    uint32_t *d_top = nullptr, top = 0;      // the largest label of a device caller's map
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->labels), N * 2);
-    if (e == hipSuccess && on_device) e = hipMalloc(reinterpret_cast<void **>(&d_top), 4);
-    if (e == hipSuccess && on_device) e = hipMemsetAsync(d_top, 0, 4, s);
-    if (e == hipSuccess && on_device) {
-        launch_bins_label_max(labels, N, d_top, s);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&top, d_top, 4, hipMemcpyDeviceToHost, s);
+    bool on_device = false;
+    uint32_t top = 0;      // the largest label of a device caller's map: known behind create's wait
+    auto check = [&]() -> const char * {
+        if (n_bins == 0 || n_bins > BINS_MAX) return "rc_bins_create: n_bins in 1..4096";
+        if (!labels) return "rc_bins_create: labels is NULL";
+        // (without a GPU no pointer is a device pointer: host labels are judged before the device is asked for)
+        on_device = is_device_ptr(labels);
+        for (uint64_t p = 0; p < N && !on_device; ++p)
+            if (labels[p] >= n_bins && labels[p] != BINS_IGNORE) return range;
+        return nullptr;
+    };
+    auto fill = [&](rc_bins *b, TableTemps &tmp, hipStream_t s) -> hipError_t {
+        uint32_t *d_top = nullptr;
+        if (on_device) {
+            HIP_PASS(tmp.alloc(&d_top, 4));
+            HIP_PASS(hipMemsetAsync(d_top, 0, 4, s));
+            launch_bins_label_max(labels, N, d_top, s);
+            HIP_PASS(hipGetLastError());
+            HIP_PASS(hipMemcpyAsync(&top, d_top, 4, hipMemcpyDeviceToHost, s));
+        }
+        return hipMemcpyAsync(b->plane, labels, N * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    };
+    rc_bins *b = table_create<rc_bins>("rc_bins_create", nx, ny, n_bins, (uint64_t)BINS_PLANES * n_bins, N * 2, status, check, fill);
+    if (b && top >= n_bins) {      // device labels are judged here: the handle goes the way every handle goes
+        (void)table_destroy(b);
+        b = nullptr;
+        if (status) *status = fail(RC_ERR_BAD_ARG, range);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(b->labels, labels, N * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
-    // (also after an error: what was queued before it may still read `d_top` and the caller's labels)
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e_sync;
-    if (d_top) (void)hipFree(d_top);
-    if (e == hipSuccess && top < n_bins) {
-        if (status) *status = RC_OK;
-        return b;
-    }
-    r = e != hipSuccess ? hip_fail(e, "rc_bins_create") : fail(RC_ERR_BAD_ARG, range);
-    if (b->labels) (void)hipFree(b->labels);
-    delete b;
-    return done(r);
+    return b;
 }
-
-RC_EXPORT int rc_bins_destroy(rc_bins *b)
-{
-    if (!b) return RC_OK;
-    RC_ON_DEVICE(b->device);
-    // (a batch still queued on a slot reads the labels: both slots' streams and the synchronous call's are waited for)
-    (void)hipDeviceSynchronize();
-    if (b->labels) (void)hipFree(b->labels);
-    delete b;
-    return RC_OK;
-}
-
-RC_EXPORT uint32_t rc_bins_count(const rc_bins *b) { return b ? b->bins : 0; }
-
-// what both forms check before the device is asked for: from the arguments alone
-static int bins_admit(const rc_bins *b, uint32_t bit_depth, uint32_t level, uint32_t op_mode, const uint8_t *data, const uint32_t *sizes, uint32_t n,
-                      const int64_t *out, uint64_t out_cells)
-{
-    using namespace rc;
-    if (!b || !data || !sizes || !out || n == 0) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: NULL / zero argument");
-    if (level < 1 || level > 3) return fail(RC_ERR_UNSUPPORTED, "rc_expand_frames: reduction level 1, 2 or 3");
-    if (level == 1 && bit_depth == 0) return fail(RC_ERR_BAD_ARG, "bit_depth must be 1..64");
-    if (level == 1 && bit_depth > 16) return fail(RC_ERR_UNSUPPORTED, "rc_bins_frames: bit_depth above 16 (as for the summed views)");
-    if ((uintptr_t)out % 8) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: out must be aligned to its int64 cells");
-    if (out_cells < (uint64_t)n * BINS_PLANES * b->bins) return fail(RC_ERR_OUT_TOO_SMALL, "rc_bins_frames: out holds fewer than n * 2 * n_bins cells");
-    // the frame shape is the handle's; stored streams (op_mode 0) show another one on their face - compressed ones when they decode (RC_ERR_CORRUPT)
-    const uint64_t nb = ((uint64_t)b->nx * b->ny + 7) / 8;
-    for (uint32_t f = 0; f < n && op_mode == 0; ++f)
-        if (sizes[3 * f] != nb) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: the frames' geometry differs from the handle's");
-    return RC_OK;      // (no wrap rule: rc_bins.h - a cell stays below 2^48)
-}
-static int bins_run(rc_bins *b, const uint32_t *slot, ReadRequest q)      // (q.in.nx, ny and q.bins: the handle's, filled in here)
-{
-    if (slot && *slot >= RC_READ_SLOTS) return fail(RC_ERR_BAD_ARG, "rc_bins_frames_submit: slot 0 or 1");
-    int r = bins_admit(b, q.in.bit_depth, q.in.level, q.in.op_mode, q.in.data, q.in.sizes, q.in.n, static_cast<const int64_t *>(q.out), q.cap);
-    if (r != RC_OK) return r;
-    {
-        UtilScope util_scope;
-        if ((r = util_scope.enter()) != RC_OK) return r;
-        if (g_util.device != b->device) return fail(RC_ERR_BAD_ARG, "rc_bins_frames: the handle belongs to another device");
-    }
-    q.in.nx = b->nx; q.in.ny = b->ny; q.bins = {b->labels, b->bins};
-    return expand_run(q, slot);
-}
+RC_EXPORT int rc_bins_destroy(rc_bins *b) { return table_destroy(b); }
+RC_EXPORT uint32_t rc_bins_count(const rc_bins *b) { return b ? b->param : 0; }
+static int bins_run(rc_bins *b, const uint32_t *slot, const ReadRequest &q) { return table_run(BINS_KIND, b, slot, q, [] { return true; }); }
 RC_EXPORT int rc_bins_frames(rc_bins *b, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data, const uint32_t *sizes,
                              uint32_t n, int64_t *out, uint64_t out_cells, uint64_t *nnz_prefix)
-{ return bins_run(b, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .kind = rc::RK_BINS, .out = out, .cap = out_cells}); }
+{ return bins_run(b, nullptr, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .nnz_prefix = nnz_prefix, .out = out, .cap = out_cells}); }
 RC_EXPORT int rc_bins_frames_submit(rc_bins *b, uint32_t slot, uint32_t bit_depth, uint32_t level, uint32_t op_mode, uint32_t scheme, const uint8_t *data,
                                     const uint32_t *sizes, uint32_t n, int64_t *out, uint64_t out_cells)
-{ return bins_run(b, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .kind = rc::RK_BINS, .out = out, .cap = out_cells}); }
+{ return bins_run(b, &slot, {.in = {0, 0, bit_depth, level, op_mode, scheme, data, sizes, n}, .out = out, .cap = out_cells}); }

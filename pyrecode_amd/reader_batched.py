@@ -404,37 +404,19 @@ class _Dense(_Kind):
         return job.payload.index, self.outs[2 + job.slot].array[:self._cells(k) * self.dt.itemsize].view(self.dt).reshape(k, h, w)
 
 
-class _Traces(_Kind):
-    """A batch's traces (rc_trace_frames / _submit on the _lib.FrameTrace ft): int64[k, ft.columns] in the slot's page-locked output,
-    handed out as as_dict(first, k, cells) makes them."""
-    what = 'rc_trace_frames'
+class _Tables(_Kind):
+    """A batch's per-frame table (rc_trace_frames, rc_corr_frames or rc_bins_frames / _submit on `handle`, the _lib.FrameTrace,
+    FrameCorrelation or FrameBins): int64 of handle.out_shape(k) in the slot's page-locked output, handed out as as_dict(first, k, cells)
+    makes it - as_dict(first, k, cells, prefix) with `with_prefix`, for a dict that holds the frames' set pixels.  The synchronous call's
+    set-pixel prefix is kept where a waited-for verdict's is (job.payload.prefix): whichever call answered last says how many pixels the
+    frames have."""
 
-    def __init__(self, ft, outs, as_dict):
-        self.ft, self.outs, self.as_dict = ft, outs, as_dict
-
-    def room(self, job, geom, sizes, k):
-        self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * k * self.ft.columns)
-
-    def call(self, job, geom, data, sizes, k, slot=None):
-        out = (self.outs[2 + job.slot]._p, k * self.ft.columns)
-        return self.ft.frames_status(geom, data, sizes, k, *out) if slot is None else self.ft.submit_status(slot, geom, data, sizes, k, *out)
-
-    def item(self, job):
-        k, cols = job.count, self.ft.columns
-        return job.first, self.as_dict(job.first, k, self.outs[2 + job.slot].array[:8 * k * cols].view(np.int64).reshape(k, cols))
-
-
-class _Correlations(_Kind):
-    """A batch's correlation surfaces (rc_corr_frames / _submit on the _lib.FrameCorrelation fc): int64[k, S, S] in the slot's page-locked
-    output, handed out as as_dict(first, k, cells, prefix) makes them.  The synchronous call's set-pixel prefix is kept where a waited-for
-    verdict's is (job.payload.prefix): whichever call answered last says how many pixels the frames have."""
-    what = 'rc_corr_frames'
-
-    def __init__(self, fc, outs, as_dict):
-        self.fc, self.outs, self.as_dict = fc, outs, as_dict
+    def __init__(self, handle, outs, as_dict, with_prefix=False):
+        self.handle, self.outs, self.as_dict, self.with_prefix = handle, outs, as_dict, with_prefix
+        self.what = handle._prefix + '_frames'
 
     def _cells(self, k):
-        return k * self.fc.side * self.fc.side
+        return int(np.prod(self.handle.out_shape(k)))
 
     def room(self, job, geom, sizes, k):
         self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * self._cells(k))
@@ -442,40 +424,14 @@ class _Correlations(_Kind):
     def call(self, job, geom, data, sizes, k, slot=None):
         out = (self.outs[2 + job.slot]._p, self._cells(k))
         if slot is not None:
-            return self.fc.submit_status(slot, geom, data, sizes, k, *out)
+            return self.handle.submit_status(slot, geom, data, sizes, k, *out)
         job.payload.prefix = np.zeros(k + 1, np.uint64)
-        return self.fc.frames_status(geom, data, sizes, k, *out, job.payload.prefix)
-
-    def item(self, job):
-        k, S = job.count, self.fc.side
-        cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(k, S, S)
-        return job.first, self.as_dict(job.first, k, cells, job.payload.prefix)
-
-
-class _Bins(_Kind):
-    """A batch's binned traces (rc_bins_frames / _submit on the _lib.FrameBins fb): int64[k, 2, B] in the slot's page-locked output, handed
-    out as as_dict(first, k, cells) makes them"""
-    what = 'rc_bins_frames'
-
-    def __init__(self, fb, outs, as_dict):
-        self.fb, self.outs, self.as_dict = fb, outs, as_dict
-
-    def _cells(self, k):
-        return k * 2 * self.fb.n_bins
-
-    def room(self, job, geom, sizes, k):
-        self.outs[2 + job.slot] = _pinned(self.outs[2 + job.slot], 8 * self._cells(k))
-
-    def call(self, job, geom, data, sizes, k, slot=None):
-        out = (self.outs[2 + job.slot]._p, self._cells(k))
-        if slot is not None:
-            return self.fb.submit_status(slot, geom, data, sizes, k, *out)
-        return self.fb.frames_status(geom, data, sizes, k, *out)
+        return self.handle.frames_status(geom, data, sizes, k, *out, job.payload.prefix)
 
     def item(self, job):
         k = job.count
-        cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(k, 2, self.fb.n_bins)
-        return job.first, self.as_dict(job.first, k, cells)
+        cells = self.outs[2 + job.slot].array[:8 * self._cells(k)].view(np.int64).reshape(self.handle.out_shape(k))
+        return job.first, self.as_dict(job.first, k, cells, *((job.payload.prefix,) if self.with_prefix else ()))
 
 
 def _device_path(dev):
@@ -1621,27 +1577,51 @@ class BatchedAccess:
         vol = vol[::-1 if fz else 1, ::-1 if fy else 1, ::-1 if fx else 1]
         return vol[0 if dz else slice(None), 0 if dy else slice(None), 0 if dx else slice(None)]
 
-    # ---- frame traces (rc_trace_frames): a few exact integers per frame, reduced on the device --------------------------------------------
-    def _trace_handle(self, weights):
-        """(the _lib.FrameTrace to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
+    # ---- per-frame tables: frame traces (rc_trace_frames), correlation surfaces (rc_corr_frames), binned traces (rc_bins_frames) - a few
+    # exact integers per frame, reduced on the device.  One engine; a kind is its limits, its handle and the dict it makes of a batch's cells
+    def _frame_ids(self, first, k):
+        """the indices of frames first .. first + k - 1, a part file's frame ids"""
+        return self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
+
+    def _table_handle(self, arg, cls, make, what):
+        """(the handle to use, whether this call made it): a caller's `cls` as it is - its shape must be the file's -, else make(nx, ny)"""
         nx, ny = int(self._header['nx']), int(self._header['ny'])
-        if isinstance(weights, _lib.FrameTrace):
-            if (weights.nx, weights.ny) != (nx, ny):
-                raise ValueError('frame traces: a FrameTrace of %d x %d for frames of %d x %d' % (weights.nx, weights.ny, nx, ny))
-            return weights, False
-        return _lib.FrameTrace(nx, ny, weights), True
+        if isinstance(arg, cls):
+            if (arg.nx, arg.ny) != (nx, ny):
+                raise ValueError('%s: a %s of %d x %d for frames of %d x %d' % (what, cls.__name__, arg.nx, arg.ny, nx, ny))
+            return arg, False
+        return make(nx, ny), True
+
+    def _table_stream(self, z0, n, batch, limits, arg, cls, make, as_dict, with_prefix=False):
+        """The engine of the six methods below, a generator: the file's levels and bits are judged, then the handle (_table_handle), and the
+        batches go down the ladder as _Tables (rc_<kind>_frames_submit / rc_expand_frames_wait on the two slots), so the next batch is read
+        from the file and queued before this one is waited for; 8 bytes per cell of a frame's row cross the link.  Yields (first frame,
+        dict).  Routes and fall-backs are the summed views' (sum_frames).  The stream is always closed, the handle if this call made it."""
+        self._check_levels_and_bits(*limits)
+        handle, own = self._table_handle(arg, cls, make, limits[0])
+        stream = self._ladder(_Tables(handle, self._bufs.stream, as_dict, with_prefix), _jobs(z0, n, batch))
+        try:
+            yield from stream
+        finally:
+            stream.close()
+            if own:
+                handle.close()
+
+    @staticmethod
+    def _only_batch(stream):
+        """the dict of a _table_stream of one batch"""
+        try:
+            return next(stream)[1]
+        finally:
+            stream.close()
 
     def _trace_dict(self, first, k, cells):
         """a batch's int64[k, 4 + planes] as the dict get_frame_traces returns (copies of their own)"""
-        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
         return {'count': cells[:, 0].copy(), 'sum': cells[:, 1].copy(), 'sum_row': cells[:, 2].copy(), 'sum_col': cells[:, 3].copy(),
-                'weighted': cells[:, 4:].copy(), 'frame_ids': ids}
+                'weighted': cells[:, 4:].copy(), 'frame_ids': self._frame_ids(first, k)}
 
-    def _trace_stream(self, z0, n, batch, ft):
-        """The engine of get_frame_traces and iter_frame_traces: the batches go down the ladder as traces (_Traces: rc_trace_frames_submit /
-        rc_expand_frames_wait on the two slots), so the next batch is read from the file and queued before this one is waited for;
-        8 * (4 + k) bytes per frame cross the link.  Yields (first frame, dict).  Routes and fall-backs are the summed views' (sum_frames)."""
-        return self._ladder(_Traces(ft, self._bufs.stream, self._trace_dict), _jobs(z0, n, batch))
+    def _trace_stream(self, z0, n, batch, weights):
+        return self._table_stream(z0, n, batch, self._TRACES, weights, _lib.FrameTrace, lambda nx, ny: _lib.FrameTrace(nx, ny, weights), self._trace_dict)
 
     def get_frame_traces(self, z0, n, weights=None):
         """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) a few exact integers, reduced ON THE DEVICE in one call
@@ -1655,52 +1635,24 @@ class BatchedAccess:
         in which a column could pass 2^63 - 1 raises ValueError.  Routes (last_batch_path) and fall-backs as for sum_frames; files of more
         than 16 bits are not taken (NotImplementedError)."""
         n = self._frame_range(z0, n)
-        self._check_levels_and_bits(*self._TRACES)
-        ft, own = self._trace_handle(weights)
-        stream = self._trace_stream(z0, n, n, ft)      # (one batch of n frames)
-        try:
-            return next(stream)[1]
-        finally:
-            stream.close()
-            if own:
-                ft.close()
+        return self._only_batch(self._trace_stream(z0, n, n, weights))
 
     def iter_frame_traces(self, z0=0, n=None, batch=64, weights=None):
         """get_frame_traces for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two batches in
         flight (rc_trace_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
         n = self._frame_range(z0, n, batch)
-        self._check_levels_and_bits(*self._TRACES)
-        ft, own = self._trace_handle(weights)
-        stream = self._trace_stream(z0, n, batch, ft)
-        try:
-            yield from stream
-        finally:
-            stream.close()
-            if own:
-                ft.close()
-
-    # ---- correlation surfaces (rc_corr_frames): what drift estimation needs of every frame, summed on the device -------------------------
-    def _corr_handle(self, reference, radius):
-        """(the _lib.FrameCorrelation to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
-        nx, ny = int(self._header['nx']), int(self._header['ny'])
-        if isinstance(reference, _lib.FrameCorrelation):
-            if (reference.nx, reference.ny) != (nx, ny):
-                raise ValueError('correlation surfaces: a FrameCorrelation of %d x %d for frames of %d x %d' % (reference.nx, reference.ny, nx, ny))
-            return reference, False
-        if reference is None:
-            raise ValueError('correlation surfaces: a reference is needed - an integer (ny, nx) array or GPU tensor, a FrameSum, or a FrameCorrelation')
-        return _lib.FrameCorrelation(nx, ny, reference, radius), True
+        yield from self._trace_stream(z0, n, batch, weights)
 
     def _corr_dict(self, first, k, cells, prefix):
         """a batch's int64[k, S, S] and set-pixel prefix as the dict get_frame_correlations returns (copies of their own)"""
-        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
-        return {'corr': cells.copy(), 'count': np.diff(np.asarray(prefix[:k + 1]).astype(np.int64)), 'frame_ids': ids}
+        return {'corr': cells.copy(), 'count': np.diff(np.asarray(prefix[:k + 1]).astype(np.int64)), 'frame_ids': self._frame_ids(first, k)}
 
-    def _corr_stream(self, z0, n, batch, fc):
-        """The engine of get_frame_correlations and iter_frame_correlations: the batches go down the ladder as _Correlations
-        (rc_corr_frames_submit / rc_expand_frames_wait on the two slots); 8 * S^2 bytes per frame cross the link.  Yields (first frame,
-        dict).  Routes and fall-backs are the summed views' (sum_frames)."""
-        return self._ladder(_Correlations(fc, self._bufs.stream, self._corr_dict), _jobs(z0, n, batch))
+    def _corr_stream(self, z0, n, batch, reference, radius):
+        def make(nx, ny):
+            if reference is None:
+                raise ValueError('correlation surfaces: a reference is needed - an integer (ny, nx) array or GPU tensor, a FrameSum, or a FrameCorrelation')
+            return _lib.FrameCorrelation(nx, ny, reference, radius)
+        return self._table_stream(z0, n, batch, self._CORR, reference, _lib.FrameCorrelation, make, self._corr_dict, with_prefix=True)
 
     def get_frame_correlations(self, z0, n, reference=None, radius=8):
         """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) its correlation surface with `reference`, summed ON THE
@@ -1713,52 +1665,24 @@ class BatchedAccess:
         the part files of a run share one copy.  A batch in which a cell could pass 2^63 - 1 raises ValueError.  Routes
         (last_batch_path) and fall-backs as for sum_frames; files of more than 16 bits are not taken (NotImplementedError)."""
         n = self._frame_range(z0, n)
-        self._check_levels_and_bits(*self._CORR)
-        fc, own = self._corr_handle(reference, radius)
-        stream = self._corr_stream(z0, n, n, fc)      # (one batch of n frames)
-        try:
-            return next(stream)[1]
-        finally:
-            stream.close()
-            if own:
-                fc.close()
+        return self._only_batch(self._corr_stream(z0, n, n, reference, radius))
 
     def iter_frame_correlations(self, z0=0, n=None, batch=64, reference=None, radius=8):
         """get_frame_correlations for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two
         batches in flight (rc_corr_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
         n = self._frame_range(z0, n, batch)
-        self._check_levels_and_bits(*self._CORR)
-        fc, own = self._corr_handle(reference, radius)
-        stream = self._corr_stream(z0, n, batch, fc)
-        try:
-            yield from stream
-        finally:
-            stream.close()
-            if own:
-                fc.close()
-
-    # ---- binned frame traces (rc_bins_frames): per frame and bin of a label map the set pixels and their summed values ---------------------
-    def _bins_handle(self, labels, n_bins):
-        """(the _lib.FrameBins to use, whether this call made it): a caller's handle as it is - its shape must be the file's"""
-        nx, ny = int(self._header['nx']), int(self._header['ny'])
-        if isinstance(labels, _lib.FrameBins):
-            if (labels.nx, labels.ny) != (nx, ny):
-                raise ValueError('binned frame traces: a FrameBins of %d x %d for frames of %d x %d' % (labels.nx, labels.ny, nx, ny))
-            return labels, False
-        if labels is None:
-            raise ValueError('binned frame traces: labels are needed - an integer (ny, nx) array or GPU tensor, or a FrameBins')
-        return _lib.FrameBins(nx, ny, labels, n_bins), True
+        yield from self._corr_stream(z0, n, batch, reference, radius)
 
     def _bins_dict(self, first, k, cells):
         """a batch's int64[k, 2, B] as the dict get_frame_bins returns (copies of their own)"""
-        ids = self.part_frame_ids[first:first + k].astype(np.int64) if self._is_intermediate else np.arange(first, first + k, dtype=np.int64)
-        return {'count': cells[:, 0].copy(), 'sum': cells[:, 1].copy(), 'frame_ids': ids}
+        return {'count': cells[:, 0].copy(), 'sum': cells[:, 1].copy(), 'frame_ids': self._frame_ids(first, k)}
 
-    def _bins_stream(self, z0, n, batch, fb):
-        """The engine of get_frame_bins and iter_frame_bins: the batches go down the ladder as _Bins (rc_bins_frames_submit /
-        rc_expand_frames_wait on the two slots); 16 * B bytes per frame cross the link.  Yields (first frame, dict).  Routes and fall-backs
-        are the summed views' (sum_frames)."""
-        return self._ladder(_Bins(fb, self._bufs.stream, self._bins_dict), _jobs(z0, n, batch))
+    def _bins_stream(self, z0, n, batch, labels, n_bins):
+        def make(nx, ny):
+            if labels is None:
+                raise ValueError('binned frame traces: labels are needed - an integer (ny, nx) array or GPU tensor, or a FrameBins')
+            return _lib.FrameBins(nx, ny, labels, n_bins)
+        return self._table_stream(z0, n, batch, self._BINS, labels, _lib.FrameBins, make, self._bins_dict)
 
     def get_frame_bins(self, z0, n, labels=None, n_bins=None):
         """Per frame of z0 .. z0+n-1 of a merged file (records of a part file) and per bin of the label map the number of set pixels and the
@@ -1769,29 +1693,13 @@ class BatchedAccess:
         copy.  bin_areas(labels, B) is the denominator of a mean profile.  Routes (last_batch_path) and fall-backs as for sum_frames; files of
         more than 16 bits are not taken (NotImplementedError)."""
         n = self._frame_range(z0, n)
-        self._check_levels_and_bits(*self._BINS)
-        fb, own = self._bins_handle(labels, n_bins)
-        stream = self._bins_stream(z0, n, n, fb)      # (one batch of n frames)
-        try:
-            return next(stream)[1]
-        finally:
-            stream.close()
-            if own:
-                fb.close()
+        return self._only_batch(self._bins_stream(z0, n, n, labels, n_bins))
 
     def iter_frame_bins(self, z0=0, n=None, batch=64, labels=None, n_bins=None):
         """get_frame_bins for a whole file, streamed: yields (first frame index, dict) per batch of up to `batch` frames, two batches in
         flight (rc_bins_frames_submit / rc_expand_frames_wait).  The arrays are copies of their own."""
         n = self._frame_range(z0, n, batch)
-        self._check_levels_and_bits(*self._BINS)
-        fb, own = self._bins_handle(labels, n_bins)
-        stream = self._bins_stream(z0, n, batch, fb)
-        try:
-            yield from stream
-        finally:
-            stream.close()
-            if own:
-                fb.close()
+        yield from self._bins_stream(z0, n, batch, labels, n_bins)
 
     def get_frames_coo(self, z0, n, out=None):
         """get_frames_triplets in the COO layout: (nnz_prefix, (rows int32, columns int32, values uint16 - uint32 for a level-1 file of

@@ -1,13 +1,10 @@
 // corr_index_check.cpp - the host build of pyrecode_amd/csrc/rc_corr.h as a stand-alone program (tests/test_corr_cpu.py builds it, also
-// under AddressSanitizer / UBSan, and compares its answers with the arithmetic restated in Python integers, tests/corr_model.py), and the
-// row of rc_read_plan.h that the correlation kind adds.
+// under AddressSanitizer / UBSan, and compares its answers with the arithmetic restated in Python integers, tests/corr_model.py).
 // Reads cases from standard input, one per line, and answers each with one line:
 //   s R                                   -> side, cells, accumulators a lane keeps
 //   g nx ny R row col cell                -> cells of the padded reference, the window's base, the cell's offset
 //   w nb8 n R                             -> blocks a workgroup walks, workgroups per frame, bytes of the partial rows
 //   b nx ny level d bound n bytes_0 ..    -> 1 if the batch keeps to the no-wrap rule, else 0
-//   k                                     -> RK_CORR's row: esz coo stats counts sums cells held | its synchronous route | late(plain) late(inflate)
-//                                            | segments, offset and bytes of a 1000-byte output's copy-back at totals 0 and 7
 // Prints "ok" at the end; the exit status is 1 for a line it cannot read.
 #include <inttypes.h>
 #include <stdint.h>
@@ -17,7 +14,6 @@
 #include <vector>
 
 #include "../../pyrecode_amd/csrc/rc_corr.h"
-#include "../../pyrecode_amd/csrc/rc_read_plan.h"
 
 int main()
 {
@@ -44,12 +40,6 @@ int main()
             for (uint32_t f = 0; f < n; ++f)
                 if (scanf("%" SCNu32, &sizes[3 * (size_t)f + 2]) != 1) return 1;
             printf("%d\n", rc::corr_batch_fits(nx, ny, level, d, bound, sizes.data(), n) ? 1 : 0);
-        } else if (kind == 'k') {
-            const rc::ReadKindInfo i = rc::read_kind_info(rc::RK_CORR);
-            const rc::CopyPlan p0 = rc::read_copy_plan(rc::RK_CORR, 7, 0, 1000), p7 = rc::read_copy_plan(rc::RK_CORR, 7, 7, 1000);
-            printf("%u %u %d %d %d %d %d | %u | %d %d | %u %" PRIu64 " %" PRIu64 " %u %" PRIu64 " %" PRIu64 " | %d\n", i.esz, i.coo, i.stats, i.counts, i.sums,
-                   i.cells, i.held, (unsigned)rc::verdict_route_sync(i), rc::read_copy_is_late(rc::RK_CORR, false), rc::read_copy_is_late(rc::RK_CORR, true),
-                   p0.nseg, p0.seg[0].off, p0.seg[0].bytes, p7.nseg, p7.seg[0].off, p7.seg[0].bytes, i.pageable && strstr(i.pageable, "rc_corr_frames_submit") ? 1 : 0);
         } else
             return 1;
     }

@@ -12,7 +12,15 @@
 
 using namespace rc;
 
-static const char *const KIND[RK_KINDS] = {"triplets", "coo16", "coo32", "l2", "events", "sum", "counted_sum", "dense", "trace"};
+static_assert(RK_KINDS == 11, "a new kind: a row in every table below");
+static const char *const KIND[RK_KINDS] = {"triplets", "coo16", "coo32", "l2", "events", "sum", "counted_sum", "dense", "trace", "corr", "bins"};
+// the entry point a kind's `pageable` message names, and speaks for (the four kinds of entries share rc_expand_frames_submit's; a sum has no output)
+static const char *const SUBMIT[RK_KINDS] = {"rc_expand_frames_submit: ", "rc_expand_frames_submit: ", "rc_expand_frames_submit: ", "rc_expand_frames_submit: ",
+                                             "rc_count_frames_submit: ", nullptr, nullptr, "rc_expand_frames_dense_submit: ", "rc_trace_frames_submit: ",
+                                             "rc_corr_frames_submit: ", "rc_bins_frames_submit: "};
+// the kinds whose output is cells of a size the arguments give, all of them copied back whatever the total ... and those held back behind the verdict
+static bool is_cells(uint32_t k) { return k == RK_DENSE || k == RK_TRACE || k == RK_CORR || k == RK_BINS; }
+static bool is_held(uint32_t k) { return k == RK_EVENTS || is_cells(k); }
 static int failures = 0;
 
 // a verdict row: per error word 0..15 the statuses for total < cap, == cap, > cap - O = RC_OK, U = RC_ERR_UNSUPPORTED, C = RC_ERR_CORRUPT,
@@ -78,20 +86,21 @@ static void check_plan(const char *what, ReadKind k, uint64_t total, const CopyP
 int main()
 {
     // ---- what a kind means for the kernels: esz (line 161), values (line 176), klevel (line 177) -------------------------------------------
-    const uint32_t esz[RK_KINDS] = {24, 10, 12, 8, 20, 0, 0, 0, 0};      // (0: no entries - the kinds whose capacity was ~0 or unused)
-    const uint32_t coo[RK_KINDS] = {0, 2, 4, 2, 0, 0, 0, 0, 0};          // (the entry points' `coo` argument, lines 722, 738, 753)
+    const uint32_t esz[RK_KINDS] = {24, 10, 12, 8, 20, 0, 0, 0, 0, 0, 0};      // (0: no entries - the kinds whose capacity was ~0 or unused)
+    const uint32_t coo[RK_KINDS] = {0, 2, 4, 2, 0, 0, 0, 0, 0, 0, 0};          // (the entry points' `coo` argument, lines 722, 738, 753)
     for (uint32_t i = 0; i < RK_KINDS; ++i) {
         const ReadKind k = (ReadKind)i;
         const ReadKindInfo info = read_kind_info(k);
         const bool l2 = k == RK_L2;
         bool ok = info.esz == esz[i] && info.coo == coo[i] && info.stats == l2;
         ok = ok && info.counts == (k == RK_EVENTS || k == RK_COUNTED_SUM) && info.sums == (k == RK_SUM || k == RK_COUNTED_SUM);
-        ok = ok && info.cells == (k == RK_DENSE || k == RK_TRACE) && info.held == (k == RK_EVENTS || k == RK_DENSE || k == RK_TRACE);
+        ok = ok && info.cells == is_cells(i) && info.held == is_held(i);
         // (lines 176-177 say "level == 1 || l2out" and "level == 1 ? 1 : l2out ? 2 : 3": the level-2 kind at level 3 - refused before, line 167 -
         // answers as at level 2)
         ok = ok && read_kind_klevel(k, 1) == 1 && read_kind_klevel(k, 2) == (l2 ? 2u : 3u) && read_kind_klevel(k, 3) == (l2 ? 2u : 3u);
         ok = ok && read_kind_values(k, 1) && read_kind_values(k, 2) == l2 && read_kind_values(k, 3) == l2;
-        ok = ok && ((info.pageable != nullptr) == (info.esz != 0 || info.cells)) && (!info.pageable || strstr(info.pageable, "page-locked"));
+        ok = ok && ((info.pageable != nullptr) == (esz[i] != 0 || is_cells(i))) && (info.pageable != nullptr) == (SUBMIT[i] != nullptr);
+        ok = ok && (!info.pageable || (strncmp(info.pageable, SUBMIT[i], strlen(SUBMIT[i])) == 0 && strstr(info.pageable, "page-locked")));
         if (!ok) { printf("kind %s: wrong info\n", KIND[i]); ++failures; }
     }
     // ---- the verdict ---------------------------------------------------------------------------------------------------------------------
@@ -115,9 +124,9 @@ int main()
             check_row("sync", VR_SYNC_QUIET, k, SYNC_QUIET, k != RK_SUM, false, false);
         }
     }
-    // ---- the copy-back, cap = 7 entries, a dense / trace output of 1000 bytes ---------------------------------------------------------------
+    // ---- the copy-back, cap = 7 entries, a dense / trace / corr / bins output of 1000 bytes -------------------------------------------------
     // triplets: one copy of total * 24 (lines 696, 794); COO: rows, columns, values cap entries apart (lines 686-688, 796-799; level 2: no
-    // values); events: copy_events, lines 123-129; dense / trace: all bytes whatever the total (lines 604, 787); a sum: nothing
+    // values); events: copy_events, lines 123-129; dense / trace / corr / bins: all bytes whatever the total (lines 604, 787); a sum: nothing
     const uint64_t cap = 7, cells = 1000, totals[3] = {0, 1, 7};
     const Seg t1[] = {{0, 24}}, t7[] = {{0, 168}};
     const Seg c16_1[] = {{0, 4}, {28, 4}, {56, 2}}, c16_7[] = {{0, 28}, {28, 28}, {56, 14}};
@@ -126,11 +135,11 @@ int main()
     const Seg ev_1[] = {{0, 8}, {56, 4}, {84, 4}, {112, 4}}, ev_7[] = {{0, 56}, {56, 28}, {84, 28}, {112, 28}};
     const Seg all[] = {{0, 1000}};
     const struct { uint32_t nseg; const Seg *one, *full; } want[RK_KINDS] = {{1, t1, t7}, {3, c16_1, c16_7}, {3, c32_1, c32_7}, {2, l2_1, l2_7}, {4, ev_1, ev_7},
-                                                                              {0, nullptr, nullptr}, {0, nullptr, nullptr}, {1, all, all}, {1, all, all}};
+                                                                              {0, nullptr, nullptr}, {0, nullptr, nullptr}, {1, all, all}, {1, all, all},
+                                                                              {1, all, all}, {1, all, all}};
     for (uint32_t i = 0; i < RK_KINDS; ++i)
         for (int j = 0; j < 3; ++j) {
-            const bool is_cells = i == RK_DENSE || i == RK_TRACE;
-            const uint32_t nseg = (j == 0 && !is_cells) ? 0 : want[i].nseg;
+            const uint32_t nseg = (j == 0 && !is_cells(i)) ? 0 : want[i].nseg;
             check_plan("copy-back", (ReadKind)i, totals[j], read_copy_plan((ReadKind)i, cap, totals[j], cells), nseg, j == 2 ? want[i].full : want[i].one);
         }
     // a submit's eager copy (line 641): cap * esz bytes in one piece, nothing for cap 0; late (lines 537, 589, 640): the held kinds always,
@@ -141,8 +150,7 @@ int main()
         check_plan("early copy", (ReadKind)i, 0, read_copy_plan_early((ReadKind)i, 0), 0, nullptr);
     }
     for (uint32_t i = 0; i < RK_KINDS; ++i) {
-        const bool held = i == RK_EVENTS || i == RK_DENSE || i == RK_TRACE;
-        if (read_copy_is_late((ReadKind)i, false) != held || !read_copy_is_late((ReadKind)i, true)) { printf("%s: wrong early / late\n", KIND[i]); ++failures; }
+        if (read_copy_is_late((ReadKind)i, false) != is_held(i) || !read_copy_is_late((ReadKind)i, true)) { printf("%s: wrong early / late\n", KIND[i]); ++failures; }
     }
     if (failures) { printf("%d answers wrong\n", failures); return 1; }
     printf("ok\n");

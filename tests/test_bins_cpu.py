@@ -150,8 +150,6 @@ def _cases():
     assert want[head + 4] == "128 8 %d" % (64 * 8 * 2 * 4096 * 8) == "128 8 33554432"
     # 2048 frames of 192 x 256 (three blocks): two chunks - blocks 0, 1 and block 2 - at B = 17, one chunk at B = 4096 (512 workgroups aimed for)
     assert want[head + 7] == "2 2 %d" % (2048 * 2 * 2 * 17 * 8) and want[head + 8] == "3 1 %d" % (2048 * 2 * 4096 * 8)
-    lines.append("k")
-    want.append("0 0 0 0 0 1 1 | 3 | 1 1 | 1 0 1000 1 0 1000 | 1 | 1 1 1")     # cells of the arguments' size, held back; the quiet route; late; all its bytes; behind RK_CORR, RK_KINDS as it was
     return lines, want
 
 
